@@ -5,7 +5,7 @@ One "step" = one pass of the hot path (2-stage sdy x4 cascade, one fused kernel 
 synthetic 1080p LR frames already resident in HBM: LR 1080x1920x3 -> HR 4320x7680x3 per frame.
 `value` = HR output Mpixels/s of the whole job (LR-input Mpix/s = value / 16).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 
 N > 1 launches N ranks itself (python -m torch.distributed.run ... bench.py, before this process touches the GPU) unless
 it already runs under torchrun (WORLD_SIZE set).  Multi-GPU: frames are independent units (the reference fans images out
@@ -33,6 +33,36 @@ LDS_PEAK_GBS = 256 * 256 * CLOCK_GHZ   # 256 B/clk/CU for ds_read_b64/b128 (MI35
 STAGES, MODES, SCALE = 2, "sdy", 4
 REAL_PNG = os.path.join(ROOT, "tests", "golden", "DIV2K_LR_X4", "0001x4.png")
 LUT_DIR = os.path.join(ROOT, "tests", "golden", "luts")
+DUMP_SAMPLES = 1 << 22       # --dump-outputs: HR values in the seeded sample (16 MB as float32)
+DUMP_SUMS = 1 << 22          # --dump-outputs: at most this many row sums (32 MB as float64)
+DUMP_SEED = 2024
+
+
+def dump_index(numel):
+    """Sorted flat indices of the HR batch that --dump-outputs samples: fixed by DUMP_SEED and the batch size alone."""
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, numel, min(DUMP_SAMPLES, numel)))
+
+
+def dump_outputs(dirpath, out):
+    """--dump-outputs: the HR batch the timed path returned in its last step (uint8 [F, H, W, C], far beyond 64 MB at the bench size),
+    as float .npy files two builds can be compared by.  hr_row_sums.npy: the sum of every HR row, frame-major (consecutive rows summed
+    together once there are more than DUMP_SUMS rows), exact in float64, so every output byte counts.  hr_sample.npy: the values at
+    dump_index(), float32.  Reduced frame by frame on the device: a whole-batch reduction would first cast the batch to int64."""
+    import torch
+    F, R = out.shape[0], out.shape[1]
+    per = out[0].numel()
+    idx = dump_index(out.numel())
+    cuts = np.searchsorted(idx, np.arange(F + 1) * per)
+    sums, sample = [], []
+    for f in range(F):
+        sums.append(out[f].reshape(R, -1).sum(1, dtype=torch.int64))
+        sel = torch.from_numpy(idx[cuts[f]:cuts[f + 1]] - f * per).to(out.device)
+        sample.append(out[f].reshape(-1)[sel])
+    sums = torch.cat(sums).cpu().numpy()
+    sums = np.add.reduceat(sums, np.arange(0, sums.size, -(-sums.size // DUMP_SUMS)))
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "hr_row_sums.npy"), sums.astype(np.float64))
+    np.save(os.path.join(dirpath, "hr_sample.npy"), torch.cat(sample).cpu().numpy().astype(np.float32))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -184,7 +214,13 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=[2, 4, 5],
                     help="2: headline (2-stage sdy x4); 4: LUT fine-tune step (fwd + bwd + Adam, bs 256 x 1x48x48); "
                          "5: deep cascade (4-stage sdy x2, seeded synthetic tables), eager vs hipGraph")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="config 2: after the timed steps, write what the last step computed as DIR/*.npy (rank 0's batch; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs is implemented for config 2 only")
     global ROLLED_BATCH
     ROLLED_BATCH = args.batch == "rolled"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -267,6 +303,8 @@ def main():
     elapsed = timed(lambda: run_step(x), args.steps)
     value = world * F * H * SCALE * W * SCALE * args.steps / elapsed / 1e6
     ms_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:       # before the legs below write into `out` again
+        dump_outputs(args.dump_outputs, out)
 
     if cpu_rec is not None:
         cpu_rec["matches_gpu"] = bool(np.array_equal(out[0].cpu().numpy(), cpu_full))

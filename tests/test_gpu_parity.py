@@ -639,6 +639,29 @@ def test_bench_multi_rank_path_rehearsal(tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_step_of_the_timed_path(tmp_path, shipped_luts):
+    """bench.py --dump-outputs: float .npy files of what the timed steps computed, equal to the CPU oracle on the same seeded batch;
+    --steps is the number of timed steps and the line carries ms_per_step."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    F, H, W = 2, 270, 480
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--frames", str(F), "--launch-frames", str(F), "--lr-h", str(H),
+           "--lr-w", str(W), "--steps", "3", "--warmup", "1", "--cpu-crop", "0", "--skip-other", "--skip-strips", "--dump-outputs", str(tmp_path / "d")]
+    res = subprocess.run(cmd, env=dict(os.environ, MULUT_NO_BUILD="1"), capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert res.returncode == 0, res.stderr[-2000:]
+    rec = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path / "d")) == ["hr_row_sums.npy", "hr_sample.npy"]
+    want = np.stack([c_oracle.pipeline(shipped_luts, 2, "sdy", 4, f) for f in bench.make_batch("natural", F, H, W, seed=0)])
+    sums, sample = np.load(tmp_path / "d" / "hr_row_sums.npy"), np.load(tmp_path / "d" / "hr_sample.npy")
+    assert sums.dtype == np.float64 and np.array_equal(sums, want.reshape(F * H * 4, -1).sum(1, dtype=np.int64))
+    assert sample.dtype == np.float32 and np.array_equal(sample, want.reshape(-1)[bench.dump_index(want.size)])
+
+
+@pytest.mark.gpu
 def test_large_batch_runs_as_sub_batches(eng, shipped_luts):
     """A batch whose stage input passes 2^28 bytes is split by mulut_pipeline (the detailed-tile work lists index 28 bits):
     same bytes as frame-by-frame calls, on detailed content, and no slower path (the anchor-slab kernels still run)."""
