@@ -5,13 +5,17 @@ One "step" = one pass of the hot path (2-stage sdy x4 cascade, one fused kernel 
 synthetic 1080p LR frames already resident in HBM: LR 1080x1920x3 -> HR 4320x7680x3 per frame.
 `value` = HR output Mpixels/s of the whole job (LR-input Mpix/s = value / 16).
 
-  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: it builds the batch, warms up, times the K steps, writes
+--dump-outputs and prints the result line.  --full also runs, after the headline, the legs beside it: the CPU baseline,
+per-stage and per-kernel timing for the roofline, the other input distributions, config 3 and configs 4 and 5 in brief.
 
 N > 1 launches N ranks itself (python -m torch.distributed.run ... bench.py, before this process touches the GPU) unless
 it already runs under torchrun (WORLD_SIZE set).  Multi-GPU: frames are independent units (the reference fans images out
 with Pool(24).map, sr/4_test_lut.py:257-259), so each rank processes its own batch with no data-path collective: weak
 scaling -- that is `value`.  The north star's other sharding -- each frame cut into one strip per GPU (+halo), the HR
-strips gathered on rank 0 over RCCL -- is timed in the same run on LR 2160x3840 batches (config 3) and reported under
+strips gathered on rank 0 over RCCL -- is timed by --full on LR 2160x3840 batches (config 3) and reported under
 config["strips_gather"].  The oracle is imported only by the cpu_baseline leg.
 """
 import argparse
@@ -206,9 +210,12 @@ def main():
     ap.add_argument("--dist", choices=["natural", "noise", "real"], default="natural",
                     help="natural: smooth synthetic field (headline); noise: uniform random bytes (worst case); "
                          "real: the DIV2K LR photo the reference ships, mirror-tiled")
-    ap.add_argument("--cpu-crop", type=int, default=512, help="window edge for the single-core CPU baseline (0 = skip the CPU legs)")
-    ap.add_argument("--skip-other", action="store_true", help="do not also time the other input distributions")
-    ap.add_argument("--skip-strips", action="store_true", help="N > 1: do not also time the strips + gather sharding (config 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="config 2: after the headline, also run the legs beside it: the CPU baseline, per-stage and per-kernel timing for the "
+                         "roofline, the other input distributions, config 3 and configs 4 and 5 in brief (a plain run times the headline alone)")
+    ap.add_argument("--cpu-crop", type=int, default=512, help="--full: window edge for the single-core CPU baseline (0 = skip the CPU legs)")
+    ap.add_argument("--skip-other", action="store_true", help="--full: do not also time the other input distributions and configs")
+    ap.add_argument("--skip-strips", action="store_true", help="--full: do not also time config 3 (N > 1: the strips + gather sharding)")
     ap.add_argument("--strip-frames", type=int, default=4, help="LR 2160x3840 frames per step of the strips + gather leg")
     ap.add_argument("--strips-timeout", type=int, default=240, help="seconds the strips + gather leg may take before the headline is printed without it")
     ap.add_argument("--config", type=int, default=2, choices=[2, 4, 5],
@@ -240,7 +247,7 @@ def main():
 
     # CPU legs first: the Pool forks, which must happen before this process initialises the GPU
     cpu_rec = cpu_full = None
-    if world == 1 and args.cpu_crop > 0 and args.config == 2:
+    if args.full and world == 1 and args.cpu_crop > 0 and args.config == 2:
         cpu_rec, cpu_full = cpu_baseline_host(luts, host[0], min(args.cpu_crop, H, W))
 
     import torch
@@ -310,17 +317,18 @@ def main():
         cpu_rec["matches_gpu"] = bool(np.array_equal(out[0].cpu().numpy(), cpu_full))
         del cpu_full
 
-    # per-stage and per-dominant-kernel device time: HIP events the library records on the launch stream
-    eng.set_stage_timing(True)
-    per_stage, per_kernel = [], []
-    for _ in range(max(2, args.steps // calls)):
-        run_step(x, each=lambda: (per_stage.append(eng.last_stage_ms()), per_kernel.append(eng.last_kernel_ms())))      # per call of LF frames
-    eng.set_stage_timing(False)
-    ms_stage = np.mean(np.asarray(per_stage), axis=0)
-    ms_kernel = np.mean(np.asarray(per_kernel), axis=0)
+    # --full: per-stage and per-dominant-kernel device time: HIP events the library records on the launch stream
+    if args.full:
+        eng.set_stage_timing(True)
+        per_stage, per_kernel = [], []
+        for _ in range(max(2, args.steps // calls)):
+            run_step(x, each=lambda: (per_stage.append(eng.last_stage_ms()), per_kernel.append(eng.last_kernel_ms())))      # per call of LF frames
+        eng.set_stage_timing(False)
+        ms_stage = np.mean(np.asarray(per_stage), axis=0)
+        ms_kernel = np.mean(np.asarray(per_kernel), axis=0)
 
     others = {}
-    if not args.skip_other:
+    if args.full and not args.skip_other:
         for other in ("natural", "noise", "real"):
             if other == args.dist or (other == "real" and not os.path.exists(REAL_PNG)):
                 continue
@@ -332,7 +340,7 @@ def main():
             del x2
         if args.dist == "natural" and not ROLLED_BATCH:
             # the batch definition of rounds 1-2 (two draws + rolled copies: their wrap seams are edges the field does not have), so that the
-            # default line carries the number that compares with those rounds
+            # --full line carries the number that compares with those rounds
             ROLLED_BATCH = True
             x2 = torch.from_numpy(make_batch("natural", F, H, W, seed=rank)).cuda()
             ROLLED_BATCH = False
@@ -350,11 +358,12 @@ def main():
         workload = "2-stage sdy x4, %d x LR %dx%dx3 -> HR %dx%dx3 per GPU per step%s, D-%s" % (
             F, H, W, H * SCALE, W * SCALE, "" if calls == 1 else " in %d launches of %d frames" % (calls, LF), args.dist)
         achieved = alg / (ms_step * 1e-3) / 1e9
-        k2_ms = float(ms_kernel[-1]) if ms_kernel[-1] > 0 else float(ms_stage[-1])
-        counters = load_profile_json("kernel_counters.json", workload if world == 1 else None) if world == 1 else None
         traffic = load_profile_json("hbm_traffic.json", workload) if world == 1 else None
-        secondary = None
-        issue = load_profile_json("valu_issue.json")
+        counters = secondary = None
+        if args.full:
+            k2_ms = float(ms_kernel[-1]) if ms_kernel[-1] > 0 else float(ms_stage[-1])
+            counters = load_profile_json("kernel_counters.json", workload if world == 1 else None) if world == 1 else None
+            issue = load_profile_json("valu_issue.json")
         if counters:
             k2 = counters["final_stage_kernel"]
             scale_f = LF / float(counters.get("frames", LF))      # the counters were collected at counters["frames"] frames per launch
@@ -394,16 +403,18 @@ def main():
             "roofline": {"bound": "hbm", "kernel": "fused 2-stage pipeline: %s | %s" % (eng.kernel_name(False), eng.kernel_name(True)),
                          "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
                          "traffic": traffic.get("pipeline_bytes_per_step") * calls if traffic else None,      # (the JSON holds bytes per launch of every kernel)
-                         "algorithmic_bytes_per_step": alg,
-                         "stage_ms": [round(float(v), 4) for v in ms_stage],
-                         "dominant_kernel": {"name": "stage_tube2_kernel<rgb>" if "tube2" in eng.kernel_name(True) else "stage_tube_kernel<rgb>" if "tube" in eng.kernel_name(True) else eng.kernel_name(True),
-                                             "ms": round(k2_ms, 4), "algorithmic_bytes_per_launch": alg_k2,
-                                             "achieved": round(alg_k2 / (k2_ms * 1e-3) / 1e9, 2),
-                                             "kernel_frac": round(alg_k2 / (k2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                                             "traffic": traffic.get("final_stage_bytes_per_launch") if traffic else None},
-                         "first_stage_kernel_ms": round(float(ms_kernel[0]), 4),
-                         "secondary": secondary},
+                         "algorithmic_bytes_per_step": alg},
         }
+        if args.full:      # the figures that take timed launches of their own
+            rec["roofline"].update({
+                "stage_ms": [round(float(v), 4) for v in ms_stage],
+                "dominant_kernel": {"name": "stage_tube2_kernel<rgb>" if "tube2" in eng.kernel_name(True) else "stage_tube_kernel<rgb>" if "tube" in eng.kernel_name(True) else eng.kernel_name(True),
+                                    "ms": round(k2_ms, 4), "algorithmic_bytes_per_launch": alg_k2,
+                                    "achieved": round(alg_k2 / (k2_ms * 1e-3) / 1e9, 2),
+                                    "kernel_frac": round(alg_k2 / (k2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                    "traffic": traffic.get("final_stage_bytes_per_launch") if traffic else None},
+                "first_stage_kernel_ms": round(float(ms_kernel[0]), 4),
+                "secondary": secondary})
         if cpu_rec is not None:
             rec["cpu_baseline"] = cpu_rec
 
@@ -413,7 +424,7 @@ def main():
     # it: an exception is recorded, and a watchdog prints the record without the leg and ends every rank with exit code 3 if the exchange
     # has not come back in time.
     strips = None
-    if not args.skip_strips:
+    if args.full and not args.skip_strips:
         import threading
         lock, state = threading.Lock(), {"printed": False}
 
@@ -439,7 +450,7 @@ def main():
                 return
             state["printed"] = True
     extra = None
-    if not args.skip_other and world == 1:
+    if args.full and not args.skip_other and world == 1:
         del x, out
         torch.cuda.empty_cache()
         extra = other_configs(args, world, rank, local, timed)
@@ -649,7 +660,7 @@ def config5(args, world, rank, local, timed, size=None, steps=None):
 
 
 def other_configs(args, world, rank, local, timed):
-    """Configs 4 and 5 in brief, for the default line's config.other_configs (the driver only runs the default line)."""
+    """Configs 4 and 5 in brief, for config.other_configs of the --full line."""
     out = {}
     for name, fn in (("config5_p1", lambda: config5(args, world, rank, local, timed, size=(8, 1080, 1920), steps=10)),
                      ("config5_small_frames", lambda: config5(args, world, rank, local, timed, size=(8, 270, 480), steps=50)),

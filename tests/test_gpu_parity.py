@@ -623,7 +623,7 @@ def test_bench_multi_rank_path_rehearsal(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--frames", "2", "--steps", "2", "--warmup", "1",
-           "--cpu-crop", "0", "--skip-other", "--lr-h", "270", "--lr-w", "480", "--strip-frames", "2"]
+           "--full", "--cpu-crop", "0", "--skip-other", "--lr-h", "270", "--lr-w", "480", "--strip-frames", "2"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -659,6 +659,33 @@ def test_bench_dump_outputs_are_the_last_step_of_the_timed_path(tmp_path, shippe
     sums, sample = np.load(tmp_path / "d" / "hr_row_sums.npy"), np.load(tmp_path / "d" / "hr_sample.npy")
     assert sums.dtype == np.float64 and np.array_equal(sums, want.reshape(F * H * 4, -1).sum(1, dtype=np.int64))
     assert sample.dtype == np.float32 and np.array_equal(sample, want.reshape(-1)[bench.dump_index(want.size)])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_alone_and_full_adds_the_legs(tmp_path):
+    """A plain bench.py run prints the headline without the legs beside it; --full runs them after the same timed steps: the CPU
+    baseline (compared with the GPU's frame), per-stage and per-kernel timing in the roofline, and config 3."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--frames", "2", "--launch-frames", "2", "--lr-h", "270", "--lr-w", "480",
+            "--steps", "2", "--warmup", "1", "--skip-other", "--strip-frames", "1"]
+    recs = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--cpu-crop", "32"])):
+        res = subprocess.run(base + extra, env=dict(os.environ, MULUT_NO_BUILD="1"), capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, res.stdout[-2000:]
+        recs[name] = json.loads(lines[0])
+    plain, full = recs["plain"], recs["full"]
+    for rec in (plain, full):
+        assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["steps"] == 2 and rec["warmup"] == 1 and rec["dtype"] == "u8"
+        assert rec["roofline"]["frac"] > 0
+    assert "cpu_baseline" not in plain and "strips_gather" not in plain["config"] and "stage_ms" not in plain["roofline"]
+    assert full["cpu_baseline"]["matches_gpu"] is True and full["cpu_baseline"]["tiles_match_window"] is True
+    assert len(full["roofline"]["stage_ms"]) == 2 and full["roofline"]["dominant_kernel"]["ms"] > 0
+    assert full["config"]["strips_gather"]["value"] > 0
 
 
 @pytest.mark.gpu

@@ -3,7 +3,7 @@
 # (build/ubench_stream and build/ubench_ifetch are built in the authoring container: tools/asm_stats.sh stage_tube2_kernelILi2 &&
 #  python tools/ubench/gen_stream_ubench.py build/asm/kernel.s > build/ubench_stream.hip && hipcc ... ; the probe library by
 #  python tools/prof_phases.py --build-only)
-#   gpurun_out/<tag>_bench.json (default bench.py line), _config4.json, _config5.json, _finetune_stats.csv + ft_pmc_<tag>/ (fine-tune step),
+#   <tag>_bench.json (the bench.py --full line), _config4.json, _config5.json, _finetune_stats.csv + ft_pmc_<tag>/ (fine-tune step),
 #   prof_<tag>/ (tools/prof_round.sh: kernel stats + PMC of the bench workload), <tag>_tube2_phases.json, <tag>_ubench_stream.txt, <tag>_ubench_ifetch.txt
 set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -35,7 +35,7 @@ ks = {k: {c: v["mean_per_dispatch"] for c, v in d[k].items()} for k in d if "ft_
 json.dump({"source_hash": _native.source_hash(), "tag": sys.argv[2], "workload": "bench.py --config 4", "kernels": ks}, open("profiles/finetune_counters.json", "w"), indent=1)
 print("finetune_counters:", list(ks))
 PY
-timeout -k 10 900 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
+timeout -k 10 900 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
 timeout -k 10 200 python bench.py --config 4 > $O/${TAG}_config4.json 2>> $O/${TAG}_bench.err; echo "config4 rc=$?"
 timeout -k 10 300 python bench.py --config 5 --frames 8 > $O/${TAG}_config5.json 2>> $O/${TAG}_bench.err; echo "config5 rc=$?"
 timeout -k 10 400 python bench.py --batch rolled --skip-other --skip-strips --cpu-crop 0 > $O/${TAG}_bench_rolled_batch.json 2>> $O/${TAG}_bench.err; echo "bench (rolled batch) rc=$?"
