@@ -1,6 +1,6 @@
 /*
  * mulut.h -- C ABI of libmulut_hip.so: MuLUT LUT inference (4D LUT retrieval + 4-simplex
- * interpolation over rotated s/d/y patches, cascaded stages) on AMD MI355X (gfx950).
+ * interpolation over rotated s/d/y/e/h/o patches, cascaded stages) on AMD MI355X (gfx950).
  *
  * This is the drop-in boundary for the hot path of the reference's `sr/4_test_lut.py`.  The
  * reference is pure Python and has no FFI layer; each entry point below states which reference
@@ -37,7 +37,7 @@ extern "C" {
 enum {
     MULUT_OK = 0,
     MULUT_EINVAL = -1,      /* bad argument (NULL pointer, non-positive size, ...)             */
-    MULUT_EMODE = -2,       /* mode not in {s,d,y}: reference raises ValueError, 4_test_lut.py:54 */
+    MULUT_EMODE = -2,       /* mode not in {s,d,y,e,h,o}: reference raises ValueError, 4_test_lut.py:54 */
     MULUT_ENOLUT = -3,      /* table (stage,mode) not set: reference raises from np.load, :333  */
     MULUT_ESHAPE = -4,      /* table shape does not match (rows, v_num) expected for the stage */
     MULUT_EUNSUPPORTED = -5,/* interval != 4, scale not in 1..4, stages/modes beyond limits    */
@@ -65,12 +65,15 @@ int mulut_destroy(mulut_ctx *ctx);
 
 /* The model shape: replaces the options the reference reads from TestOptions
  * (common/option.py:21-23,17: --stages --modes --interval --scale) at sr/4_test_lut.py:279-287.
- * `modes` is a NUL-terminated string iterated character-wise exactly like `opt.modes` (:287).
+ * `modes` is a NUL-terminated string iterated character-wise exactly like `opt.modes` (:287): any mix and repeat of the
+ * 3 x 3 patterns s, d, y and the 4 x 4 patterns e, h, o (sr/model.py:12, common/network.py:173-215), up to MULUT_MAX_MODES.
+ * A list holding e, h or o is "wide": its keys reach 3 pixels from the anchor, and every stage of it runs on the wide kernels
+ * (one table in LDS per mode for 1-byte rows, full-table gathers for u*u-byte rows); a list of s, d, y only runs as before.
  * Only interval == 4 (q=16, L=17, 83521 rows) is supported -- the only value for which the
  * reference's reader and writers agree on file names. */
 int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, int interval);
 
-/* Upload one table: replaces
+/* Upload one table (any of the six patterns): replaces
  *   lutDict["s{stage}_{mode}"] = np.load(path).astype(np.float32).reshape(-1, v_num)
  * (sr/4_test_lut.py:322-333).  `host_rows` is the int8 C-order content of the .npy file,
  * rows = 17^4 = 83521, vnum = scale*scale for the last stage, 1 otherwise.  stage is 1-based. */
@@ -109,8 +112,8 @@ int mulut_pipeline(mulut_ctx *ctx, const uint8_t *in, uint8_t *out, int N, int H
 int mulut_pipeline_rows(mulut_ctx *ctx, const uint8_t *in, int in_row0, int in_rows, uint8_t *out, int y0, int y1,
                         int N, int H_full, int W, int C, int layout, void *stream);
 
-/* LR rows of context needed above/below a strip for the configured cascade (2 per stage: the
- * reach of the d / y patterns over the four rotations). */
+/* LR rows of context needed above/below a strip for the configured cascade: 2 per stage (the reach of the d / y patterns
+ * over the four rotations), 3 per stage for a wide mode list (e, h, o). */
 int mulut_halo(const mulut_ctx *ctx);
 
 /* Pre-size the intermediate-stage workspace and every device work list so that later pipeline calls of at most this shape
@@ -142,7 +145,8 @@ int mulut_debug_read(mulut_ctx *ctx, unsigned long long *out, int cap, int reset
 
 /* ---- LUT-aware fine-tuning (the differentiable twin; stateless, float32) -----------------------------
  * One stage of MuLUT.forward (sr/model.py:289-312) = InterpTorchBatch (:69-287) over all modes x 4 rotations
- * with the per-pass BPDA rounding (:308) and the stage's clamp/round (:309).
+ * with the per-pass BPDA rounding (:308) and the stage's clamp/round (:309).  Modes s, d, y only: e, h, o return MULUT_EMODE
+ * (the input-gradient tiles stage a 2-pixel halo; the reference's module raises for them too, sr/model.py:121).
  *   weights_q : M device pointers, the QUANTISED tables clamp(round(w*127),-127,127) as float32 [83521][u*u]
  *               (sr/model.py:74-76 -- done by the caller, which also applies that step's backward)
  *   x         : device float32 [B][C][H][W] in 0..255 (the module multiplies its input by 255, :290)
@@ -205,6 +209,8 @@ int mulut_eval_y(int device, const void *gt_hwc, const void *out_hwc, int H, int
  * "first_stage_detail_per_1024": tile threshold of first_stage_kernel 0 (default 24).
  * "u1t_persist" (experiments): 0 (default) = one workgroup per tile of the 1-byte-row tube kernel, 1..8 = that many persistent
  *   workgroups per CU walking XCD-contiguous tile ranges.  Per context, like every other key.
+ * Wide mode lists (e, h, o): every key above is accepted and stored, but does not change their route -- all their stages run on
+ *   the wide kernels (stage_wide1_kernel, stage_wide_up_kernel), which have no tube, hybrid, slab or work-list variants.
  * Unknown key or value: MULUT_EINVAL.
  * hipGraph capture: call mulut_reserve() for the largest (N, H, W, C) first -- the context's workspace, verdict and work-list
  * buffers are then never reallocated by smaller calls; a LARGER later call reallocates them and invalidates graphs captured

@@ -31,7 +31,8 @@ struct mulut_ctx {
     char modes[MULUT_MAX_MODES + 1] = {0};
     signed char di[MULUT_MAX_MODES][3], dj[MULUT_MAX_MODES][3];
     int reach = 2;  // LR rows one stage looks beyond its output rows
-    DevTable tab[MULUT_MAX_STAGES][3];  // [stage-1][pattern id s,d,y]
+    bool wide = false;  // the mode list holds a 4 x 4 pattern (e, h, o): reach 3, every stage on the wide kernels (mulut_wide.hip)
+    DevTable tab[MULUT_MAX_STAGES][6];  // [stage-1][pattern id s,d,y,e,h,o]
     uint8_t *ws[2] = {nullptr, nullptr};
     size_t ws_bytes = 0;
     std::string hip_err;
@@ -74,7 +75,9 @@ struct mulut_ctx {
     int timed_stages = 0;
 };
 
-static int pattern_id(char m) { return m == 's' ? 0 : m == 'd' ? 1 : m == 'y' ? 2 : -1; }
+static int pattern_id(char m) {
+    return m == 's' ? 0 : m == 'd' ? 1 : m == 'y' ? 2 : m == 'e' ? 3 : m == 'h' ? 4 : m == 'o' ? 5 : -1;
+}
 
 #define HIP_TRY(ctx, expr)                                                                  \
     do {                                                                                    \
@@ -164,10 +167,13 @@ int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, in
     const size_t M = strlen(modes);
     if (stages < 1 || stages > MULUT_MAX_STAGES || M < 1 || M > MULUT_MAX_MODES) return MULUT_EUNSUPPORTED;
     if (interval != kInterval || scale < 1 || scale > 4) return MULUT_EUNSUPPORTED;
-    const int reach = 2;  // tiles always stage a 2-px halo (d / y patterns); s-only models use it too
+    // tiles of the s / d / y kernels always stage a 2-px halo (d / y patterns; s-only models use it too); a list with a 4 x 4
+    // pattern (e, h, o) reaches 3 px per stage and runs on the wide kernels
+    int reach = 2;
     for (size_t m = 0; m < M; ++m) {
         int di[3], dj[3];
         if (!pattern_offsets(modes[m], di, dj)) return MULUT_EMODE;
+        reach = imax(reach, pattern_reach(modes[m]));
         for (int k = 0; k < 3; ++k) {
             ctx->di[m][k] = (signed char)di[k];
             ctx->dj[m][k] = (signed char)dj[k];
@@ -179,6 +185,7 @@ int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, in
     ctx->interval = interval;
     memcpy(ctx->modes, modes, M + 1);
     ctx->reach = reach;
+    ctx->wide = reach > 2;
     for (int last = 0; last < 2; ++last) {
         const DivMagic dm = make_div_magic((uint32_t)stage_divisor((int)M, last != 0));
         const int span = 128 * kQ * 4 * (int)M;      // |q * sum| <= 128 * 16 * 4M
@@ -231,7 +238,14 @@ int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows,
     HIP_TRY(ctx, hipMemcpy(t.dev, img.data(), img.size(), hipMemcpyHostToDevice));
     t.vnum = vnum;
     t.bytes = img.size();
-    if (u == 1) {
+    if (pattern_reach(mode) > 2) {
+        // e / h / o tables: the wide kernels gather from the full table only (no tube band, no anchor slabs)
+        if (t.tube) HIP_TRY(ctx, hipFree(t.tube));
+        if (t.slab) HIP_TRY(ctx, hipFree(t.slab));
+        t.tube = nullptr;
+        t.slab = nullptr;
+        t.tube_bytes = 0;
+    } else if (u == 1) {
         // tube band of a 1-byte-row table: one dword per slot, the value as int16 in both halves
         std::vector<uint32_t> tb((size_t)kTube1BandBytes / 4, 0u);
         for (int A = 0; A < kL; ++A)
@@ -441,6 +455,22 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
     a.use_f32 = ctx->f32_ok[last ? 1 : 0];
     a.epi_c = last ? ctx->epi_c : 127.0f;
     a.use_fma = last ? ctx->fma_ok : ctx->fma1_ok;
+    if (ctx->wide) {
+        // a list with a 4 x 4 pattern: every stage on the wide kernels, before any tube / hybrid / slab / fix-up / tile-statistic
+        // path (they all stage a 2-px halo or assume the s / d / y offsets); no tile marks are left for the next stage
+        ctx->k1_valid = false;
+        int tw, th;
+        stage_wide_tile(u, tw, th);
+        a.tiles_x = (W + tw - 1) / tw;
+        a.tiles_y = (oy1 - oy0 + th - 1) / th;
+        a.verdict = nullptr;
+        a.verdict_take = -1;
+        WideArgs wa;
+        for (int m = 0; m < kMaxModes; ++m) wa.pat[m] = m < ctx->n_modes ? pattern_id(ctx->modes[m]) : 0;
+        if (u == 1) MAIN_KERNEL(ctx, stage, st, launch_stage_wide1(a, wa, st));
+        else MAIN_KERNEL(ctx, stage, st, launch_stage_wide_up(a, u, st));
+        return MULUT_OK;
+    }
     // u == 4: the LDS kernels (tube bands resident) for up to 3 modes, and for longer lists that stage_tube2_kernel takes as a multiset of
     // its three patterns; final_kernel 5 = on every tile, 0 / 6 = hybrid with the per-tile statistic
     const bool tube = u == 4 && ctx->final_kernel != 1 && (ctx->n_modes <= 3 || (ctx->tube2 && C <= 3 && stage_tube2_supported(a)));
@@ -594,6 +624,7 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
 static int stage_fit_images(const mulut_ctx *ctx, int stage, const View &in, int N, int H, int W, int C) {
     const int u = stage_u(ctx, stage);
     unsigned long long fit = (unsigned long long)N;
+    if (ctx->wide) return N;      // (the wide kernels keep no work lists: nothing binds)
     auto cap = [&](unsigned long long limit, unsigned long long per_image) {
         const unsigned long long f = per_image ? (limit - 1) / per_image : fit;
         if (f < fit) fit = f;
@@ -715,7 +746,7 @@ int mulut_reserve(mulut_ctx *ctx, int N, int H, int W, int C) {
     if (!ctx || N <= 0 || H <= 0 || W <= 0 || C <= 0) return MULUT_EINVAL;
     if (!ctx->configured) return MULUT_ENOTCONFIGURED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    {
+    if (!ctx->wide) {     // (the wide kernels use no verdicts or work lists: only the workspace below)
         int tw, th;
         stage_band_tile(tw, th);
         int rc = ensure_verdict(ctx, (size_t)N * ((W + tw - 1) / tw) * ((H + th - 1) / th));
@@ -953,6 +984,7 @@ int mulut_set_tuning(mulut_ctx *ctx, const char *key, int value) {
 
 const char *mulut_kernel_name(const mulut_ctx *ctx, int is_final) {
     if (!ctx || !ctx->configured) return "";
+    if (ctx->wide) return stage_wide_name(is_final ? ctx->scale : 1);
     if (!is_final || ctx->scale == 1) return stage_u1_name(ctx->first_kernel);
     if (ctx->scale == 2 && ctx->final_kernel != 1) return "stage_u1t_kernel<2> + stage_up_fix_site_kernel<2>";
     if (ctx->scale == 3 && ctx->final_kernel != 1) return "stage_u1t_kernel<3> + stage_up_fix_site_kernel<3>";

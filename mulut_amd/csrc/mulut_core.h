@@ -36,14 +36,28 @@ MULUT_HD int imin(int a, int b) { return a < b ? a : b; }
 MULUT_HD int imax(int a, int b) { return a > b ? a : b; }
 
 // Pattern offsets (row, col) of keys b, c, d relative to the anchor a (= (0,0)).
-// 's' :20-23, 'd' :32-35, 'y' :43-46.  Returns false for an unknown mode (:54 raises).
+// 's' :20-23, 'd' :32-35, 'y' :43-46; the 4 x 4 patterns 'e', 'h', 'o' are the taps of the reference network
+// (common/network.py:173-185, 207-215; pad 3 in sr/model.py:12).  Returns false for an unknown mode (:54 raises).
 MULUT_HD bool pattern_offsets(char mode, int (&di)[3], int (&dj)[3]) {
     switch (mode) {
         case 's': di[0] = 0; dj[0] = 1; di[1] = 1; dj[1] = 0; di[2] = 1; dj[2] = 1; return true;
         case 'd': di[0] = 0; dj[0] = 2; di[1] = 2; dj[1] = 0; di[2] = 2; dj[2] = 2; return true;
         case 'y': di[0] = 1; dj[0] = 1; di[1] = 1; dj[1] = 2; di[2] = 2; dj[2] = 1; return true;
+        case 'e': di[0] = 0; dj[0] = 3; di[1] = 3; dj[1] = 0; di[2] = 3; dj[2] = 3; return true;
+        case 'h': di[0] = 2; dj[0] = 2; di[1] = 2; dj[1] = 3; di[2] = 3; dj[2] = 2; return true;
+        case 'o': di[0] = 2; dj[0] = 2; di[1] = 1; dj[1] = 3; di[2] = 3; dj[2] = 1; return true;
         default: return false;
     }
+}
+
+// Reach of a pattern: the largest key offset, i.e. how many pixels one pass looks beyond its site in any direction
+// over the four rotations (= the reference's edge pad, sr/model.py:12).  0 for an unknown mode.
+MULUT_HD int pattern_reach(char mode) {
+    int di[3], dj[3];
+    if (!pattern_offsets(mode, di, dj)) return 0;
+    int r = 0;
+    for (int k = 0; k < 3; ++k) r = imax(r, imax(di[k], dj[k]));
+    return r;
 }
 
 // Rotation r turns the pattern offset (di,dj) into this displacement in the un-rotated image;

@@ -659,7 +659,8 @@ static int ft_fill(FtArgs &a, const float *const *weights, float *const *grad_wq
     memset(&a, 0, sizeof(a));
     for (size_t m = 0; m < M; ++m) {
         int di[3], dj[3];
-        if (!pattern_offsets(modes[m], di, dj)) return MULUT_EMODE;
+        // the input-gradient tiles stage a 2-pixel halo: the 4 x 4 patterns e, h, o (reach 3) are not fine-tuned
+        if (!pattern_offsets(modes[m], di, dj) || pattern_reach(modes[m]) > 2) return MULUT_EMODE;
         if (!weights[m] || (grad_wq && !grad_wq[m])) return MULUT_EINVAL;
         a.w[m] = weights[m];
         a.gw[m] = grad_wq ? grad_wq[m] : nullptr;

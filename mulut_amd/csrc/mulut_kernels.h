@@ -158,5 +158,17 @@ void stage_up_tile(int &tw, int &th);
 const char *stage_u1_name(int variant);
 const char *stage_up_name(int u, int out_mode);
 
+// mode lists with a 4 x 4 pattern (e, h, o: reach 3 per stage), mulut_wide.hip.  Every stage of such a list runs here, any mix and
+// repeat of the six patterns, up to kMaxModes modes; no tube band, work list or tile mark is involved.
+//   launch_stage_wide1   1-byte rows (non-final stages, a final stage with u == 1): one mode's whole table in LDS, swapped per mode
+//   launch_stage_wide_up u in {2,3,4}: rows gathered from the full tables in global memory, generic output layout
+struct WideArgs {
+    int pat[kMaxModes];   // pattern of mode m: 0..5 = s, d, y, e, h, o (from the mode letter: the kernel takes one instance per pattern)
+};
+hipError_t launch_stage_wide1(const StageArgs &a, const WideArgs &w, hipStream_t st);
+hipError_t launch_stage_wide_up(const StageArgs &a, int u, hipStream_t st);
+void stage_wide_tile(int u, int &tw, int &th);
+const char *stage_wide_name(int u);
+
 }  // namespace mulut
 #endif

@@ -6,7 +6,7 @@ Two shardings are offered:
 * **frames** (default, what bench.py scales with): images / frames of a batch are independent units ->
   each rank takes a contiguous slice, no data-path collective at all.
 * **strips** (one big frame, latency mode): the LR image is cut into ``world`` horizontal strips; a rank
-  needs its strip plus a ``halo`` of LR rows (2 per stage) above and below, clamped to the image, and
+  needs its strip plus a ``halo`` of LR rows (``mulut_halo()``: 2 per stage, 3 with a 4 x 4 pattern e / h / o) above and below, clamped to the image, and
   runs the whole cascade on it with ``mulut_pipeline_rows`` (edge replication only at true image
   borders, so seams are bit-exact).  The only exchange step is the final gather of the uint8 HR strips:
   every strip travels point to point (one batched RCCL group of send / recv, backend "nccl" on ROCm)

@@ -83,6 +83,11 @@ class MuLUT(nn.Module):
             raise NotImplementedError("only interval 4 is supported")
         self.interval, self.upscale, self.stages = interval, upscale, stages
         self.modes = "".join(modes)
+        for mode in self.modes:
+            # the device fine-tuning kernels cover s, d and y (the 4 x 4 patterns e, h, o run in inference only);
+            # the reference raises the same way for any mode it does not implement (sr/model.py:121)
+            if mode not in "sdy":
+                raise ValueError("Mode {} not implemented.".format(mode))
         for s in range(stages):
             stage = s + 1
             scale = upscale if stage == stages else 1

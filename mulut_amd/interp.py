@@ -13,7 +13,7 @@ import torch
 from .engine import MuLUTEngine
 
 _ENGINES = {}
-_PAD = {"s": 1, "d": 2, "y": 2}
+_PAD = {"s": 1, "d": 2, "y": 2, "e": 3, "h": 3, "o": 3}      # sr/model.py:12
 
 
 def _engine(device):

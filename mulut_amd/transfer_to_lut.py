@@ -27,14 +27,18 @@ def get_input_tensor(opt, device=None):
 
 
 def get_mode_input_tensor(input_tensor, mode):
-    """sr/2_transfer_to_lut.py:44-66: place the 2x2 grid values at the pattern's positions of a zero 3x3 patch."""
+    """sr/2_transfer_to_lut.py:44-66: place the 2x2 grid values at the pattern's positions of a zero 3x3 patch (d, y)
+    or 4x4 patch (e, h, o: the taps of network.TAPS, which the reference's script leaves out, :63)."""
     if mode == "d":
         pos = ((0, 0), (0, 2), (2, 0), (2, 2))
     elif mode == "y":
         pos = ((0, 0), (1, 1), (1, 2), (2, 1))
+    elif mode in ("e", "h", "o"):
+        pos = network.TAPS[mode.upper()][1]
     else:
         raise ValueError("Mode {} not implemented.".format(mode))
-    out = torch.zeros((input_tensor.shape[0], input_tensor.shape[1], 3, 3), dtype=input_tensor.dtype,
+    k = 4 if mode in ("e", "h", "o") else 3
+    out = torch.zeros((input_tensor.shape[0], input_tensor.shape[1], k, k), dtype=input_tensor.dtype,
                       device=input_tensor.device)
     for (i, j), (si, sj) in zip(pos, ((0, 0), (0, 1), (1, 0), (1, 1))):
         out[:, :, i, j] = input_tensor[:, :, si, sj]
