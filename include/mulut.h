@@ -198,8 +198,6 @@ int mulut_eval_y(int device, const void *gt_hwc, const void *out_hwc, int H, int
  *   rows in flight under the current pass's multiply-adds, one 16x4 tile per wave, no workgroup barrier), 0 = stage_tube_kernel.
  * "detail_kernel": the detailed tiles of the hybrid: 0 (default) = anchor slabs in LDS (samples grouped by anchor MSB on the
  *   device, stage_slab_kernel; taken when the stage input is planar, < 2^28 bytes, <= 3 modes), 1 = full-table gather kernel.
- * "fix_kernel": the fix-up of the tube kernels' work list: 0 (default) = one pass per lane, 1 = one entry per thread,
- *               2 = one pass per lane with the list walk software-pipelined.
  * "stat_from_first_stage": 1 (default) = when the final stage reads what a content-routing first-stage launch of the same
  *   call wrote, its per-tile statistic looks only at the tiles that launch marked detailed; 0 = at every tile.
  * "hybrid_oob_per_1024": tile threshold of the hybrid (sites out of band per 1024, default 128).
@@ -207,8 +205,6 @@ int mulut_eval_y(int device, const void *gt_hwc, const void *out_hwc, int H, int
  *   window kernel, flagged sites are recomputed through a device work list), 2 = window kernel (full table in LDS) on every
  *   tile, 3 = tube kernel on every tile.  (1: the first one-read-per-neighbour kernel, retired: MULUT_EINVAL.)
  * "first_stage_detail_per_1024": tile threshold of first_stage_kernel 0 (default 24).
- * "u1t_persist" (experiments): 0 (default) = one workgroup per tile of the 1-byte-row tube kernel, 1..8 = that many persistent
- *   workgroups per CU walking XCD-contiguous tile ranges.  Per context, like every other key.
  * Wide mode lists (e, h, o): every key above is accepted and stored, but does not change their route -- all their stages run on
  *   the wide kernels (stage_wide1_kernel, stage_wide_up_kernel), which have no tube, hybrid, slab or work-list variants.
  * Unknown key or value: MULUT_EINVAL.

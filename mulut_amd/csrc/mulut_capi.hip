@@ -20,8 +20,18 @@ struct DevTable {
                             // v_num 1: one dword per slot (kTube1BandBytes)
     size_t tube_bytes = 0;
     uint8_t *slab = nullptr; // v_num 16: the table as 16 anchor slab pairs (mulut_core.h), kSlabTableBytes
+    size_t slab_bytes = 0;
     int vnum = 0;
     size_t bytes = 0;
+};
+
+// tuning keys that choose a stage's route (plan_stage); the defaults take the routes that use every buffer any route does
+struct Routing {
+    int final_kernel = 0;   // tuning "final_stage_kernel": 0 auto (= 6), 1 full-table kernel, 5 tube kernel (all bands resident), 6 hybrid (tube)
+    int first_kernel = 0;   // tuning "first_stage_kernel", 1-byte-row stages: 0 auto (tube kernel, detailed tiles to the window kernel), 2 window kernel (full table in
+                            // LDS) on every tile, 3 tube kernel on every tile
+    int tube2 = 1;          // tuning "tube_pipelined": 1 = stage_tube2_kernel (hand-scheduled LDS reads) where the mode list has one, 0 = stage_tube_kernel
+    int detail_kernel = 0;  // tuning "detail_kernel": 0 = anchor slabs in LDS (when the launch qualifies), 1 = full-table gather kernel
 };
 
 struct mulut_ctx {
@@ -34,34 +44,27 @@ struct mulut_ctx {
     bool wide = false;  // the mode list holds a 4 x 4 pattern (e, h, o): reach 3, every stage on the wide kernels (mulut_wide.hip)
     DevTable tab[MULUT_MAX_STAGES][6];  // [stage-1][pattern id s,d,y,e,h,o]
     uint8_t *ws[2] = {nullptr, nullptr};
-    size_t ws_bytes = 0;
+    size_t ws_cap[2] = {0, 0};
     std::string hip_err;
     int num_cus = 256;
-    int final_kernel = 0;   // 0 auto (= 6 hybrid with the tube kernel), 1 full-table kernel, 2 compact LDS band, 3 expanded LDS band, 4 hybrid (band-x),
-                            // 5 tube kernel (all bands resident), 6 hybrid (tube)
+    Routing routing;
     int f32_ok[2] = {0, 0}; // float epilogue proven exact for the [non-final, final] divisor
     int fma_ok = 0;         // fused (biased-sum) float epilogue proven exact for the final stage
     float epi_c = 0.0f;
     uint32_t *verdict = nullptr;   // per-tile smooth/detailed verdicts of the hybrid final stage
-    size_t verdict_tiles = 0;
+    size_t verdict_cap = 0;
     uint32_t *fix = nullptr;       // [0] = count, [16...] = entries of the fix-up list (samples recomputed from the full tables)
-    size_t fix_cap = 0;            // capacity in ids
+    size_t fix_cap = 0;            // capacities in elements (here: header + ids)
     unsigned long long *dbg = nullptr;   // probe buffer (mulut_debug_read), MULUT_DEBUG_WORDS words, allocated on first use
     uint32_t *det_ctl = nullptr;   // detailed-tile path of the final stage (launch_detail_slab): counters, items, sample ids, blocks
     uint32_t *det_items = nullptr, *det_desc = nullptr, *det_tpos = nullptr, *det_dlist = nullptr;
     uint16_t *det_thist = nullptr;
     uint4 *det_blocks = nullptr;
-    size_t det_items_cap = 0, det_ids_cap = 0, det_blocks_cap = 0, det_tiles_cap = 0;
+    size_t det_items_cap = 0, det_ids_cap = 0, det_blocks_cap = 0, det_thist_cap = 0, det_tpos_cap = 0, det_dlist_cap = 0;
     bool k1_valid = false;         // ctx->tlist holds the marks of the first-stage launch that produced the next stage's input ...
     int k1_N = 0, k1_W = 0, k1_H = 0, k1_tiles_x = 0, k1_tiles_y = 0, k1_oy0 = 0, k1_oy1 = 0;   // ... of this shape ...
     const uint8_t *k1_out = nullptr;                                      // ... written to this buffer
     int stat_from_k1 = 1;          // tuning "stat_from_first_stage": the final stage's statistic looks only at tiles the first stage marked
-    int fix_variant = 0;           // tuning "fix_kernel"
-    int tube2 = 1;                 // tuning "tube_pipelined": 1 = stage_tube2_kernel (hand-scheduled LDS reads) where the mode list has one, 0 = stage_tube_kernel
-    int u1t_persist = 0;           // tuning "u1t_persist": persistent workgroups per CU of the 1-byte-row tube kernel (0 = one workgroup per tile)
-    int detail_kernel = 0;         // tuning "detail_kernel": 0 = anchor slabs in LDS (when the launch qualifies), 1 = full-table gather kernel
-    int first_kernel = 0;   // 1-byte-row stages: 0 auto (tube kernel, detailed tiles to the window kernel), 2 window kernel (full table in
-                            // LDS) on every tile, 3 tube kernel on every tile
     int up_detail_per_1024 = 8;    // the same threshold for the routed x2 / x3 final stages (their detailed tiles go to the gather kernel; profiles/r04y_scale_bench.jsonl)
     int u1_detail_per_1024 = 24;   // a tile goes to the full-table kernel when more than this share of its (sampled) 4-pixel groups spans > 1 MSB step
     uint32_t *tlist = nullptr;     // [16 + tile] = 1: the tube kernel left this tile to the full-table kernel
@@ -87,6 +90,86 @@ static int pattern_id(char m) {
             return MULUT_EHIP;                                                              \
         }                                                                                   \
     } while (0)
+
+// Device copy of a host image: the buffer is reallocated only when the size changes
+template <class P, class V>
+static int upload(mulut_ctx *ctx, P *&dev, size_t &bytes, const std::vector<V> &img) {
+    const size_t n = img.size() * sizeof(V);
+    if (dev && bytes != n) {
+        HIP_TRY(ctx, hipFree(dev));
+        dev = nullptr;
+    }
+    if (!dev) HIP_TRY(ctx, hipMalloc((void **)&dev, n));
+    bytes = n;
+    HIP_TRY(ctx, hipMemcpy(dev, img.data(), n, hipMemcpyHostToDevice));
+    return MULUT_OK;
+}
+
+template <class P>
+static int release(mulut_ctx *ctx, P *&dev, size_t &bytes) {
+    if (dev) HIP_TRY(ctx, hipFree(dev));
+    dev = nullptr;
+    bytes = 0;
+    return MULUT_OK;
+}
+
+// Tube band of a table with u x u-value rows (img: its device image): the rows with max - min of the keys <= 2, at tube_slot().
+// Slots of rows outside the tube keep the fill (value + 128 = 128 in every 16-bit field; 0 for 1-byte rows)
+static std::vector<uint32_t> tube_band(int u, const int8_t *rows, const std::vector<uint8_t> &img) {
+    const size_t bytes = u == 1 ? kTube1BandBytes : u == 2 ? kTube2BandBytes : u == 3 ? kTube3BandBytes : kTubeBandBytes;
+    std::vector<uint32_t> tb(bytes / 4, u == 1 ? 0u : 0x00800080u);
+    const int rb = row_dwords(u) * 4;
+    for (int A = 0; A < kL; ++A)
+        for (int B = imax(0, A - 2); B <= imin(kL - 1, A + 2); ++B)
+            for (int C = imax(0, A - 2); C <= imin(kL - 1, A + 2); ++C)
+                for (int D = imax(0, A - 2); D <= imin(kL - 1, A + 2); ++D) {
+                    if (!tube_contains(A, B, C, D)) continue;
+                    const size_t row = (size_t)A * kStrideA + B * kStrideB + C * kStrideC + D, slot = (size_t)tube_slot(A, B, C, D);
+                    if (u == 1) {           // one dword per slot: the value as int16 in both halves
+                        const uint32_t v = (uint32_t)(uint16_t)(int16_t)rows[row];
+                        tb[slot] = v | (v << 16);
+                        continue;
+                    }
+                    const uint8_t *e = &img[row * rb];
+                    if (u == 2) {           // two dwords per slot: (e0 | e1 << 16), (e2 | e3 << 16)
+                        tb[slot * 2] = (uint32_t)e[0] | ((uint32_t)e[1] << 16);
+                        tb[slot * 2 + 1] = (uint32_t)e[2] | ((uint32_t)e[3] << 16);
+                    } else if (u == 3) {    // 24 bytes per slot: the nine values as ten 16-bit fields e0 e1 e2 e3 e4 e4 e5 e6 e7 e8
+                        uint32_t f[10];
+                        for (int q = 0; q < 9; ++q) f[tube3_field(q)] = e[q];
+                        f[5] = e[4];
+                        for (int k = 0; k < 5; ++k) tb[slot * (kTube3SlotBytes / 4) + k] = f[2 * k] | (f[2 * k + 1] << 16);
+                    } else {                // 16-bit fields in two planes: LO (lo_k = e(4k) | e(4k+2) << 16) then HI (hi_k = e(4k+1) | e(4k+3) << 16)
+                        for (int k = 0; k < 4; ++k) {
+                            tb[slot * 4 + k] = (uint32_t)e[4 * k] | ((uint32_t)e[4 * k + 2] << 16);
+                            tb[(size_t)kTubePlaneBytes / 4 + slot * 4 + k] = (uint32_t)e[4 * k + 1] | ((uint32_t)e[4 * k + 3] << 16);
+                        }
+                    }
+                }
+    return tb;
+}
+
+// anchor slab pairs of a u == 4 table: pair A = rows (A, b, c, d) and (A + 1, b, c, d) interleaved, 32 bytes per (b, c, d)
+static std::vector<uint8_t> slab_pairs(const std::vector<uint8_t> &img) {
+    std::vector<uint8_t> sl((size_t)kSlabTableBytes + 1024, 128);      // the LDS copy of a pair moves whole KiB
+    for (int A = 0; A < 16; ++A)
+        for (int bcd = 0; bcd < kStrideA; ++bcd)
+            for (int f = 0; f < 2; ++f)
+                memcpy(&sl[(size_t)A * kSlabPairBytes + (size_t)bcd * 32 + (size_t)f * 16], &img[((size_t)(A + f) * kStrideA + bcd) * 16], 16);
+    return sl;
+}
+
+// Device buffer of at least n elements: reallocated (contents dropped) only when it is too small; cap counts elements
+template <class T>
+static int grow(mulut_ctx *ctx, T *&p, size_t &cap, size_t n) {
+    if (n <= cap) return MULUT_OK;
+    if (p) HIP_TRY(ctx, hipFree(p));
+    p = nullptr;
+    cap = 0;
+    HIP_TRY(ctx, hipMalloc((void **)&p, n * sizeof(T)));
+    cap = n;
+    return MULUT_OK;
+}
 
 extern "C" {
 
@@ -230,124 +313,14 @@ int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows,
         for (int64_t i = 0; i < kRows; ++i)
             for (int e = 0; e < vnum; ++e) img[(size_t)i * rb + e] = (uint8_t)((int)host_rows[i * vnum + e] + 128);
     }
-    if (t.dev && t.bytes != img.size()) {
-        HIP_TRY(ctx, hipFree(t.dev));
-        t.dev = nullptr;
-    }
-    if (!t.dev) HIP_TRY(ctx, hipMalloc(&t.dev, img.size()));
-    HIP_TRY(ctx, hipMemcpy(t.dev, img.data(), img.size(), hipMemcpyHostToDevice));
+    int rc = upload(ctx, t.dev, t.bytes, img);
+    if (rc) return rc;
     t.vnum = vnum;
-    t.bytes = img.size();
-    if (pattern_reach(mode) > 2) {
-        // e / h / o tables: the wide kernels gather from the full table only (no tube band, no anchor slabs)
-        if (t.tube) HIP_TRY(ctx, hipFree(t.tube));
-        if (t.slab) HIP_TRY(ctx, hipFree(t.slab));
-        t.tube = nullptr;
-        t.slab = nullptr;
-        t.tube_bytes = 0;
-    } else if (u == 1) {
-        // tube band of a 1-byte-row table: one dword per slot, the value as int16 in both halves
-        std::vector<uint32_t> tb((size_t)kTube1BandBytes / 4, 0u);
-        for (int A = 0; A < kL; ++A)
-            for (int B = imax(0, A - 2); B <= imin(kL - 1, A + 2); ++B)
-                for (int C = imax(0, A - 2); C <= imin(kL - 1, A + 2); ++C)
-                    for (int D = imax(0, A - 2); D <= imin(kL - 1, A + 2); ++D) {
-                        if (!tube_contains(A, B, C, D)) continue;
-                        const uint32_t v = (uint32_t)(uint16_t)(int16_t)host_rows[(size_t)A * kStrideA + B * kStrideB + C * kStrideC + D];
-                        tb[(size_t)tube_slot(A, B, C, D)] = v | (v << 16);
-                    }
-        if (t.tube && t.tube_bytes != tb.size() * 4) {
-            HIP_TRY(ctx, hipFree(t.tube));
-            t.tube = nullptr;
-        }
-        if (!t.tube) HIP_TRY(ctx, hipMalloc(&t.tube, tb.size() * 4));
-        t.tube_bytes = tb.size() * 4;
-        HIP_TRY(ctx, hipMemcpy(t.tube, tb.data(), tb.size() * 4, hipMemcpyHostToDevice));
-    } else if (u == 2) {
-        // tube band of a u == 2 table: 8 bytes per slot, (e0 | e1 << 16), (e2 | e3 << 16) as value + 128
-        std::vector<uint32_t> tb((size_t)kTube2BandBytes / 4, 0x00800080u);
-        for (int A = 0; A < kL; ++A)
-            for (int B = imax(0, A - 2); B <= imin(kL - 1, A + 2); ++B)
-                for (int C = imax(0, A - 2); C <= imin(kL - 1, A + 2); ++C)
-                    for (int D = imax(0, A - 2); D <= imin(kL - 1, A + 2); ++D) {
-                        if (!tube_contains(A, B, C, D)) continue;
-                        const uint8_t *e = &img[((size_t)A * kStrideA + B * kStrideB + C * kStrideC + D) * 4];
-                        tb[(size_t)tube_slot(A, B, C, D) * 2] = (uint32_t)e[0] | ((uint32_t)e[1] << 16);
-                        tb[(size_t)tube_slot(A, B, C, D) * 2 + 1] = (uint32_t)e[2] | ((uint32_t)e[3] << 16);
-                    }
-        if (t.tube && t.tube_bytes != tb.size() * 4) {
-            HIP_TRY(ctx, hipFree(t.tube));
-            t.tube = nullptr;
-        }
-        if (!t.tube) HIP_TRY(ctx, hipMalloc(&t.tube, tb.size() * 4));
-        t.tube_bytes = tb.size() * 4;
-        HIP_TRY(ctx, hipMemcpy(t.tube, tb.data(), tb.size() * 4, hipMemcpyHostToDevice));
-    } else if (u == 3) {
-        // tube band of a u == 3 table: 24 bytes per slot, the nine values (+ 128) as ten 16-bit fields e0 e1 e2 e3 e4 e4 e5 e6 e7 e8
-        std::vector<uint32_t> tb((size_t)kTube3BandBytes / 4, 0x00800080u);
-        const int rb = row_dwords(3) * 4;
-        for (int A = 0; A < kL; ++A)
-            for (int B = imax(0, A - 2); B <= imin(kL - 1, A + 2); ++B)
-                for (int C = imax(0, A - 2); C <= imin(kL - 1, A + 2); ++C)
-                    for (int D = imax(0, A - 2); D <= imin(kL - 1, A + 2); ++D) {
-                        if (!tube_contains(A, B, C, D)) continue;
-                        const uint8_t *e = &img[((size_t)A * kStrideA + B * kStrideB + C * kStrideC + D) * rb];
-                        uint32_t *d = &tb[(size_t)tube_slot(A, B, C, D) * (kTube3SlotBytes / 4)];
-                        uint32_t f[10];
-                        for (int q = 0; q < 9; ++q) f[tube3_field(q)] = e[q];
-                        f[5] = e[4];
-                        for (int k = 0; k < 5; ++k) d[k] = f[2 * k] | (f[2 * k + 1] << 16);
-                    }
-        if (t.tube && t.tube_bytes != tb.size() * 4) {
-            HIP_TRY(ctx, hipFree(t.tube));
-            t.tube = nullptr;
-        }
-        if (!t.tube) HIP_TRY(ctx, hipMalloc(&t.tube, tb.size() * 4));
-        t.tube_bytes = tb.size() * 4;
-        HIP_TRY(ctx, hipMemcpy(t.tube, tb.data(), tb.size() * 4, hipMemcpyHostToDevice));
-    } else if (u == 4) {
-        // tube band: rows with max - min of the keys <= 2 at tube_slot(), expanded to 16-bit fields in two planes: LO (lo_k = e(4k) | e(4k+2) << 16)
-        // then HI (hi_k = e(4k+1) | e(4k+3) << 16)
-        std::vector<uint32_t> tb((size_t)kTubeBandBytes / 4, 0x00800080u);
-        for (int A = 0; A < kL; ++A)
-            for (int B = imax(0, A - 2); B <= imin(kL - 1, A + 2); ++B)
-                for (int C = imax(0, A - 2); C <= imin(kL - 1, A + 2); ++C)
-                    for (int D = imax(0, A - 2); D <= imin(kL - 1, A + 2); ++D) {
-                        if (!tube_contains(A, B, C, D)) continue;
-                        const uint8_t *e = &img[((size_t)A * kStrideA + B * kStrideB + C * kStrideC + D) * 16];
-                        const size_t s4 = (size_t)tube_slot(A, B, C, D) * 4;
-                        for (int k = 0; k < 4; ++k) {
-                            tb[s4 + k] = (uint32_t)e[4 * k] | ((uint32_t)e[4 * k + 2] << 16);
-                            tb[(size_t)kTubePlaneBytes / 4 + s4 + k] = (uint32_t)e[4 * k + 1] | ((uint32_t)e[4 * k + 3] << 16);
-                        }
-                    }
-        if (t.tube && t.tube_bytes != tb.size() * 4) {
-            HIP_TRY(ctx, hipFree(t.tube));
-            t.tube = nullptr;
-        }
-        if (!t.tube) HIP_TRY(ctx, hipMalloc(&t.tube, tb.size() * 4));
-        t.tube_bytes = tb.size() * 4;
-        HIP_TRY(ctx, hipMemcpy(t.tube, tb.data(), tb.size() * 4, hipMemcpyHostToDevice));
-        // anchor slab pairs: pair A = rows (A, b, c, d) and (A + 1, b, c, d) interleaved, 32 bytes per (b, c, d)
-        std::vector<uint8_t> sl((size_t)kSlabTableBytes + 1024, 128);      // the LDS copy of a pair moves whole KiB
-        for (int A = 0; A < 16; ++A)
-            for (int bcd = 0; bcd < kStrideA; ++bcd)
-                for (int f = 0; f < 2; ++f)
-                    memcpy(&sl[(size_t)A * kSlabPairBytes + (size_t)bcd * 32 + (size_t)f * 16], &img[((size_t)(A + f) * kStrideA + bcd) * 16], 16);
-        if (!t.slab) HIP_TRY(ctx, hipMalloc((void **)&t.slab, sl.size()));
-        HIP_TRY(ctx, hipMemcpy(t.slab, sl.data(), sl.size(), hipMemcpyHostToDevice));
-    } else {
-        if (t.tube) HIP_TRY(ctx, hipFree(t.tube));
-        if (t.slab) HIP_TRY(ctx, hipFree(t.slab));
-        t.tube = nullptr;
-        t.slab = nullptr;
-        t.tube_bytes = 0;
-    }
-    if (u != 4 && t.slab) {
-        HIP_TRY(ctx, hipFree(t.slab));
-        t.slab = nullptr;
-    }
-    return MULUT_OK;
+    // e / h / o tables: the wide kernels gather from the full table only (no tube band, no anchor slabs)
+    const bool band = pattern_reach(mode) <= 2;
+    rc = band ? upload(ctx, t.tube, t.tube_bytes, tube_band(u, host_rows, img)) : release(ctx, t.tube, t.tube_bytes);
+    if (rc) return rc;
+    return band && u == 4 ? upload(ctx, t.slab, t.slab_bytes, slab_pairs(img)) : release(ctx, t.slab, t.slab_bytes);
 }
 
 // bracket the dominant kernel of a stage with events when timing is on (mulut_last_kernel_ms)
@@ -415,29 +388,48 @@ static View make_view(const uint8_t *p, int layout, int rows, int W, int C, int 
     return v;
 }
 
-static int ensure_verdict(mulut_ctx *ctx, size_t tiles);
-static int ensure_fix(mulut_ctx *ctx, size_t ids);
-static int ensure_tlist(mulut_ctx *ctx, size_t tiles);
-static int ensure_detail(mulut_ctx *ctx, size_t tiles, size_t items, size_t ids, size_t blocks);
+// Routes of a stage launch (plan_stage)
+enum Route {
+    kRouteWide1,    // a list with a 4 x 4 pattern (e, h, o), 1-byte rows: stage_wide1_kernel
+    kRouteWideUp,   // the same, u > 1: stage_wide_up_kernel
+    kRouteU1Full,   // 1-byte rows: window kernel (full table in LDS) on every tile
+    kRouteU1Tube,   // 1-byte rows: tube kernel (+ window kernel on the tiles it marks, when routed) + site fix-up
+    kRouteUpTube,   // x2 / x3: tube-band kernel + site fix-up (+ gather kernel on the tiles it marks, when routed)
+    kRouteGather,   // u > 1: gather kernel on every tile
+    kRouteTube,     // x4: tube kernel on every tile + pixel fix-up
+    kRouteHybrid,   // x4: tile statistic, tube kernel on the smooth tiles, slab path or gather kernel on the detailed ones, pixel fix-up
+};
 
-static hipError_t tube_launch(mulut_ctx *ctx, const StageArgs &a, const BandArgs &b, int mode, hipStream_t st) {
-    if (ctx->tube2 && stage_tube2_supported(a)) return launch_stage_tube2(a, b, mode, ctx->num_cus, st);
-    return launch_stage_tube(a, b, mode, ctx->num_cus, st);
+// What one stage launch runs and what it needs.  plan_stage is the one place that decides it: run_stage_one executes the plan,
+// stage_fit_images splits a batch by its index width, mulut_reserve sizes the buffers from it and mulut_kernel_name names it.
+struct StagePlan {
+    Route route;
+    bool routed;            // kRouteU1Tube / kRouteUpTube: the tiles the tube kernel calls detailed go to the window / gather kernel
+    bool tube2;             // x4 tube kernel: stage_tube2_kernel (else stage_tube_kernel)
+    bool slab;              // kRouteHybrid: detailed tiles on the anchor slabs (else the gather kernel)
+    bool wide4;             // x4 gather kernel: stage_up_wide4 (merged 16-bit fields hold 4 modes at most)
+    int out_mode;           // K2Out of the x4 kernels
+    int tiles_x, tiles_y;   // grid of the stage's main kernel
+    size_t fix_ids, tlist_tiles, verdict_tiles;             // work lists (0: not used)
+    size_t det_tiles, det_items, det_ids, det_blocks;       // buffers of the slab path
+    // Index widths of the device work lists: site ids of the 1-byte-row / x2 / x3 tube kernels 32 bits (N C H W), pixel ids of the
+    // x4 fix-up list 30 bits (N H W), sample descriptors of the slab path 28 bits of byte offset into the stage input.  The width
+    // that admits the fewest images, and what one image takes of it (0: no list)
+    unsigned long long width, per_image;
+};
+
+static void tile_grid(const StageArgs &a, void (*tile)(int &, int &), int &tiles_x, int &tiles_y) {
+    int tw, th;
+    tile(tw, th);
+    tiles_x = (a.W + tw - 1) / tw;
+    tiles_y = (a.oy1 - a.oy0 + th - 1) / th;
 }
 
-// Launch one stage: input view holds LR rows [in.row0, ...), outputs for LR rows [oy0, oy1).
-// C channels are processed (<= 3); they may be a group of an image with more (then the views carry that image's strides and
-// packed_ok is false: the packed-RGB store needs a pixel stride of exactly 3)
-// k1_ref / k1_n0: when this launch is a sub-launch of a larger one (run_stage below), the buffer and first image of the WHOLE launch --
-// what the first stage's tile marks are recorded against
-static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &out, int out_layout, int N, int H, int W,
-                         int C, int oy0, int oy1, hipStream_t st, bool packed_ok, const uint8_t *k1_ref, int k1_n0) {
+// The launch arguments every route shares; run_stage_one adds the tables and the route's own fields
+static StageArgs stage_args(const mulut_ctx *ctx, int stage, const View &in, const View &out, int N, int H, int W, int C, int oy0, int oy1) {
     StageArgs a;
     memset(&a, 0, sizeof(a));
-    int rc = stage_tables(ctx, stage, a.lut);
-    if (rc) return rc;
     const bool last = stage == ctx->stages;
-    const int u = stage_u(ctx, stage);
     a.in = in; a.out = out;
     a.dbg = ctx->dbg;
     a.in_padded = (in.p == ctx->ws[0] || in.p == ctx->ws[1]) ? 1 : 0;
@@ -455,192 +447,229 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
     a.use_f32 = ctx->f32_ok[last ? 1 : 0];
     a.epi_c = last ? ctx->epi_c : 127.0f;
     a.use_fma = last ? ctx->fma_ok : ctx->fma1_ok;
+    if (stage_u(ctx, stage) == 1 && last && !ctx->wide) a.use_fma = 0;     // (a final stage with 1-byte rows -- scale 1 -- takes the integer epilogue)
+    a.verdict_take = -1;
+    return a;
+}
+
+// Route of a launch with upscale u and arguments a (tiles unset); C <= 3.  packed_ok: the output may take the packed-RGB store (a
+// pixel stride of exactly 3)
+static StagePlan plan_stage(const mulut_ctx *ctx, const Routing &r, int u, const StageArgs &a, int out_layout, bool packed_ok) {
+    StagePlan p;
+    memset(&p, 0, sizeof(p));
+    const unsigned long long N = (unsigned long long)a.N, rows = (unsigned long long)(a.oy1 - a.oy0), sites = (unsigned long long)a.C * a.H * a.W;
+    auto bind = [&](unsigned long long width, unsigned long long per_image) {
+        if (!p.width || (width - 1) / per_image < (p.width - 1) / p.per_image) {
+            p.width = width;
+            p.per_image = per_image;
+        }
+    };
     if (ctx->wide) {
         // a list with a 4 x 4 pattern: every stage on the wide kernels, before any tube / hybrid / slab / fix-up / tile-statistic
-        // path (they all stage a 2-px halo or assume the s / d / y offsets); no tile marks are left for the next stage
-        ctx->k1_valid = false;
+        // path (they all stage a 2-px halo or assume the s / d / y offsets); no work lists
         int tw, th;
         stage_wide_tile(u, tw, th);
-        a.tiles_x = (W + tw - 1) / tw;
-        a.tiles_y = (oy1 - oy0 + th - 1) / th;
-        a.verdict = nullptr;
-        a.verdict_take = -1;
-        WideArgs wa;
-        for (int m = 0; m < kMaxModes; ++m) wa.pat[m] = m < ctx->n_modes ? pattern_id(ctx->modes[m]) : 0;
-        if (u == 1) MAIN_KERNEL(ctx, stage, st, launch_stage_wide1(a, wa, st));
-        else MAIN_KERNEL(ctx, stage, st, launch_stage_wide_up(a, u, st));
-        return MULUT_OK;
+        p.route = u == 1 ? kRouteWide1 : kRouteWideUp;
+        p.tiles_x = (a.W + tw - 1) / tw;
+        p.tiles_y = ((int)rows + th - 1) / th;
+        return p;
+    }
+    if (u == 1) {
+        // (any mode list: the bands live in LDS per PATTERN, a repeated pattern is simply computed again into the int32 sum)
+        tile_grid(a, stage_u1_tile, p.tiles_x, p.tiles_y);
+        p.route = (r.first_kernel == 0 || r.first_kernel == 3) && N * sites < (1ull << 32) ? kRouteU1Tube : kRouteU1Full;
+        if (p.route == kRouteU1Full) return p;
+        p.routed = r.first_kernel == 0;
+        p.fix_ids = N * a.C * rows * a.W;
+        p.tlist_tiles = N * p.tiles_x * p.tiles_y;
+        bind(1ull << 32, sites);
+        return p;
+    }
+    if (u == 4 && (out_layout == MULUT_LAYOUT_CHW || (a.C == 1 && packed_ok))) p.out_mode = kOutPlanarU4;
+    else if (u == 4 && out_layout == MULUT_LAYOUT_HWC && a.C == 3 && packed_ok) p.out_mode = kOutPackedRGBU4;
+    else p.out_mode = kOutGeneric;
+    if ((u == 2 || u == 3) && r.final_kernel != 1 && N * sites < (1ull << 32)) {
+        // x2 / x3 final stage on the tube band (the 1-byte-row kernel family with 4- / 9-value rows); flagged sites recomputed from the
+        // full table.  final_kernel 5: the tube kernel on every tile; otherwise routed by the 1-byte-row family's local-detail
+        // statistic -- detailed 64 x 64 tiles (where most sites would end up on the fix-up list) go to the gather kernel
+        tile_grid(a, stage_u1t_tile, p.tiles_x, p.tiles_y);
+        p.route = kRouteUpTube;
+        p.routed = r.final_kernel != 5;
+        p.fix_ids = N * a.C * rows * a.W;
+        if (p.routed) p.tlist_tiles = N * p.tiles_x * p.tiles_y;
+        bind(1ull << 32, sites);
+        return p;
     }
     // u == 4: the LDS kernels (tube bands resident) for up to 3 modes, and for longer lists that stage_tube2_kernel takes as a multiset of
     // its three patterns; final_kernel 5 = on every tile, 0 / 6 = hybrid with the per-tile statistic
-    const bool tube = u == 4 && ctx->final_kernel != 1 && (ctx->n_modes <= 3 || (ctx->tube2 && C <= 3 && stage_tube2_supported(a)));
-    const bool hybrid = tube && ctx->final_kernel != 5;
-    a.verdict = nullptr;
-    a.verdict_take = -1;
-    int tw, th;
-    if (u == 1) stage_u1_tile(tw, th); else if (tube) stage_band_tile(tw, th); else stage_up_tile(tw, th);
-    a.tiles_x = (W + tw - 1) / tw;
-    a.tiles_y = (oy1 - oy0 + th - 1) / th;
-    if (u == 1 && last) a.use_fma = 0;     // (a final stage with 1-byte rows -- scale 1 -- takes the integer epilogue)
+    p.tube2 = u == 4 && r.tube2 && stage_tube2_supported(a);
+    p.wide4 = u == 4 && a.M > 4;
+    if (u != 4 || r.final_kernel == 1 || (a.M > 3 && !p.tube2)) {
+        tile_grid(a, stage_up_tile, p.tiles_x, p.tiles_y);
+        p.route = kRouteGather;
+        return p;
+    }
+    tile_grid(a, stage_band_tile, p.tiles_x, p.tiles_y);
+    p.route = r.final_kernel == 5 ? kRouteTube : kRouteHybrid;
+    p.fix_ids = N * rows * a.W * 3;     // every sample of the launch may end up on the fix-up list (entries: 30-bit pixel id + channel)
+    bind(1ull << 30, (unsigned long long)a.H * a.W);
+    if (p.route == kRouteTube) return p;
+    // per-tile choice on the device: smooth tiles -> tube kernel, detailed tiles -> anchor slabs in LDS (samples grouped by anchor
+    // MSB), or the full-table gather kernel where that path does not apply
+    p.verdict_tiles = N * p.tiles_x * p.tiles_y;
+    StageArgs t = a;
+    t.tiles_x = p.tiles_x;
+    t.tiles_y = p.tiles_y;
+    p.slab = r.detail_kernel == 0 && detail_slab_supported(t);
+    if (p.slab) {
+        p.det_tiles = p.verdict_tiles;
+        p.det_items = detail_items_max(t);
+        p.det_ids = detail_ids_count(t);
+        p.det_blocks = detail_blocks_count(t);
+        bind(1ull << 28, (unsigned long long)(a.in.sN < 0 ? -a.in.sN : a.in.sN));
+    }
+    return p;
+}
+
+// Device buffers a plan needs (grown, never shrunk)
+static int ensure_plan(mulut_ctx *ctx, const StagePlan &p) {
+    int rc = MULUT_OK;
+    if (p.fix_ids) rc = grow(ctx, ctx->fix, ctx->fix_cap, p.fix_ids + 16);
+    if (!rc && p.tlist_tiles) rc = grow(ctx, ctx->tlist, ctx->tlist_cap, p.tlist_tiles + 16);
+    if (!rc && p.verdict_tiles) rc = grow(ctx, ctx->verdict, ctx->verdict_cap, p.verdict_tiles);
+    if (rc || !p.det_tiles) return rc;
+    if (!ctx->det_ctl) {
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->det_ctl, kDetCtlDwords * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipMemset(ctx->det_ctl, 0, kDetCtlDwords * sizeof(uint32_t)));
+    }
+    rc = grow(ctx, ctx->det_thist, ctx->det_thist_cap, p.det_tiles * 16);
+    if (!rc) rc = grow(ctx, ctx->det_tpos, ctx->det_tpos_cap, p.det_tiles * 16);
+    if (!rc) rc = grow(ctx, ctx->det_dlist, ctx->det_dlist_cap, p.det_tiles);
+    if (!rc) rc = grow(ctx, ctx->det_items, ctx->det_items_cap, p.det_items * 2);
+    if (!rc) rc = grow(ctx, ctx->det_desc, ctx->det_ids_cap, p.det_ids);
+    if (!rc) rc = grow(ctx, ctx->det_blocks, ctx->det_blocks_cap, p.det_blocks);
+    return rc;
+}
+
+// Launch one stage: input view holds LR rows [in.row0, ...), outputs for LR rows [oy0, oy1).
+// C channels are processed (<= 3); they may be a group of an image with more (then the views carry that image's strides and
+// packed_ok is false: the packed-RGB store needs a pixel stride of exactly 3)
+// k1_ref / k1_n0: when this launch is a sub-launch of a larger one (run_stage below), the buffer and first image of the WHOLE launch --
+// what the first stage's tile marks are recorded against
+static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &out, int out_layout, int N, int H, int W,
+                         int C, int oy0, int oy1, hipStream_t st, bool packed_ok, const uint8_t *k1_ref, int k1_n0) {
+    StageArgs a = stage_args(ctx, stage, in, out, N, H, W, C, oy0, oy1);
+    int rc = stage_tables(ctx, stage, a.lut);
+    if (rc) return rc;
+    const int u = stage_u(ctx, stage);
+    const StagePlan p = plan_stage(ctx, ctx->routing, u, a, out_layout, packed_ok);
+    a.tiles_x = p.tiles_x;
+    a.tiles_y = p.tiles_y;
+    if (p.route == kRouteWide1 || p.route == kRouteWideUp) {
+        ctx->k1_valid = false;      // (no tile marks are left for the next stage)
+        WideArgs wa;
+        for (int m = 0; m < kMaxModes; ++m) wa.pat[m] = m < ctx->n_modes ? pattern_id(ctx->modes[m]) : 0;
+        if (p.route == kRouteWide1) MAIN_KERNEL(ctx, stage, st, launch_stage_wide1(a, wa, st));
+        else MAIN_KERNEL(ctx, stage, st, launch_stage_wide_up(a, u, st));
+        return MULUT_OK;
+    }
     // marks of the first-stage launch that produced this stage's input (same buffer, same shape); consumed here, never kept
     const bool k1_marks = ctx->k1_valid && ctx->k1_out == k1_ref && k1_n0 + N <= ctx->k1_N && ctx->k1_W == W && ctx->k1_H == H && ctx->k1_oy0 <= oy0 &&
                           oy1 <= ctx->k1_oy1;      // the marks cover exactly the images and rows that launch wrote: never index past its tile grid
     ctx->k1_valid = false;
-    if (u == 1) {
-        // (any mode list: the bands live in LDS per PATTERN, a repeated pattern is simply computed again into the int32 sum)
-        const bool tube1 = (ctx->first_kernel == 0 || ctx->first_kernel == 3) &&
-                           (unsigned long long)N * C * H * W < (1ull << 32);
-        if (!tube1) {
-            MAIN_KERNEL(ctx, stage, st, launch_stage_u1(a, st, 0));
-            return MULUT_OK;
-        }
-        // tube kernel on the smooth tiles; the sites it flags are recomputed from the full tables, the tiles it leaves go
-        // to the full-table kernel -- both through device-side lists (no host synchronisation, hipGraph-capturable)
-        rc = ensure_fix(ctx, (size_t)N * C * (oy1 - oy0) * W);
-        if (rc) return rc;
-        rc = ensure_tlist(ctx, (size_t)N * a.tiles_x * a.tiles_y);
-        if (rc) return rc;
-        BandArgs b1;
-        for (int m = 0; m < ctx->n_modes; ++m) b1.band[m] = ctx->tab[stage - 1][pattern_id(ctx->modes[m])].tube;
-        a.fix_count = ctx->fix;
-        a.fix_list = ctx->fix + 16;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->fix, 0, sizeof(uint32_t), st));
-        if (ctx->first_kernel == 0) HIP_TRY(ctx, hipMemsetAsync(ctx->tlist, 0, (16 + (size_t)N * a.tiles_x * a.tiles_y) * sizeof(uint32_t), st));
-        const bool route = ctx->first_kernel == 0;
-        a.tile_count = ctx->tlist;
-        a.tile_list = ctx->tlist + 16;
-        a.verdict_take = route ? 0 : -1;
-        MAIN_KERNEL(ctx, stage, st, launch_stage_u1t(a, b1, (unsigned)ctx->u1_detail_per_1024, ctx->num_cus, ctx->u1t_persist, st));
-        if (route) HIP_TRY(ctx, launch_stage_u1w_list(a, ctx->num_cus, st));
-        HIP_TRY(ctx, launch_stage_u1_fix(a, ctx->num_cus, st));
-        ctx->k1_valid = route;
-        ctx->k1_N = N; ctx->k1_W = W; ctx->k1_tiles_x = a.tiles_x; ctx->k1_tiles_y = a.tiles_y; ctx->k1_oy0 = oy0; ctx->k1_oy1 = oy1; ctx->k1_H = H;
-        ctx->k1_out = out.p;
+    if (p.route == kRouteU1Full || p.route == kRouteGather) {
+        if (p.route == kRouteU1Full) MAIN_KERNEL(ctx, stage, st, launch_stage_u1(a, st));
+        else if (p.wide4) MAIN_KERNEL(ctx, stage, st, launch_stage_up_wide4(a, st));
+        else MAIN_KERNEL(ctx, stage, st, launch_stage_up(a, u, p.out_mode, st));
         return MULUT_OK;
     }
-    int mode = kOutGeneric;
-    if (u == 4 && (out_layout == MULUT_LAYOUT_CHW || (C == 1 && packed_ok))) mode = kOutPlanarU4;
-    else if (u == 4 && out_layout == MULUT_LAYOUT_HWC && C == 3 && packed_ok) mode = kOutPackedRGBU4;
-    if ((u == 2 || u == 3) && ctx->final_kernel != 1 && (unsigned long long)N * C * H * W < (1ull << 32)) {
-        // u == 2 / u == 3 final stage on the tube band (the 1-byte-row kernel family with 4- / 9-value rows); flagged sites recomputed from the full table
-        rc = ensure_fix(ctx, (size_t)N * C * (oy1 - oy0) * W);
-        if (rc) return rc;
-        BandArgs b2;
-        for (int m = 0; m < ctx->n_modes; ++m) b2.band[m] = ctx->tab[stage - 1][pattern_id(ctx->modes[m])].tube;
-        a.fix_count = ctx->fix;
-        a.fix_list = ctx->fix + 16;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->fix, 0, sizeof(uint32_t), st));
-        int t2w, t2h;
-        stage_u1t_tile(t2w, t2h);
-        StageArgs g = a;                // the gather kernel's launch on the tiles the tube kernel leaves out (its own tiling)
-        a.tiles_x = (W + t2w - 1) / t2w;
-        a.tiles_y = (oy1 - oy0 + t2h - 1) / t2h;
-        // final_kernel 5: the tube kernel on every tile; otherwise routed by the 1-byte-row family's local-detail statistic -- detailed
-        // 64 x 64 tiles (where most sites would end up on the fix-up list) go to the gather kernel, through device-side marks
-        const bool route = ctx->final_kernel != 5;
-        if (route) {
-            rc = ensure_tlist(ctx, (size_t)N * a.tiles_x * a.tiles_y);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipMemsetAsync(ctx->tlist, 0, (16 + (size_t)N * a.tiles_x * a.tiles_y) * sizeof(uint32_t), st));
-            a.tile_count = ctx->tlist;
-            a.tile_list = ctx->tlist + 16;
-            a.verdict_take = 0;
-        }
-        if (u == 2) MAIN_KERNEL(ctx, stage, st, launch_stage_u2t(a, b2, (unsigned)ctx->up_detail_per_1024, ctx->num_cus, ctx->u1t_persist, st));
-        else MAIN_KERNEL(ctx, stage, st, launch_stage_u3t(a, b2, (unsigned)ctx->up_detail_per_1024, ctx->num_cus, ctx->u1t_persist, st));
-        if (route) {
-            g.tile_list = a.tile_list;
-            HIP_TRY(ctx, launch_stage_up(g, u, kOutGeneric, st));
-        }
-        return MULUT_OK;
-    }
-    if (!tube) {
-        if (u == 4 && ctx->n_modes > 4) MAIN_KERNEL(ctx, stage, st, launch_stage_up_wide4(a, st));   // merged 16-bit fields hold 4 modes at most
-        else MAIN_KERNEL(ctx, stage, st, launch_stage_up(a, u, mode, st));
-        return MULUT_OK;
-    }
-    // every sample of the launch may end up on the fix-up list (entries: 30-bit pixel id + channel)
-    if ((unsigned long long)N * H * W >= (1ull << 30)) return MULUT_EUNSUPPORTED;
-    rc = ensure_fix(ctx, (size_t)N * (oy1 - oy0) * W * 3);
+    // the tube kernels: sites (pixels at x4) they flag are recomputed from the full tables, the tiles they leave go to the full-table
+    // kernels -- both through device-side lists (no host synchronisation, hipGraph-capturable)
+    if ((unsigned long long)N * p.per_image >= p.width) return MULUT_EUNSUPPORTED;     // (one image beyond a width: run_stage splits batches)
+    rc = ensure_plan(ctx, p);
     if (rc) return rc;
     a.fix_count = ctx->fix;
     a.fix_list = ctx->fix + 16;
     HIP_TRY(ctx, hipMemsetAsync(ctx->fix, 0, sizeof(uint32_t), st));
     BandArgs b;
     for (int m = 0; m < ctx->n_modes; ++m) b.band[m] = ctx->tab[stage - 1][pattern_id(ctx->modes[m])].tube;
-    if (!hybrid) {
-        MAIN_KERNEL(ctx, stage, st, tube_launch(ctx, a, b, mode, st));
-        HIP_TRY(ctx, launch_stage_up_fix(a, mode, ctx->num_cus, st, ctx->fix_variant));
+    if (p.route == kRouteU1Tube || p.route == kRouteUpTube) {
+        StageArgs g = a;            // the gather kernel's launch on the tiles the tube kernel leaves (its own tiling)
+        tile_grid(g, stage_up_tile, g.tiles_x, g.tiles_y);
+        if (p.routed) HIP_TRY(ctx, hipMemsetAsync(ctx->tlist, 0, (16 + p.tlist_tiles) * sizeof(uint32_t), st));
+        if (p.route == kRouteU1Tube || p.routed) {
+            a.tile_count = ctx->tlist;
+            a.tile_list = ctx->tlist + 16;
+        }
+        a.verdict_take = p.routed ? 0 : -1;
+        if (p.route == kRouteUpTube) {
+            if (u == 2) MAIN_KERNEL(ctx, stage, st, launch_stage_u2t(a, b, (unsigned)ctx->up_detail_per_1024, ctx->num_cus, st));
+            else MAIN_KERNEL(ctx, stage, st, launch_stage_u3t(a, b, (unsigned)ctx->up_detail_per_1024, ctx->num_cus, st));
+            g.tile_list = a.tile_list;
+            if (p.routed) HIP_TRY(ctx, launch_stage_up(g, u, kOutGeneric, st));
+            return MULUT_OK;
+        }
+        MAIN_KERNEL(ctx, stage, st, launch_stage_u1t(a, b, (unsigned)ctx->u1_detail_per_1024, st));
+        if (p.routed) HIP_TRY(ctx, launch_stage_u1w_list(a, ctx->num_cus, st));
+        HIP_TRY(ctx, launch_stage_u1_fix(a, ctx->num_cus, st));
+        ctx->k1_valid = p.routed;
+        ctx->k1_N = N; ctx->k1_W = W; ctx->k1_tiles_x = a.tiles_x; ctx->k1_tiles_y = a.tiles_y; ctx->k1_oy0 = oy0; ctx->k1_oy1 = oy1; ctx->k1_H = H;
+        ctx->k1_out = out.p;
         return MULUT_OK;
     }
-    // per-tile choice on the device: smooth tiles -> tube kernel, detailed tiles -> anchor slabs in LDS (samples grouped by anchor
-    // MSB), or the full-table gather kernel where that path does not apply
-    rc = ensure_verdict(ctx, (size_t)N * a.tiles_x * a.tiles_y);
-    if (rc) return rc;
-    const bool slab = ctx->detail_kernel == 0 && detail_slab_supported(a);
-    if (slab) {
-        rc = ensure_detail(ctx, (size_t)N * a.tiles_x * a.tiles_y, detail_items_max(a), detail_ids_count(a), detail_blocks_count(a));
-        if (rc) return rc;
-        // the control words of the detailed-tile path are cleared before the statistic: it raises ctl[kDetAny] when it marks a tile
-        HIP_TRY(ctx, hipMemsetAsync(ctx->det_ctl, 0, kDetCtlDwords * sizeof(uint32_t), st));
+    auto tube = [&]() {
+        return p.tube2 ? launch_stage_tube2(a, b, p.out_mode, ctx->num_cus, st) : launch_stage_tube(a, b, p.out_mode, ctx->num_cus, st);
+    };
+    if (p.route == kRouteTube) {
+        MAIN_KERNEL(ctx, stage, st, tube());
+        HIP_TRY(ctx, launch_stage_up_fix(a, ctx->num_cus, st));
+        return MULUT_OK;
     }
+    // the control words of the slab path are cleared before the statistic: it raises ctl[kDetAny] when it marks a tile
+    if (p.slab) HIP_TRY(ctx, hipMemsetAsync(ctx->det_ctl, 0, kDetCtlDwords * sizeof(uint32_t), st));
     if (ctx->stat_from_k1 && k1_marks) {
         a.k1_hdr = ctx->tlist;
         a.k1_tiles_x = ctx->k1_tiles_x; a.k1_tiles_y = ctx->k1_tiles_y; a.k1_oy0 = ctx->k1_oy0; a.k1_n0 = k1_n0;
     }
-    HIP_TRY(ctx, launch_tile_stat(a, ctx->verdict, (uint32_t)ctx->hybrid_oob_per_1024, st, slab ? ctx->det_thist : nullptr, slab ? ctx->det_ctl + kDetAny : nullptr));
+    HIP_TRY(ctx, launch_tile_stat(a, ctx->verdict, (uint32_t)ctx->hybrid_oob_per_1024, st, p.slab ? ctx->det_thist : nullptr, p.slab ? ctx->det_ctl + kDetAny : nullptr));
     a.k1_hdr = nullptr;
     a.verdict = ctx->verdict;
     a.vt_x = a.tiles_x;
     a.vt_y = a.tiles_y;
     a.verdict_take = 0;
-    MAIN_KERNEL(ctx, stage, st, tube_launch(ctx, a, b, mode, st));
-    if (slab) {
+    MAIN_KERNEL(ctx, stage, st, tube());
+    if (p.slab) {
         DetailArgs d;
         memset(&d, 0, sizeof(d));
         d.ctl = ctx->det_ctl; d.items = ctx->det_items; d.desc = ctx->det_desc; d.blocks = ctx->det_blocks;
         d.thist = ctx->det_thist; d.tpos = ctx->det_tpos; d.dlist = ctx->det_dlist;
         for (int m = 0; m < 3; ++m) d.slab[m] = m < ctx->n_modes ? ctx->tab[stage - 1][pattern_id(ctx->modes[m])].slab : nullptr;
-        HIP_TRY(ctx, launch_detail_slab(a, d, mode, ctx->num_cus, st));
+        HIP_TRY(ctx, launch_detail_slab(a, d, p.out_mode, ctx->num_cus, st));
     } else {
         StageArgs g = a;
-        int gw, gh;
-        stage_up_tile(gw, gh);
-        g.tiles_x = (W + gw - 1) / gw;
-        g.tiles_y = (oy1 - oy0 + gh - 1) / gh;
+        tile_grid(g, stage_up_tile, g.tiles_x, g.tiles_y);
         g.verdict_take = 1;
-        if (ctx->n_modes > 4) HIP_TRY(ctx, launch_stage_up_wide4(g, st));      // (merged 16-bit fields hold 4 modes at most)
-        else HIP_TRY(ctx, launch_stage_up(g, u, mode, st));
+        if (p.wide4) HIP_TRY(ctx, launch_stage_up_wide4(g, st));
+        else HIP_TRY(ctx, launch_stage_up(g, u, p.out_mode, st));
     }
-    HIP_TRY(ctx, launch_stage_up_fix(a, mode, ctx->num_cus, st, ctx->fix_variant));
+    HIP_TRY(ctx, launch_stage_up_fix(a, ctx->num_cus, st));
     return MULUT_OK;
 }
 
-// Index widths of the device work lists, per launch: site ids of the 1-byte-row / u == 2 tube kernels 32 bits (N C H W), pixel ids of the
-// u == 4 fix-up list 30 bits (N H W), sample descriptors of the detailed-tile path 28 bits of byte offset into the stage input.  Images
-// are independent (sr/4_test_lut.py:257-259 fans them out one by one), so a launch beyond a width runs as sub-launches of whole images
-// that fit -- every entry point (mulut_stage, mulut_pipeline_rows, mulut_pipeline) comes through here, none falls to a slower kernel
-// because of its batch size.  How many images of the launch fit one sub-launch (>= 1; N when nothing binds):
-static int stage_fit_images(const mulut_ctx *ctx, int stage, const View &in, int N, int H, int W, int C) {
-    const int u = stage_u(ctx, stage);
-    unsigned long long fit = (unsigned long long)N;
-    if (ctx->wide) return N;      // (the wide kernels keep no work lists: nothing binds)
-    auto cap = [&](unsigned long long limit, unsigned long long per_image) {
-        const unsigned long long f = per_image ? (limit - 1) / per_image : fit;
-        if (f < fit) fit = f;
-    };
-    if (u == 1 || u == 2 || u == 3) cap(1ull << 32, (unsigned long long)C * H * W);
-    if (u == 4 && ctx->final_kernel != 1) {
-        cap(1ull << 30, (unsigned long long)H * W);
-        if (ctx->final_kernel != 5 && ctx->detail_kernel == 0 && ctx->n_modes <= 3 && in.sX == 1)      // (what detail_slab_supported() asks of a launch)
-            cap(1ull << 28, (unsigned long long)(in.sN < 0 ? -in.sN : in.sN));
-    }
-    return fit < 1 ? 1 : (int)fit;
+// Images are independent (sr/4_test_lut.py:257-259 fans them out one by one), so a launch beyond an index width of its work lists
+// (StagePlan::width) runs as sub-launches of whole images that fit -- every entry point (mulut_stage, mulut_pipeline_rows,
+// mulut_pipeline) comes through here, none falls to a slower kernel because of its batch size.  How many images of the launch fit
+// one sub-launch (>= 1; N when nothing binds):
+static int stage_fit_images(const mulut_ctx *ctx, const Routing &r, int stage, const View &in, int N, int H, int W, int C, int oy0, int oy1) {
+    // (the route of one image, and the widths its lists bind)
+    const StagePlan p = plan_stage(ctx, r, stage_u(ctx, stage), stage_args(ctx, stage, in, in, 1, H, W, C, oy0, oy1), MULUT_LAYOUT_CHW, false);
+    const unsigned long long fit = p.width ? (p.width - 1) / p.per_image : (unsigned long long)N;
+    return fit < 1 ? 1 : fit < (unsigned long long)N ? (int)fit : N;
 }
 
 static int run_stage(mulut_ctx *ctx, int stage, const View &in, const View &out, int out_layout, int N, int H, int W,
                      int C, int oy0, int oy1, hipStream_t st, bool packed_ok = true) {
-    const int fit = stage_fit_images(ctx, stage, in, N, H, W, C);
+    const int fit = stage_fit_images(ctx, ctx->routing, stage, in, N, H, W, C, oy0, oy1);
     if (N <= fit) return run_stage_one(ctx, stage, in, out, out_layout, N, H, W, C, oy0, oy1, st, packed_ok, in.p, 0);
     // the first stage's tile marks (if this stage reads what it wrote) serve every sub-launch: kept across the calls that consume them
     const bool k1_valid = ctx->k1_valid;
@@ -660,124 +689,37 @@ static int run_stage(mulut_ctx *ctx, int stage, const View &in, const View &out,
 int mulut_halo(const mulut_ctx *ctx) { return (ctx && ctx->configured) ? ctx->reach * ctx->stages : 0; }
 
 static int ensure_workspace(mulut_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->ws_bytes) return MULUT_OK;
-    for (auto &w : ctx->ws) {
-        if (w) HIP_TRY(ctx, hipFree(w));
-        w = nullptr;
-    }
-    ctx->ws_bytes = 0;
-    for (auto &w : ctx->ws) HIP_TRY(ctx, hipMalloc((void **)&w, bytes + 64));      // + padding: kernels may read whole dwords / 8 bytes at the very end (StageArgs::in_padded)
-    ctx->ws_bytes = bytes;
-    return MULUT_OK;
-}
-
-static int ensure_fix(mulut_ctx *ctx, size_t ids) {
-    if (ids <= ctx->fix_cap) return MULUT_OK;
-    if (ctx->fix) HIP_TRY(ctx, hipFree(ctx->fix));
-    ctx->fix = nullptr;
-    ctx->fix_cap = 0;
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->fix, (ids + 16) * sizeof(uint32_t)));
-    ctx->fix_cap = ids;
-    return MULUT_OK;
-}
-
-static int ensure_tlist(mulut_ctx *ctx, size_t tiles) {
-    if (tiles <= ctx->tlist_cap) return MULUT_OK;
-    if (ctx->tlist) HIP_TRY(ctx, hipFree(ctx->tlist));
-    ctx->tlist = nullptr;
-    ctx->tlist_cap = 0;
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->tlist, (tiles + 16) * sizeof(uint32_t)));
-    ctx->tlist_cap = tiles;
-    return MULUT_OK;
-}
-
-static int ensure_detail(mulut_ctx *ctx, size_t tiles, size_t items, size_t ids, size_t blocks) {
-    if (!ctx->det_ctl) {
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->det_ctl, kDetCtlDwords * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMemset(ctx->det_ctl, 0, kDetCtlDwords * sizeof(uint32_t)));
-    }
-    if (tiles > ctx->det_tiles_cap) {
-        if (ctx->det_thist) HIP_TRY(ctx, hipFree(ctx->det_thist));
-        if (ctx->det_dlist) HIP_TRY(ctx, hipFree(ctx->det_dlist));
-        if (ctx->det_tpos) HIP_TRY(ctx, hipFree(ctx->det_tpos));
-        ctx->det_thist = nullptr;
-        ctx->det_dlist = ctx->det_tpos = nullptr;
-        ctx->det_tiles_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->det_thist, tiles * 16 * sizeof(uint16_t)));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->det_tpos, tiles * 16 * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->det_dlist, tiles * sizeof(uint32_t)));
-        ctx->det_tiles_cap = tiles;
-    }
-    if (items > ctx->det_items_cap) {
-        if (ctx->det_items) HIP_TRY(ctx, hipFree(ctx->det_items));
-        ctx->det_items = nullptr;
-        ctx->det_items_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->det_items, items * 2 * sizeof(uint32_t)));
-        ctx->det_items_cap = items;
-    }
-    if (ids > ctx->det_ids_cap) {
-        if (ctx->det_desc) HIP_TRY(ctx, hipFree(ctx->det_desc));
-        ctx->det_desc = nullptr;
-        ctx->det_ids_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->det_desc, ids * sizeof(uint32_t)));
-        ctx->det_ids_cap = ids;
-    }
-    if (blocks > ctx->det_blocks_cap) {
-        if (ctx->det_blocks) HIP_TRY(ctx, hipFree(ctx->det_blocks));
-        ctx->det_blocks = nullptr;
-        ctx->det_blocks_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->det_blocks, blocks * sizeof(uint4)));
-        ctx->det_blocks_cap = blocks;
-    }
-    return MULUT_OK;
-}
-
-static int ensure_verdict(mulut_ctx *ctx, size_t tiles) {
-    if (tiles <= ctx->verdict_tiles) return MULUT_OK;
-    if (ctx->verdict) HIP_TRY(ctx, hipFree(ctx->verdict));
-    ctx->verdict = nullptr;
-    ctx->verdict_tiles = 0;
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->verdict, tiles * sizeof(uint32_t)));
-    ctx->verdict_tiles = tiles;
-    return MULUT_OK;
+    int rc = MULUT_OK;
+    for (int k = 0; k < 2 && !rc; ++k) rc = grow(ctx, ctx->ws[k], ctx->ws_cap[k], bytes + 64);      // + padding: kernels may read whole dwords / 8 bytes at the very end (StageArgs::in_padded)
+    return rc;
 }
 
 int mulut_reserve(mulut_ctx *ctx, int N, int H, int W, int C) {
     if (!ctx || N <= 0 || H <= 0 || W <= 0 || C <= 0) return MULUT_EINVAL;
     if (!ctx->configured) return MULUT_ENOTCONFIGURED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->wide) {     // (the wide kernels use no verdicts or work lists: only the workspace below)
-        int tw, th;
-        stage_band_tile(tw, th);
-        int rc = ensure_verdict(ctx, (size_t)N * ((W + tw - 1) / tw) * ((H + th - 1) / th));
-        if (rc) return rc;
-        {
-            const bool u1 = ctx->stages > 1 || ctx->scale == 1;
-            rc = ensure_fix(ctx, (size_t)N * H * W * ((u1 || ctx->scale == 2 || ctx->scale == 3 || ctx->scale == 4) ? (size_t)(C > 3 ? C : 3) : 1));
-            if (rc) return rc;
-            if (ctx->scale == 4) {
-                stage_band_tile(tw, th);
-                StageArgs t;
-                memset(&t, 0, sizeof(t));
-                // the final stage of a batch beyond the 28-bit sample descriptors runs as sub-launches (run_stage): the detailed-tile path's
-                // buffers are sized for the largest of those, so that a captured call never allocates
-                t.in.sN = (long long)H * W * imin(C, 3);       // (a cascade's final stage reads the planar workspace: groups of <= 3 channels)
-                t.in.sX = 1; t.C = imin(C, 3); t.M = ctx->n_modes; t.H = H; t.W = W;
-                t.N = imin(N, stage_fit_images(ctx, ctx->stages, t.in, N, H, W, t.C));
-                t.tiles_x = (W + tw - 1) / tw; t.tiles_y = (H + th - 1) / th;
-                if (detail_slab_supported(t)) {       // launches of this size that the anchor-slab path would take
-                    rc = ensure_detail(ctx, (size_t)t.N * t.tiles_x * t.tiles_y, detail_items_max(t), detail_ids_count(t), detail_blocks_count(t));
-                    if (rc) return rc;
-                }
-            }
-            if (u1 || ctx->scale == 2 || ctx->scale == 3) {      // tile marks of the routed 1-byte-row family (first stages; x2 / x3 final stages)
-                stage_u1_tile(tw, th);
-                rc = ensure_tlist(ctx, (size_t)N * ((W + tw - 1) / tw) * ((H + th - 1) / th));
-                if (rc) return rc;
-            }
+    // the plans of every stage's largest launches -- all N images, and the sub-launch a batch beyond an index width runs as (run_stage)
+    // -- under the default routes, which use every buffer any route does: a later call of at most this shape allocates nothing,
+    // whatever the tuning.  Channels run in groups of <= 3; the input is planar, as a cascade's final stage reads the workspace
+    const Routing r;
+    const int Cg = imin(C, 3);
+    const View in = make_view(nullptr, MULUT_LAYOUT_CHW, H, W, Cg, 0);
+    StagePlan need;
+    memset(&need, 0, sizeof(need));
+    auto atleast = [](size_t &v, size_t x) { v = x > v ? x : v; };
+    for (int s = 1; s <= ctx->stages; ++s)
+        for (const int n : {N, stage_fit_images(ctx, r, s, in, N, H, W, Cg, 0, H)}) {
+            const StagePlan p = plan_stage(ctx, r, stage_u(ctx, s), stage_args(ctx, s, in, in, imin(n, N), H, W, Cg, 0, H), MULUT_LAYOUT_CHW, true);
+            atleast(need.fix_ids, p.fix_ids);
+            atleast(need.tlist_tiles, p.tlist_tiles);
+            atleast(need.verdict_tiles, p.verdict_tiles);
+            atleast(need.det_tiles, p.det_tiles);
+            atleast(need.det_items, p.det_items);
+            atleast(need.det_ids, p.det_ids);
+            atleast(need.det_blocks, p.det_blocks);
         }
-    }
-    if (ctx->stages < 2) return MULUT_OK;
+    const int rc = ensure_plan(ctx, need);
+    if (rc || ctx->stages < 2) return rc;
     return ensure_workspace(ctx, (size_t)N * H * W * C);
 }
 
@@ -931,12 +873,12 @@ int mulut_set_tuning(mulut_ctx *ctx, const char *key, int value) {
     if (!ctx || !key) return MULUT_EINVAL;
     if (!strcmp(key, "final_stage_kernel")) {
         if (value != 0 && value != 1 && value != 5 && value != 6) return MULUT_EINVAL;      // (2-4: generations retired in round 3)
-        ctx->final_kernel = value;
+        ctx->routing.final_kernel = value;
         return MULUT_OK;
     }
     if (!strcmp(key, "first_stage_kernel")) {
         if (value != 0 && value != 2 && value != 3) return MULUT_EINVAL;      // (1: retired in round 3)
-        ctx->first_kernel = value;
+        ctx->routing.first_kernel = value;
         return MULUT_OK;
     }
     if (!strcmp(key, "stat_from_first_stage")) {
@@ -944,24 +886,14 @@ int mulut_set_tuning(mulut_ctx *ctx, const char *key, int value) {
         ctx->stat_from_k1 = value;
         return MULUT_OK;
     }
-    if (!strcmp(key, "fix_kernel")) {      // fix-up of the u == 4 tube kernels: 0 = one pass per lane, 1 = one entry per thread, 2 = one pass per lane with the list walk pipelined
-        if (value < 0 || value > 2) return MULUT_EINVAL;
-        ctx->fix_variant = value;
-        return MULUT_OK;
-    }
     if (!strcmp(key, "tube_pipelined")) {
         if (value < 0 || value > 1) return MULUT_EINVAL;
-        ctx->tube2 = value;
+        ctx->routing.tube2 = value;
         return MULUT_OK;
     }
     if (!strcmp(key, "detail_kernel")) {     // final-stage tiles the statistic marks detailed: 0 anchor slabs in LDS, 1 full-table gathers
         if (value < 0 || value > 1) return MULUT_EINVAL;
-        ctx->detail_kernel = value;
-        return MULUT_OK;
-    }
-    if (!strcmp(key, "u1t_persist")) {      // experiment: persistent workgroups per CU of the 1-byte-row tube kernel (0 = one per tile)
-        if (value < 0 || value > 8) return MULUT_EINVAL;
-        ctx->u1t_persist = value;
+        ctx->routing.detail_kernel = value;
         return MULUT_OK;
     }
     if (!strcmp(key, "first_stage_detail_per_1024")) {
@@ -984,23 +916,28 @@ int mulut_set_tuning(mulut_ctx *ctx, const char *key, int value) {
 
 const char *mulut_kernel_name(const mulut_ctx *ctx, int is_final) {
     if (!ctx || !ctx->configured) return "";
-    if (ctx->wide) return stage_wide_name(is_final ? ctx->scale : 1);
-    if (!is_final || ctx->scale == 1) return stage_u1_name(ctx->first_kernel);
-    if (ctx->scale == 2 && ctx->final_kernel != 1) return "stage_u1t_kernel<2> + stage_up_fix_site_kernel<2>";
-    if (ctx->scale == 3 && ctx->final_kernel != 1) return "stage_u1t_kernel<3> + stage_up_fix_site_kernel<3>";
-    // (as run_stage decides: the pipelined kernel takes every list that uses all of s, d, y, up to kMaxTube2Modes modes, when the float
-    // epilogue is exact for the divisor)
-    const bool all3 = strchr(ctx->modes, 's') && strchr(ctx->modes, 'd') && strchr(ctx->modes, 'y');
-    const bool t2 = ctx->tube2 && all3 && ctx->n_modes <= kMaxTube2Modes && (ctx->n_modes > 4 || ctx->f32_ok[1]);
-    if (ctx->scale == 4 && (ctx->n_modes <= 3 || t2) && ctx->final_kernel != 1) {
-        if (ctx->final_kernel == 5) return t2 ? "stage_tube2_kernel<rgb> + stage_up_fix2_kernel" : "stage_tube_kernel<rgb> + stage_up_fix2_kernel";
-        if (ctx->detail_kernel == 0)
-            return t2 ? "hybrid: tile_stat_kernel + stage_tube2_kernel<rgb> (smooth tiles; hand-scheduled LDS pipeline, one 16x4 tile per wave) + stage_slab_kernel (detailed tiles, anchor slabs in LDS)"
-                      : "hybrid: tile_stat_kernel + stage_tube_kernel<rgb> (smooth tiles) + stage_slab_kernel (detailed tiles, anchor slabs in LDS)";
-        return t2 ? "hybrid: tile_stat_kernel + stage_tube2_kernel<rgb> (smooth tiles) + stage_up_kernel<4,rgb> (detailed tiles)"
-                  : "hybrid: tile_stat_kernel + stage_tube_kernel<rgb> (smooth tiles) + stage_up_kernel<4,rgb> (detailed tiles)";
+    // the plan of a representative launch: one whole 3-channel image, read planar (as a cascade's final stage reads the workspace),
+    // written as packed RGB; the non-final stage has 1-byte rows
+    const int stage = is_final ? ctx->stages : 1, u = is_final ? ctx->scale : 1;
+    const View in = make_view(nullptr, MULUT_LAYOUT_CHW, 64, 64, 3, 0);
+    const StagePlan p = plan_stage(ctx, ctx->routing, u, stage_args(ctx, stage, in, in, 1, 64, 64, 3, 0, 64), MULUT_LAYOUT_HWC, true);
+    switch (p.route) {
+        case kRouteWide1:
+        case kRouteWideUp: return stage_wide_name(u);
+        case kRouteU1Full: return "stage_u1w_kernel";
+        case kRouteU1Tube: return p.routed ? "stage_u1t_kernel (smooth tiles) + stage_u1w_kernel (detailed tiles) + stage_u1_fix_kernel"
+                                           : "stage_u1t_kernel + stage_u1_fix_kernel";
+        case kRouteUpTube: return u == 2 ? "stage_u1t_kernel<2> + stage_up_fix_site_kernel<2>" : "stage_u1t_kernel<3> + stage_up_fix_site_kernel<3>";
+        case kRouteGather: return p.wide4 ? "stage_up_kernel<4,generic,wide>" : stage_up_name(u, p.out_mode);
+        case kRouteTube: return p.tube2 ? "stage_tube2_kernel<rgb> + stage_up_fix2_kernel" : "stage_tube_kernel<rgb> + stage_up_fix2_kernel";
+        default: break;
     }
-    return stage_up_name(ctx->scale, ctx->scale == 4 ? kOutPackedRGBU4 : kOutGeneric);
+    if (p.slab)
+        return p.tube2 ? "hybrid: tile_stat_kernel + stage_tube2_kernel<rgb> (smooth tiles; hand-scheduled LDS pipeline, one 16x4 tile per wave) + stage_slab_kernel (detailed tiles, anchor slabs in LDS)"
+                       : "hybrid: tile_stat_kernel + stage_tube_kernel<rgb> (smooth tiles) + stage_slab_kernel (detailed tiles, anchor slabs in LDS)";
+    if (p.wide4) return "hybrid: tile_stat_kernel + stage_tube2_kernel<rgb> (smooth tiles) + stage_up_kernel<4,generic,wide> (detailed tiles)";
+    return p.tube2 ? "hybrid: tile_stat_kernel + stage_tube2_kernel<rgb> (smooth tiles) + stage_up_kernel<4,rgb> (detailed tiles)"
+                   : "hybrid: tile_stat_kernel + stage_tube_kernel<rgb> (smooth tiles) + stage_up_kernel<4,rgb> (detailed tiles)";
 }
 
 }  // extern "C"

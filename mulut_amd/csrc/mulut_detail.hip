@@ -26,7 +26,7 @@ namespace mulut {
 //   detail_retile_kernel         writes the blocks of the detailed tiles to the output image in its layout
 // A sample's 5x5 window is read straight from the stage input (L2-resident), 8 unaligned bytes per row from column
 // x - 2; pixels in the first 2 / last 6 columns of the image would need edge replication inside those 8 bytes and go to
-// the pixel fix-up list (stage_up_fix_kernel) instead.
+// the pixel fix-up list (stage_up_fix2_kernel) instead.
 // ------------------------------------------------------------------------------------------
 constexpr int kSlabNT = 1024, kSlabS = 4, kSlabItem = kSlabNT * kSlabS;
 constexpr int kSlabLdsBytes = ((kSlabPairBytes + 1023) / 1024) * 1024;      // whole 1-KiB LDS-DMA pieces: 157,696

@@ -202,14 +202,9 @@ constexpr int K1_TW = 64, K1_TH = 64, K1_NT = 1024, K1_SPT = 12;  // 3 ch * 64*6
 static_assert(K1_SPT * K1_NT >= 3 * K1_TW * K1_TH, "SPT too small for 3 channels");
 
 void stage_u1_tile(int &tw, int &th) { tw = K1_TW; th = K1_TH; }
-const char *stage_u1_name(int variant) {
-    return variant == 1 ? "stage_u1_kernel" : variant == 2 ? "stage_u1w_kernel" : variant == 3 ? "stage_u1t_kernel + stage_u1_fix_kernel"
-                        : "stage_u1t_kernel (smooth tiles) + stage_u1w_kernel (detailed tiles) + stage_u1_fix_kernel";
-}
-
-hipError_t launch_stage_u1(const StageArgs &a, hipStream_t st, int variant) {
+hipError_t launch_stage_u1(const StageArgs &a, hipStream_t st) {
     if (a.C > 3) return hipErrorInvalidValue;
-    auto kern = stage_u1w_kernel<K1_TW, K1_TH, K1_NT, false>;      // (variant: kept in the signature for the tuning knob; one kernel is left)
+    auto kern = stage_u1w_kernel<K1_TW, K1_TH, K1_NT, false>;
     const size_t lds = (size_t)kU1TableBytes + (size_t)a.C * (K1_TH + 2 * kHalo) * (K1_TW + 2 * kHalo);
     {
         const hipError_t e = raise_lds_limit((const void *)kern, 120 * 1024);
@@ -857,7 +852,7 @@ __global__ void __launch_bounds__(256) stage_u1_fix_kernel(StageArgs a) {
 void stage_u1t_tile(int &tw, int &th) { tw = K1T_TW; th = K1T_TH; }
 
 template <int U>
-static hipError_t launch_u1t_t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, int persist_per_cu, hipStream_t st) {
+static hipError_t launch_u1t_t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, hipStream_t st) {
     // the shipped mode list gets the instance with its passes in straight-line code
     const bool sdy = a.M == 3 && a.di[0][0] == 0 && a.dj[0][0] == 1 && a.dj[1][0] == 2 && a.di[2][0] == 1 && a.dj[2][0] == 1;
     auto kern = sdy ? stage_u1t_kernel<U, kU1tPatsSDY> : stage_u1t_kernel<U, 0>;
@@ -867,18 +862,16 @@ static hipError_t launch_u1t_t(const StageArgs &a, const BandArgs &b, unsigned d
     }
     const long long ntiles = (long long)a.N * a.tiles_x * a.tiles_y;
     if (ntiles <= 0 || ntiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    // persist_per_cu > 0: that many persistent workgroups per CU walk XCD-contiguous tile ranges; 0: one workgroup per tile
+    // one workgroup per tile
     const int threads = sdy ? u1t_threads(U, kU1tPatsSDY) : u1t_threads(U, 0);
-    const long long want = persist_per_cu > 0 ? (long long)persist_per_cu * num_cus : ntiles;
-    const unsigned grid = (unsigned)(ntiles < want ? ntiles : want);
     const size_t lds = 3 * (size_t)u1t_band_bytes<U>() + kU1tTileBytes + 16 + kU1tDirtyBytes + 80;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a, b, (uint32_t)detail_per_1024);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(threads), lds, st, a, b, (uint32_t)detail_per_1024);
     return hipGetLastError();
 }
 
-hipError_t launch_stage_u1t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, int persist_per_cu, hipStream_t st) {
+hipError_t launch_stage_u1t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, hipStream_t st) {
     if (a.C > 3 || a.M > kMaxModes || !a.fix_list || !a.fix_count) return hipErrorInvalidValue;
-    return launch_u1t_t<1>(a, b, detail_per_1024, num_cus, persist_per_cu, st);
+    return launch_u1t_t<1>(a, b, detail_per_1024, st);
 }
 
 hipError_t launch_stage_u1w_list(const StageArgs &a, int num_cus, hipStream_t st) {
@@ -941,18 +934,18 @@ __global__ void __launch_bounds__(256) stage_up_fix_site_kernel(StageArgs a) {
 // the same kernel family on a FINAL stage with u == 2 (4-value rows, 2 x 2 output blocks): b.band[m] = 8-byte-per-slot
 // tube band; flagged sites go to stage_up_fix_site_kernel through a.fix_list; a.verdict_take >= 0: tiles whose local-detail statistic
 // exceeds detail_per_1024 are marked in a.tile_list and left out (the caller runs the gather kernel on them)
-hipError_t launch_stage_u2t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, int persist_per_cu, hipStream_t st) {
+hipError_t launch_stage_u2t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, hipStream_t st) {
     if (a.C > 3 || a.M > kMaxModes || !a.fix_list || !a.fix_count || (a.verdict_take >= 0 && !a.tile_list)) return hipErrorInvalidValue;      // (a merged pair of rotations sums to <= 8160 per mode in its unsigned 16-bit field: 8 modes fit)
-    hipError_t e = launch_u1t_t<2>(a, b, detail_per_1024, num_cus, persist_per_cu, st);
+    hipError_t e = launch_u1t_t<2>(a, b, detail_per_1024, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(stage_up_fix_site_kernel<2>, dim3((unsigned)(4 * num_cus)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 // and with u == 3 (9-value rows as ten 16-bit fields, 24 bytes per slot; 3 x 3 output blocks)
-hipError_t launch_stage_u3t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, int persist_per_cu, hipStream_t st) {
+hipError_t launch_stage_u3t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, hipStream_t st) {
     if (a.C > 3 || a.M > kMaxModes || !a.fix_list || !a.fix_count || (a.verdict_take >= 0 && !a.tile_list)) return hipErrorInvalidValue;      // (a merged pair of rotations sums to <= 8160 per mode in its unsigned 16-bit field: 8 modes fit)
-    hipError_t e = launch_u1t_t<3>(a, b, detail_per_1024, num_cus, persist_per_cu, st);
+    hipError_t e = launch_u1t_t<3>(a, b, detail_per_1024, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(stage_up_fix_site_kernel<3>, dim3((unsigned)(4 * num_cus)), dim3(256), 0, st, a);
     return hipGetLastError();

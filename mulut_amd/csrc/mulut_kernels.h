@@ -55,7 +55,7 @@ struct StageArgs {
     int k1_tiles_x, k1_tiles_y, k1_oy0;
     int k1_n0;              // image 0 of this launch is image k1_n0 of that first-stage launch (sub-launches of a large batch)
     // tube kernel: pixels with a pass outside the tube are appended here (id = (n H + y) W + x) and recomputed by
-    // stage_up_fix_kernel; *fix_count is zeroed by the host side before the stage
+    // stage_up_fix2_kernel; *fix_count is zeroed by the host side before the stage
     uint32_t *fix_list;
     uint32_t *fix_count;
     // 1-byte-row tube kernel: tile_list[tile] = 1 for the tiles it leaves to the full-table kernel (stage_u1w_kernel in
@@ -107,19 +107,19 @@ struct DetailArgs {
 hipError_t raise_lds_limit(const void *kernel, int bytes);
 
 hipError_t launch_pass(const PassArgs &a, hipStream_t st);
-// non-final (or u == 1 final) stage: tables staged in LDS, one byte out per site
-// variant 0: window kernel (four adjacent pixels per thread, neighbours from registers), 1: one site per LDS read
-hipError_t launch_stage_u1(const StageArgs &a, hipStream_t st, int variant);
+// non-final (or u == 1 final) stage: tables staged in LDS, one byte out per site; window kernel (four adjacent pixels per thread,
+// neighbours from registers)
+hipError_t launch_stage_u1(const StageArgs &a, hipStream_t st);
 // the same stage on the tube band (b.band[m] = dword-per-slot band of mode m, kTube1BandBytes): computes every tile
 // whose local-detail statistic is at most detail_per_1024 (all tiles when a.tile_list is null), lists the others in
 // a.tile_list and the sites that may have left the tube in a.fix_list
-hipError_t launch_stage_u1t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, int persist_per_cu, hipStream_t st);
+hipError_t launch_stage_u1t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, hipStream_t st);
 // final stage with u == 2 on the tube band (8 bytes per slot: four 16-bit fields), + its site fix-up
 // (a.verdict_take >= 0: routed -- tiles above detail_per_1024 are marked in a.tile_list and left to launch_stage_up, which then
 // computes only marked tiles)
-hipError_t launch_stage_u2t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, int persist_per_cu, hipStream_t st);
+hipError_t launch_stage_u2t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, hipStream_t st);
 // final stage with u == 3 on the tube band (24 bytes per slot: the nine values as ten 16-bit fields, mulut_core.h), + its site fix-up
-hipError_t launch_stage_u3t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, int persist_per_cu, hipStream_t st);
+hipError_t launch_stage_u3t(const StageArgs &a, const BandArgs &b, unsigned detail_per_1024, int num_cus, hipStream_t st);
 // full-table kernel over the tiles marked in a.tile_list[]
 hipError_t launch_stage_u1w_list(const StageArgs &a, int num_cus, hipStream_t st);
 // recompute the sites in a.fix_list[0 .. *a.fix_count) from the full tables (1-byte rows)
@@ -139,7 +139,7 @@ constexpr int kMaxTube2Modes = 8;
 bool stage_tube2_supported(const StageArgs &a);
 hipError_t launch_stage_tube2(const StageArgs &a, const BandArgs &b, int out_mode, int num_cus, hipStream_t st);
 // recompute the pixels listed in a.fix_list[0 .. *a.fix_count) from the full tables (u == 4)
-hipError_t launch_stage_up_fix(const StageArgs &a, int out_mode, int num_cus, hipStream_t st, int variant = 0);
+hipError_t launch_stage_up_fix(const StageArgs &a, int num_cus, hipStream_t st);
 // detailed tiles (a.verdict[tile] == 1, 64x16 tiling) of a u == 4 final stage from anchor slabs in LDS: bucket, plan,
 // fill, slab and retile kernels; border columns are appended to a.fix_list.  d.thist comes from launch_tile_stat.
 bool detail_slab_supported(const StageArgs &a);
@@ -155,7 +155,6 @@ hipError_t launch_tile_stat(const StageArgs &a, uint32_t *verdict, uint32_t max_
 void stage_band_tile(int &tw, int &th);
 void stage_u1_tile(int &tw, int &th);
 void stage_up_tile(int &tw, int &th);
-const char *stage_u1_name(int variant);
 const char *stage_up_name(int u, int out_mode);
 
 // mode lists with a 4 x 4 pattern (e, h, o: reach 3 per stage), mulut_wide.hip.  Every stage of such a list runs here, any mix and

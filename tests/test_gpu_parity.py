@@ -359,15 +359,16 @@ def test_hybrid_final_stage_variants_agree_and_capture(eng, shipped_luts):
                 eng.set_tuning("hybrid_oob_per_1024", thr)
             assert torch.equal(eng.pipeline(x), want), (pipelined, sel, thr)
     eng.set_tuning("tube_pipelined", 1).set_tuning("hybrid_oob_per_1024", 128).set_tuning("final_stage_kernel", 0)
-    for key in ("stat_from_first_stage", "detail_kernel", "fix_kernel"):       # the routing / work-list options of the default path
-        for val in ((0, 1, 2) if key == "fix_kernel" else (0, 1)):
+    for key in ("stat_from_first_stage", "detail_kernel"):       # the routing / work-list options of the default path
+        for val in (0, 1):
             eng.set_tuning(key, val)
             assert torch.equal(eng.pipeline(x), want), (key, val)
-    eng.set_tuning("stat_from_first_stage", 1).set_tuning("detail_kernel", 0).set_tuning("fix_kernel", 0)
+    eng.set_tuning("stat_from_first_stage", 1).set_tuning("detail_kernel", 0)
     for first in (2, 3, 0):                 # first stage: window kernel everywhere, tube kernel everywhere, the routed default
         eng.set_tuning("first_stage_kernel", first)
         assert torch.equal(eng.pipeline(x), want), first
-    for retired in (("final_stage_kernel", 3), ("first_stage_kernel", 1), ("tube_site_flags", 1)):      # generations moved out in round 3
+    for retired in (("final_stage_kernel", 3), ("first_stage_kernel", 1), ("tube_site_flags", 1),      # generations moved out in round 3
+                    ("fix_kernel", 0), ("u1t_persist", 1)):                                              # and the variants that lost their A/B runs
         with pytest.raises(Exception):
             eng.set_tuning(*retired)
     # capture the default path
@@ -511,15 +512,32 @@ def test_five_to_eight_modes_on_the_lds_path(modes):
         want = np.stack([c_oracle.pipeline(luts, 2, modes, 4, im) for im in img])
         for sel in (0, 5, 1):
             e.set_tuning("final_stage_kernel", sel)
-            for fixk in (0, 1, 2):        # (1 merges rotation pairs in 16-bit fields: the library takes the default kernel for these lists)
-                e.set_tuning("fix_kernel", fixk)
-                assert np.array_equal(e.pipeline(dev(img)).cpu().numpy(), want), (modes, val, sel, fixk)
-            e.set_tuning("fix_kernel", 0)
+            assert np.array_equal(e.pipeline(dev(img)).cpu().numpy(), want), (modes, val, sel)
             # two channels (the byte-wise output form) and a planar batch (the dword form) of the same images
             got2 = e.pipeline(dev(np.ascontiguousarray(img[..., :2]))).cpu().numpy()
             assert np.array_equal(got2, want[..., :2]), (modes, val, sel, "C=2")
             gotp = e.pipeline(dev(np.ascontiguousarray(img.transpose(0, 3, 1, 2))), layout=0).cpu().numpy()
             assert np.array_equal(gotp, want.transpose(0, 3, 1, 2)), (modes, val, sel, "planar")
+        e.close()
+
+
+@pytest.mark.gpu
+def test_kernel_names_of_four_to_eight_mode_lists():
+    """The kernel name of an x4 final stage with four to eight modes is what runs: a list stage_tube2_kernel does not take (no y) goes to
+    the per-rotation gather kernel, and the detailed tiles of a hybrid beyond three modes to the gather kernel (the anchor-slab path
+    takes three modes at most)."""
+    from mulut_amd import MuLUTEngine
+    wide = "stage_up_kernel<4,generic,wide>"
+    for modes, detailed in (("sdsds", None), ("sdys", "stage_up_kernel<4,rgb>"), ("sdysd", wide), ("yyddsss", wide), ("sdysdysd", wide)):
+        e = MuLUTEngine(0).configure(2, modes, 4, 4)
+        if detailed is None:
+            assert e.kernel_name(True) == wide, modes
+        else:
+            for dk in (0, 1):
+                e.set_tuning("detail_kernel", dk)
+                assert e.kernel_name(True) == ("hybrid: tile_stat_kernel + stage_tube2_kernel<rgb> (smooth tiles) + %s (detailed tiles)" % detailed), (modes, dk)
+            e.set_tuning("final_stage_kernel", 5)
+            assert e.kernel_name(True) == "stage_tube2_kernel<rgb> + stage_up_fix2_kernel", modes
         e.close()
 
 
