@@ -40,7 +40,7 @@ enum {
     MULUT_EMODE = -2,       /* mode not in {s,d,y,e,h,o}: reference raises ValueError, 4_test_lut.py:54 */
     MULUT_ENOLUT = -3,      /* table (stage,mode) not set: reference raises from np.load, :333  */
     MULUT_ESHAPE = -4,      /* table shape does not match (rows, v_num) expected for the stage */
-    MULUT_EUNSUPPORTED = -5,/* interval != 4, scale not in 1..4, stages/modes beyond limits    */
+    MULUT_EUNSUPPORTED = -5,/* interval not in {4,5,6}, scale not in 1..4, stages/modes beyond limits */
     MULUT_EHIP = -6,        /* a HIP runtime call failed (mulut_last_hip_error() has the text) */
     MULUT_ENODEVICE = -7,   /* no usable gfx950 device: there is no CPU path                   */
     MULUT_ENOTCONFIGURED = -8,
@@ -69,14 +69,19 @@ int mulut_destroy(mulut_ctx *ctx);
  * 3 x 3 patterns s, d, y and the 4 x 4 patterns e, h, o (sr/model.py:12, common/network.py:173-215), up to MULUT_MAX_MODES.
  * A list holding e, h or o is "wide": its keys reach 3 pixels from the anchor, and every stage of it runs on the wide kernels
  * (one table in LDS per mode for 1-byte rows, full-table gathers for u*u-byte rows); a list of s, d, y only runs as before.
- * Only interval == 4 (q=16, L=17, 83521 rows) is supported -- the only value for which the
- * reference's reader and writers agree on file names. */
+ * interval is 4 (q=16, L=17, 83521 rows), 5 (q=32, L=9, 6561 rows) or 6 (q=64, L=5, 625 rows) (sr/4_test_lut.py:14-16); any other
+ * value returns MULUT_EUNSUPPORTED.  Every stage of an interval-5 / 6 context runs on stage_interval_kernel (the stage's tables in
+ * LDS when they fit 96 KiB, else rows gathered from global memory), whatever the mode list.  Configuring an interval other than
+ * the one the context's tables were set for clears every table: pipeline calls return MULUT_ENOLUT until they are set again, and
+ * graphs captured before are invalid (see the hipGraph note at mulut_set_tuning). */
 int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, int interval);
 
 /* Upload one table (any of the six patterns): replaces
  *   lutDict["s{stage}_{mode}"] = np.load(path).astype(np.float32).reshape(-1, v_num)
  * (sr/4_test_lut.py:322-333).  `host_rows` is the int8 C-order content of the .npy file,
- * rows = 17^4 = 83521, vnum = scale*scale for the last stage, 1 otherwise.  stage is 1-based. */
+ * rows = L^4 of the configured interval (83521 at 4 -- also before any mulut_configure() --, 6561 at 5, 625 at 6; anything else
+ * returns MULUT_ESHAPE), vnum = scale*scale for the last stage, 1 otherwise.  stage is 1-based.  At interval 5 / 6 the plain rows
+ * are uploaded (no tube bands, slabs or 16-bit images are built). */
 int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows, int64_t rows, int vnum);
 
 /* One (table, mode, rotation) pass: replaces FourSimplexInterpFaster(weight, img_in, h, w,
@@ -207,10 +212,14 @@ int mulut_eval_y(int device, const void *gt_hwc, const void *out_hwc, int H, int
  * "first_stage_detail_per_1024": tile threshold of first_stage_kernel 0 (default 24).
  * Wide mode lists (e, h, o): every key above is accepted and stored, but does not change their route -- all their stages run on
  *   the wide kernels (stage_wide1_kernel, stage_wide_up_kernel), which have no tube, hybrid, slab or work-list variants.
+ * Intervals 5 and 6: the same -- every key is accepted and stored, and their stages run on stage_interval_kernel regardless.
  * Unknown key or value: MULUT_EINVAL.
  * hipGraph capture: call mulut_reserve() for the largest (N, H, W, C) first -- the context's workspace, verdict and work-list
  * buffers are then never reallocated by smaller calls; a LARGER later call reallocates them and invalidates graphs captured
- * before it.  Run the call to be captured once outside capture first: the first launch of each kernel raises that kernel's
+ * before it.  Configuring the context at another interval frees every table, and mulut_set_lut() with a table of another size
+ * reallocates that table: graphs captured before either would replay against freed table memory and must be captured again
+ * (setting a table of the same shape rewrites it in place, so a captured graph then reads the new values).  Run the call to be
+ * captured once outside capture first: the first launch of each kernel raises that kernel's
  * dynamic-LDS limit (hipFuncSetAttribute), which is not a capturable operation.  These one-time per-device set-ups are
  * serialised inside the library: contexts may be created and first used from several host threads. */
 int mulut_set_tuning(mulut_ctx *ctx, const char *key, int value);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mulut.h"
+#include "mulut_interval.h"
 #include "mulut_kernels.h"
 
 using namespace mulut;
@@ -38,6 +39,7 @@ struct mulut_ctx {
     int device = 0;
     bool configured = false;
     int stages = 0, n_modes = 0, scale = 0, interval = 0;
+    int tab_interval = kInterval;   // the interval the tables in tab[][] were set for (configuring another one clears them)
     char modes[MULUT_MAX_MODES + 1] = {0};
     signed char di[MULUT_MAX_MODES][3], dj[MULUT_MAX_MODES][3];
     int reach = 2;  // LR rows one stage looks beyond its output rows
@@ -181,8 +183,8 @@ const char *mulut_strerror(int err) {
         case MULUT_EINVAL: return "invalid argument";
         case MULUT_EMODE: return "Mode not implemented.";
         case MULUT_ENOLUT: return "LUT for (stage, mode) not set";
-        case MULUT_ESHAPE: return "LUT shape does not match (83521, v_num) for this stage";
-        case MULUT_EUNSUPPORTED: return "unsupported configuration (interval must be 4, scale 1..4)";
+        case MULUT_ESHAPE: return "LUT shape does not match (L^4, v_num) for this stage (83521 rows at interval 4, 6561 at 5, 625 at 6)";
+        case MULUT_EUNSUPPORTED: return "unsupported configuration (interval must be 4, 5 or 6, scale 1..4)";
         case MULUT_EHIP: return "HIP runtime error";
         case MULUT_ENODEVICE: return "no usable HIP device (there is no CPU path)";
         case MULUT_ENOTCONFIGURED: return "mulut_configure() has not been called";
@@ -249,7 +251,7 @@ int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, in
     if (!ctx || !modes) return MULUT_EINVAL;
     const size_t M = strlen(modes);
     if (stages < 1 || stages > MULUT_MAX_STAGES || M < 1 || M > MULUT_MAX_MODES) return MULUT_EUNSUPPORTED;
-    if (interval != kInterval || scale < 1 || scale > 4) return MULUT_EUNSUPPORTED;
+    if ((interval != kInterval && interval != 5 && interval != 6) || scale < 1 || scale > 4) return MULUT_EUNSUPPORTED;
     // tiles of the s / d / y kernels always stage a 2-px halo (d / y patterns; s-only models use it too); a list with a 4 x 4
     // pattern (e, h, o) reaches 3 px per stage and runs on the wide kernels
     int reach = 2;
@@ -261,6 +263,19 @@ int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, in
             ctx->di[m][k] = (signed char)di[k];
             ctx->dj[m][k] = (signed char)dj[k];
         }
+    }
+    if (interval != ctx->tab_interval) {
+        // tables of another interval have another row count: none of them can serve this one (MULUT_ENOLUT until set again)
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        for (auto &st : ctx->tab)
+            for (auto &t : st) {
+                int rc = release(ctx, t.dev, t.bytes);
+                if (!rc) rc = release(ctx, t.tube, t.tube_bytes);
+                if (!rc) rc = release(ctx, t.slab, t.slab_bytes);
+                if (rc) return rc;
+                t.vnum = 0;
+            }
+        ctx->tab_interval = interval;
     }
     ctx->stages = stages;
     ctx->n_modes = (int)M;
@@ -296,13 +311,27 @@ int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows,
     if (stage < 1 || stage > MULUT_MAX_STAGES) return MULUT_EINVAL;
     const int pid = pattern_id(mode);
     if (pid < 0) return MULUT_EMODE;
-    if (rows != kRows) return MULUT_ESHAPE;
+    const int iv = ctx->tab_interval;
+    const int64_t want = iv == 5 ? IvGeom<5>::rows : iv == 6 ? IvGeom<6>::rows : kRows;
+    if (rows != want) return MULUT_ESHAPE;
     int u = 0;
     for (int k = 1; k <= 4; ++k)
         if (k * k == vnum) u = k;
     if (!u) return MULUT_ESHAPE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevTable &t = ctx->tab[stage - 1][pid];
+    if (iv != kInterval) {
+        // intervals 5 / 6: the plain int8 rows, padded to iv_row_bytes(u) (mulut_interval.hip reads nothing else)
+        const int rb = iv_row_bytes(u);
+        std::vector<uint8_t> img((size_t)iv_table_bytes((int)rows, u), 0);
+        for (int64_t i = 0; i < rows; ++i) memcpy(&img[(size_t)i * rb], host_rows + i * vnum, (size_t)vnum);
+        int rc = upload(ctx, t.dev, t.bytes, img);
+        if (!rc) rc = release(ctx, t.tube, t.tube_bytes);
+        if (!rc) rc = release(ctx, t.slab, t.slab_bytes);
+        if (rc) return rc;
+        t.vnum = vnum;
+        return MULUT_OK;
+    }
     std::vector<uint8_t> img;
     if (u == 1) {
         img.assign(kU1TableBytes, 0);
@@ -371,7 +400,8 @@ int mulut_pass(mulut_ctx *ctx, int stage, char mode, int r, const uint8_t *in_ch
         a.dj[k] = (signed char)dj[k];
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_pass(a, (hipStream_t)stream));
+    if (ctx->interval != kInterval) HIP_TRY(ctx, launch_pass_interval(a, ctx->interval, (hipStream_t)stream));
+    else HIP_TRY(ctx, launch_pass(a, (hipStream_t)stream));
     return MULUT_OK;
 }
 
@@ -390,6 +420,8 @@ static View make_view(const uint8_t *p, int layout, int rows, int W, int C, int 
 
 // Routes of a stage launch (plan_stage)
 enum Route {
+    kRouteIvLds,    // interval 5 / 6: stage_interval_kernel with the stage's tables in LDS
+    kRouteIvGlobal, // interval 5 / 6: stage_interval_kernel gathering rows from the tables in global memory
     kRouteWide1,    // a list with a 4 x 4 pattern (e, h, o), 1-byte rows: stage_wide1_kernel
     kRouteWideUp,   // the same, u > 1: stage_wide_up_kernel
     kRouteU1Full,   // 1-byte rows: window kernel (full table in LDS) on every tile
@@ -464,6 +496,14 @@ static StagePlan plan_stage(const mulut_ctx *ctx, const Routing &r, int u, const
             p.per_image = per_image;
         }
     };
+    if (ctx->interval != kInterval) {
+        // interval 5 / 6: every stage on stage_interval_kernel, before any other route (they are all built for q = 16, L = 17);
+        // the tables sit in LDS when the whole stage's fit kIvLdsBudget.  No work lists; the tuning keys do not apply
+        const int iv_rows = ctx->interval == 5 ? IvGeom<5>::rows : IvGeom<6>::rows;
+        tile_grid(a, stage_interval_tile, p.tiles_x, p.tiles_y);
+        p.route = (long long)a.M * iv_table_bytes(iv_rows, u) <= kIvLdsBudget ? kRouteIvLds : kRouteIvGlobal;
+        return p;
+    }
     if (ctx->wide) {
         // a list with a 4 x 4 pattern: every stage on the wide kernels, before any tube / hybrid / slab / fix-up / tile-statistic
         // path (they all stage a 2-px halo or assume the s / d / y offsets); no work lists
@@ -565,6 +605,19 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
     const StagePlan p = plan_stage(ctx, ctx->routing, u, a, out_layout, packed_ok);
     a.tiles_x = p.tiles_x;
     a.tiles_y = p.tiles_y;
+    if (p.route == kRouteIvLds || p.route == kRouteIvGlobal) {
+        ctx->k1_valid = false;      // (no tile marks are left for the next stage)
+        const bool last = stage == ctx->stages;
+        IvArgs v;
+        memset(&v, 0, sizeof(v));
+        for (int m = 0; m < kMaxModes; ++m) v.pat[m] = m < ctx->n_modes ? pattern_id(ctx->modes[m]) : 0;
+        v.reach = ctx->reach;
+        v.dm = make_div_magic((uint32_t)iv_div_modes(ctx->n_modes, last));
+        v.bias_num = ctx->interval == 5 ? iv_bias_num<5>(ctx->n_modes, last) : iv_bias_num<6>(ctx->n_modes, last);
+        v.table_bytes = iv_table_bytes(ctx->interval == 5 ? IvGeom<5>::rows : IvGeom<6>::rows, u);
+        MAIN_KERNEL(ctx, stage, st, launch_stage_interval(a, v, ctx->interval, u, p.route == kRouteIvLds, ctx->num_cus, st));
+        return MULUT_OK;
+    }
     if (p.route == kRouteWide1 || p.route == kRouteWideUp) {
         ctx->k1_valid = false;      // (no tile marks are left for the next stage)
         WideArgs wa;
@@ -922,6 +975,8 @@ const char *mulut_kernel_name(const mulut_ctx *ctx, int is_final) {
     const View in = make_view(nullptr, MULUT_LAYOUT_CHW, 64, 64, 3, 0);
     const StagePlan p = plan_stage(ctx, ctx->routing, u, stage_args(ctx, stage, in, in, 1, 64, 64, 3, 0, 64), MULUT_LAYOUT_HWC, true);
     switch (p.route) {
+        case kRouteIvLds:
+        case kRouteIvGlobal: return stage_interval_name(ctx->interval, u, p.route == kRouteIvLds);
         case kRouteWide1:
         case kRouteWideUp: return stage_wide_name(u);
         case kRouteU1Full: return "stage_u1w_kernel";

@@ -99,6 +99,9 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
 
 constexpr int kPatDi[3][3] = {{0, 1, 1}, {0, 2, 2}, {1, 1, 2}};   // s, d, y: row offsets of keys b, c, d (pattern_offsets)
 constexpr int kPatDj[3][3] = {{1, 0, 1}, {2, 0, 2}, {1, 2, 1}};
+// rows / columns of keys b, c, d per pattern id (mulut_capi.hip pattern_id: s, d, y, e, h, o) -- pattern_offsets() as constants
+constexpr int kWideDi[6][3] = {{0, 1, 1}, {0, 2, 2}, {1, 1, 2}, {0, 3, 3}, {2, 2, 3}, {2, 1, 3}};
+constexpr int kWideDj[6][3] = {{1, 0, 1}, {2, 0, 2}, {1, 2, 1}, {3, 0, 3}, {2, 3, 2}, {2, 3, 1}};
 constexpr int rot_dy(int r, int di, int dj) { return r == 0 ? di : r == 1 ? dj : r == 2 ? -di : -dj; }   // sample_offset
 constexpr int rot_dx(int r, int di, int dj) { return r == 0 ? dj : r == 1 ? -di : r == 2 ? -dj : di; }
 

@@ -169,5 +169,23 @@ hipError_t launch_stage_wide_up(const StageArgs &a, int u, hipStream_t st);
 void stage_wide_tile(int u, int &tw, int &th);
 const char *stage_wide_name(int u);
 
+// sampling intervals 5 and 6 (q = 32 / 64, L = 9 / 5), mulut_interval.hip.  Every stage of a context configured at these intervals
+// runs here, any mode list, any u; tables are plain int8 rows (mulut_interval.h iv_row_bytes), no tube band, slab or work list.
+//   launch_stage_interval  lds: every table of the stage staged into LDS once per persistent workgroup (kIvLdsBudget), else rows
+//                          gathered from the tables in global memory; 64 x 64 tiles with a 3-px halo, 32-bit sums
+//   launch_pass_interval   mulut_pass: q * out as int32
+constexpr int kIvLdsBudget = 96 * 1024;      // the stage's tables (M * iv_table_bytes) go to LDS when they fit this
+struct IvArgs {
+    int pat[kMaxModes];   // pattern of mode m: 0..5 = s, d, y, e, h, o (one instance of the pass body per pattern)
+    int reach;            // rows beyond [oy0, oy1) the caller's band holds (2, or 3 for a list with e, h or o)
+    DivMagic dm;          // epilogue divisor / 2^(interval - 1): 2 M (final stage) or 8 M (mulut_interval.h iv_div_modes)
+    int bias_num;         // 127 q 4 M (non-final stage) or 0
+    int table_bytes;      // iv_table_bytes of one mode's table
+};
+hipError_t launch_stage_interval(const StageArgs &a, const IvArgs &v, int interval, int u, bool lds, int num_cus, hipStream_t st);
+hipError_t launch_pass_interval(const PassArgs &a, int interval, hipStream_t st);
+void stage_interval_tile(int &tw, int &th);
+const char *stage_interval_name(int interval, int u, bool lds);
+
 }  // namespace mulut
 #endif

@@ -15,10 +15,6 @@ namespace mulut {
 
 constexpr int kWideHalo = 3;      // pattern_reach() of e, h, o
 
-// rows / columns of keys b, c, d per pattern id (mulut_capi.hip pattern_id: s, d, y, e, h, o) -- pattern_offsets() as constants
-constexpr int kWideDi[6][3] = {{0, 1, 1}, {0, 2, 2}, {1, 1, 2}, {0, 3, 3}, {2, 2, 3}, {2, 1, 3}};
-constexpr int kWideDj[6][3] = {{1, 0, 1}, {2, 0, 2}, {1, 2, 1}, {3, 0, 3}, {2, 3, 2}, {2, 3, 1}};
-
 // ------------------------------------------------------------------------------------------
 // 1-byte rows.  Tile 64 x 64, 1024 threads, a thread owns four horizontally adjacent pixels of a row.  LDS:
 //   [ table: kU1TableBytes = 83,536 ][ image: C x 70 rows x 72 bytes (64 + 2 x 3 columns, padded to whole dwords) = 15,120 for C = 3 ]

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .lut_io import load_lut_dict
+from .lut_io import load_lut_dict, lut_rows
 
 LAYOUT_CHW, LAYOUT_HWC = 0, 1
 
@@ -30,7 +30,7 @@ class MuLUTEngine:
         h = ctypes.c_void_p()
         self._check(self._lib.mulut_create(self.device.index, ctypes.byref(h)))
         self._h = h
-        self.stages = self.modes = self.scale = None
+        self.stages = self.modes = self.scale = self.interval = None
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc):
@@ -82,7 +82,8 @@ class MuLUTEngine:
         t = np.ascontiguousarray(table)
         if t.dtype != np.int8:
             raise TypeError("LUT must be int8")
-        t = t.reshape(17 ** 4, -1) if t.size % 17 ** 4 == 0 else t
+        rows = lut_rows(getattr(self, "interval", None) or 4)      # the configured interval's L^4 (interval 4 before configure())
+        t = t.reshape(rows, -1) if t.size % rows == 0 else t
         self._check(self._lib.mulut_set_lut(self._h, int(stage), mode.encode()[:1], t.ctypes.data, t.shape[0],
                                             int(t.shape[1]) if t.ndim == 2 else 0))
 

@@ -80,7 +80,8 @@ class MuLUT(nn.Module):
     def __init__(self, lut_folder, stages, modes, upscale=4, interval=4):
         super().__init__()
         if interval != 4:
-            raise NotImplementedError("only interval 4 is supported")
+            # the fine-tuning kernels (mulut_ft.hip) are built for q = 16, L = 17; inference runs intervals 5 and 6 as well
+            raise NotImplementedError("fine-tuning is interval-4 only (got interval {})".format(interval))
         self.interval, self.upscale, self.stages = interval, upscale, stages
         self.modes = "".join(modes)
         for mode in self.modes:

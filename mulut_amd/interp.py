@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from .engine import MuLUTEngine
+from .lut_io import INTERVALS, lut_rows
 
 _ENGINES = {}
 _PAD = {"s": 1, "d": 2, "y": 2, "e": 3, "h": 3, "o": 3}      # sr/model.py:12
@@ -25,11 +26,11 @@ def _engine(device):
 def FourSimplexInterpFaster(weight, img_in, h, w, interval, rot, upscale=4, mode='s', device=0):
     if mode not in _PAD:
         raise ValueError("Mode {} not implemented.".format(mode))
-    if interval != 4:
-        raise NotImplementedError("only --interval 4 is supported (SURVEY.md quirk 3)")
+    if interval not in INTERVALS:
+        raise NotImplementedError("only --interval 4, 5 and 6 are supported")
     weight = np.asarray(weight)
     img_in = np.asarray(img_in)
-    table = np.ascontiguousarray(weight.reshape(17 ** 4, upscale * upscale))
+    table = np.ascontiguousarray(weight.reshape(lut_rows(interval), upscale * upscale))
     q8 = table.astype(np.int8)
     if not np.array_equal(q8.astype(table.dtype), table):
         raise ValueError("weight must hold int8-valued entries (it is np.load(int8 LUT).astype(float32))")
