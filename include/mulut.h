@@ -178,6 +178,17 @@ int mulut_ft_stage_forward_mask(int device, const float *const *weights_q, const
 int mulut_ft_stage_backward_mask(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                                  const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
                                  float *const *grad_wq, float *grad_x, void *stream);
+/* The masked pair at the sampling intervals 5 and 6: the module built with interval = 5 / 6 (sr/model.py:42-44, q = 2^interval and
+ * L = 2^(8-interval) + 1 in InterpTorchBatch, :78-80; driver sr/3_finetune_lut.py:82,166).  weights_q are float32 [L^4][u*u]
+ * (6,561 / 625 rows); everything else is as above.  interval other than 5 or 6 returns MULUT_EUNSUPPORTED (interval 4 is the
+ * functions above), as do u outside 1..4 and more than MULUT_MAX_MODES modes; a mode outside s, d, y MULUT_EMODE; a NULL pointer
+ * (the mask included) or a non-positive size MULUT_EINVAL -- all decided before the device is touched.  mulut_ft_quantize and
+ * mulut_ft_quantize_backward serve these tables unchanged. */
+int mulut_ft_interval_stage_forward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                    const float *x, int B, int C, int H, int W, float *out, unsigned short *inside, void *stream);
+int mulut_ft_interval_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                     const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
+                                     float *const *grad_wq, float *grad_x, void *stream);
 
 /* ---- device-side evaluation (not on the inference path) ---------------------------------------------------
  * Y-channel PSNR and SSIM of a super-resolved frame against its ground truth, exactly as the test script scores

@@ -25,7 +25,7 @@ class _StageFn(torch.autograd.Function):
     """One stage: all modes x 4 rotations, per-pass BPDA rounding, clamp/round of the stage output."""
 
     @staticmethod
-    def forward(ctx, x, modes, is_last, u, *weights):
+    def forward(ctx, x, modes, is_last, u, interval, *weights):
         lib = _native.load()
         x = x.contiguous()
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
@@ -43,18 +43,22 @@ class _StageFn(torch.autograd.Function):
         out = torch.empty((B, C, H * u, W * u), dtype=torch.float32, device=x.device)
         # where the stage's clamp passes gradient, 16 bits per site: saves the backward a recomputation of the stage forward
         inside = torch.empty((B, C, H, W), dtype=torch.int16, device=x.device)
-        rc = lib.mulut_ft_stage_forward_mask(x.device.index, _ptr_array(wq), modes.encode(), int(is_last), int(u), x.data_ptr(),
-                                             B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
+        if interval == 4:
+            rc = lib.mulut_ft_stage_forward_mask(x.device.index, _ptr_array(wq), modes.encode(), int(is_last), int(u), x.data_ptr(),
+                                                 B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
+        else:       # intervals 5 and 6: mulut_ft_interval.hip
+            rc = lib.mulut_ft_interval_stage_forward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                                     x.data_ptr(), B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
         if rc:
             raise (ValueError if rc == -2 else RuntimeError)(lib.mulut_strerror(rc).decode())
         ctx.save_for_backward(x, wq_all, inside, *ws)
-        ctx.cfg = (modes, is_last, u)
+        ctx.cfg = (modes, is_last, u, interval)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         lib = _native.load()
-        modes, is_last, u = ctx.cfg
+        modes, is_last, u, interval = ctx.cfg
         x, wq_all, inside, *ws = ctx.saved_tensors
         wq = [wq_all[m].view(w.shape) for m, w in enumerate(ws)]
         gout = gout.contiguous()
@@ -63,25 +67,29 @@ class _StageFn(torch.autograd.Function):
         gwq = [g_all[m].view(w.shape) for m, w in enumerate(ws)]
         gx = torch.zeros_like(x)
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        rc = lib.mulut_ft_stage_backward_mask(x.device.index, _ptr_array(wq), modes.encode(), int(is_last), int(u), x.data_ptr(),
-                                              gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq), gx.data_ptr(), stream)
+        if interval == 4:
+            rc = lib.mulut_ft_stage_backward_mask(x.device.index, _ptr_array(wq), modes.encode(), int(is_last), int(u), x.data_ptr(),
+                                                  gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq), gx.data_ptr(), stream)
+        else:
+            rc = lib.mulut_ft_interval_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                                      x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
+                                                      gx.data_ptr(), stream)
         if rc:
             raise RuntimeError(lib.mulut_strerror(rc).decode())
         # backward of clamp(round_func(w*127)): round is identity (BPDA), clamp passes inside [-127,127], x127 -- in place, one launch
         rc = lib.mulut_ft_quantize_backward(x.device.index, _ptr_array(ws), _ptr_array(gwq), len(ws), ws[0].numel(), stream)
         if rc:
             raise RuntimeError(lib.mulut_strerror(rc).decode())
-        return (gx, None, None, None) + tuple(gwq)
+        return (gx, None, None, None, None) + tuple(gwq)
 
 
 class MuLUT(nn.Module):
-    """PyTorch module for LUT-aware fine-tuning on the GPU (twin of sr/model.py:39-312)."""
+    """PyTorch module for LUT-aware fine-tuning on the GPU (twin of sr/model.py:39-312), sampling interval 4.
+    Intervals 5 and 6 are ``MuLUTInterval``."""
 
     def __init__(self, lut_folder, stages, modes, upscale=4, interval=4):
         super().__init__()
-        if interval != 4:
-            # the fine-tuning kernels (mulut_ft.hip) are built for q = 16, L = 17; inference runs intervals 5 and 6 as well
-            raise NotImplementedError("fine-tuning is interval-4 only (got interval {})".format(interval))
+        self._check_interval(interval)
         self.interval, self.upscale, self.stages = interval, upscale, stages
         self.modes = "".join(modes)
         for mode in self.modes:
@@ -100,14 +108,21 @@ class MuLUT(nn.Module):
 
     def forward(self, x):
         if not x.is_cuda:
-            raise RuntimeError("mulut_amd.finetune.MuLUT has no CPU path; move the module and input to the GPU")
+            raise RuntimeError("mulut_amd.finetune.{} has no CPU path; move the module and input to the GPU".format(type(self).__name__))
         x = x * 255.0
         for s in range(self.stages):
             stage = s + 1
             last = stage == self.stages
             weights = [getattr(self, "weight_s{}_{}".format(stage, m)) for m in self.modes]
-            x = _StageFn.apply(x, self.modes, last, self.upscale if last else 1, *weights)
+            x = _StageFn.apply(x, self.modes, last, self.upscale if last else 1, self.interval, *weights)
         return x / 255.0
+
+    @staticmethod
+    def _check_interval(interval):
+        if interval != 4:
+            # this class runs the kernels of mulut_ft.hip, built for q = 16, L = 17
+            raise NotImplementedError("mulut_amd.finetune.MuLUT: fine-tuning is interval-4 only (got interval {}); "
+                                      "intervals 5 and 6 are mulut_amd.finetune.MuLUTInterval".format(interval))
 
     def export_int8(self):
         """{ 's{stage}_{mode}': int8 table } as sr/3_finetune_lut.py:162-169 writes LUT_ft_*.npy."""
@@ -117,3 +132,18 @@ class MuLUT(nn.Module):
                 w = getattr(self, "weight_s{}_{}".format(s + 1, m)).detach().cpu().numpy()
                 out["s{}_{}".format(s + 1, m)] = np.round(np.clip(w, -1, 1) * 127).astype(np.int8)
         return out
+
+
+class MuLUTInterval(MuLUT):
+    """The same module at the sampling intervals 5 and 6 (the reference's ``MuLUT(..., interval=5 | 6)``, sr/model.py:42-44):
+    tables of 6,561 / 625 rows, read from ``LUT_x{scale}_{interval}bit_int8_s{stage}_{mode}.npy`` as transfer_to_lut writes them;
+    the stages run on the kernels of mulut_amd/csrc/mulut_ft_interval.hip."""
+
+    def __init__(self, lut_folder, stages, modes, upscale=4, interval=5):
+        super().__init__(lut_folder, stages, modes, upscale=upscale, interval=interval)
+
+    @staticmethod
+    def _check_interval(interval):
+        if interval not in (5, 6):
+            raise ValueError("mulut_amd.finetune.MuLUTInterval takes interval 5 or 6 (got {}); interval 4 is "
+                             "mulut_amd.finetune.MuLUT".format(interval))
