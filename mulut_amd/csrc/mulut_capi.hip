@@ -312,8 +312,7 @@ int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows,
     const int pid = pattern_id(mode);
     if (pid < 0) return MULUT_EMODE;
     const int iv = ctx->tab_interval;
-    const int64_t want = iv == 5 ? IvGeom<5>::rows : iv == 6 ? IvGeom<6>::rows : kRows;
-    if (rows != want) return MULUT_ESHAPE;
+    if (rows != interval_rows(iv)) return MULUT_ESHAPE;
     int u = 0;
     for (int k = 1; k <= 4; ++k)
         if (k * k == vnum) u = k;
@@ -321,7 +320,7 @@ int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevTable &t = ctx->tab[stage - 1][pid];
     if (iv != kInterval) {
-        // intervals 5 / 6: the plain int8 rows, padded to iv_row_bytes(u) (mulut_interval.hip reads nothing else)
+        // intervals 5 / 6: the plain int8 rows, padded to iv_row_bytes(u) (stage_interval_kernel and pass_kernel<5 / 6> read nothing else)
         const int rb = iv_row_bytes(u);
         std::vector<uint8_t> img((size_t)iv_table_bytes((int)rows, u), 0);
         for (int64_t i = 0; i < rows; ++i) memcpy(&img[(size_t)i * rb], host_rows + i * vnum, (size_t)vnum);
@@ -400,8 +399,7 @@ int mulut_pass(mulut_ctx *ctx, int stage, char mode, int r, const uint8_t *in_ch
         a.dj[k] = (signed char)dj[k];
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->interval != kInterval) HIP_TRY(ctx, launch_pass_interval(a, ctx->interval, (hipStream_t)stream));
-    else HIP_TRY(ctx, launch_pass(a, (hipStream_t)stream));
+    HIP_TRY(ctx, launch_pass(a, ctx->interval, (hipStream_t)stream));
     return MULUT_OK;
 }
 
@@ -499,9 +497,8 @@ static StagePlan plan_stage(const mulut_ctx *ctx, const Routing &r, int u, const
     if (ctx->interval != kInterval) {
         // interval 5 / 6: every stage on stage_interval_kernel, before any other route (they are all built for q = 16, L = 17);
         // the tables sit in LDS when the whole stage's fit kIvLdsBudget.  No work lists; the tuning keys do not apply
-        const int iv_rows = ctx->interval == 5 ? IvGeom<5>::rows : IvGeom<6>::rows;
         tile_grid(a, stage_interval_tile, p.tiles_x, p.tiles_y);
-        p.route = (long long)a.M * iv_table_bytes(iv_rows, u) <= kIvLdsBudget ? kRouteIvLds : kRouteIvGlobal;
+        p.route = (long long)a.M * iv_table_bytes(interval_rows(ctx->interval), u) <= kIvLdsBudget ? kRouteIvLds : kRouteIvGlobal;
         return p;
     }
     if (ctx->wide) {
@@ -591,6 +588,11 @@ static int ensure_plan(mulut_ctx *ctx, const StagePlan &p) {
     return rc;
 }
 
+// pattern id of every mode of the list (kernels that take one instance of their pass body per pattern)
+static void fill_patterns(const mulut_ctx *ctx, PatternArgs &p) {
+    for (int m = 0; m < kMaxModes; ++m) p.pat[m] = m < ctx->n_modes ? pattern_id(ctx->modes[m]) : 0;
+}
+
 // Launch one stage: input view holds LR rows [in.row0, ...), outputs for LR rows [oy0, oy1).
 // C channels are processed (<= 3); they may be a group of an image with more (then the views carry that image's strides and
 // packed_ok is false: the packed-RGB store needs a pixel stride of exactly 3)
@@ -610,18 +612,18 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
         const bool last = stage == ctx->stages;
         IvArgs v;
         memset(&v, 0, sizeof(v));
-        for (int m = 0; m < kMaxModes; ++m) v.pat[m] = m < ctx->n_modes ? pattern_id(ctx->modes[m]) : 0;
+        fill_patterns(ctx, v);
         v.reach = ctx->reach;
         v.dm = make_div_magic((uint32_t)iv_div_modes(ctx->n_modes, last));
         v.bias_num = ctx->interval == 5 ? iv_bias_num<5>(ctx->n_modes, last) : iv_bias_num<6>(ctx->n_modes, last);
-        v.table_bytes = iv_table_bytes(ctx->interval == 5 ? IvGeom<5>::rows : IvGeom<6>::rows, u);
+        v.table_bytes = iv_table_bytes(interval_rows(ctx->interval), u);
         MAIN_KERNEL(ctx, stage, st, launch_stage_interval(a, v, ctx->interval, u, p.route == kRouteIvLds, ctx->num_cus, st));
         return MULUT_OK;
     }
     if (p.route == kRouteWide1 || p.route == kRouteWideUp) {
         ctx->k1_valid = false;      // (no tile marks are left for the next stage)
-        WideArgs wa;
-        for (int m = 0; m < kMaxModes; ++m) wa.pat[m] = m < ctx->n_modes ? pattern_id(ctx->modes[m]) : 0;
+        PatternArgs wa;
+        fill_patterns(ctx, wa);
         if (p.route == kRouteWide1) MAIN_KERNEL(ctx, stage, st, launch_stage_wide1(a, wa, st));
         else MAIN_KERNEL(ctx, stage, st, launch_stage_wide_up(a, u, st));
         return MULUT_OK;

@@ -5,7 +5,8 @@
 // NOT a product path -- mulut_amd never runs it).
 //
 // Reference behaviour restated here (paths relative to the reference repo):
-//   simplex4()      : MSB/LSB split, corner indices, 24-case simplex weights   sr/4_test_lut.py:15-51,56-109,140-230
+//   simplex4<IV>()  : MSB/LSB split, corner indices, 24-case simplex weights   sr/4_test_lut.py:15-51,56-109,140-230
+//                     (IV = the sampling interval, 4 unless said otherwise)
 //   sample_offset() : np.rot90 + bottom/right edge pad as seen from the un-rotated image  :294-296
 //   row_elem()      : block->image reshuffle + rotate back                      :232-235
 //   rhe_clip_u8()   : pred/avg + bias, np.round (half to even), clip            :300-306
@@ -22,15 +23,31 @@
 
 namespace mulut {
 
-constexpr int kInterval = 4;            // --interval 4 (common/option.py:23)
-constexpr int kQ = 1 << kInterval;      // 16
-constexpr int kL = (1 << (8 - kInterval)) + 1;  // 17
-constexpr int kStrideA = kL * kL * kL;  // 4913  key a (anchor pixel) is most significant (:61)
-constexpr int kStrideB = kL * kL;       // 289
-constexpr int kStrideC = kL;            // 17
-constexpr int kStrideD = 1;
-constexpr int kRows = kL * kL * kL * kL;            // 83521
-constexpr int kAllStrides = kStrideA + kStrideB + kStrideC + kStrideD;  // 5220: p1111 - p0000
+// Geometry of a sampling interval IV (--interval, common/option.py:23; sr/4_test_lut.py:14-16): q = 2^IV, L = 2^(8-IV) + 1
+template <int IV>
+struct IvGeom {
+    static_assert(IV >= 4 && IV <= 6, "sampling intervals 4, 5 and 6");
+    static constexpr int q = 1 << IV;                   // 16, 32, 64
+    static constexpr int L = (1 << (8 - IV)) + 1;       // 17, 9, 5
+    static constexpr int sA = L * L * L, sB = L * L, sC = L, sD = 1;   // key a (anchor pixel) is most significant (:61)
+    static constexpr int rows = L * L * L * L;          // 83521, 6561, 625
+    static constexpr int all = sA + sB + sC + sD;       // p1111 - p0000
+};
+// rows of a table at a run-time interval (0: not an interval)
+MULUT_HD constexpr int interval_rows(int interval) {
+    return interval == 4 ? IvGeom<4>::rows : interval == 5 ? IvGeom<5>::rows : interval == 6 ? IvGeom<6>::rows : 0;
+}
+
+// Interval 4 is what the timed kernels are built for (tube bands, slabs, 16-bit sums); its geometry by name:
+constexpr int kInterval = 4;
+constexpr int kQ = IvGeom<kInterval>::q;                // 16
+constexpr int kL = IvGeom<kInterval>::L;                // 17
+constexpr int kStrideA = IvGeom<kInterval>::sA;         // 4913
+constexpr int kStrideB = IvGeom<kInterval>::sB;         // 289
+constexpr int kStrideC = IvGeom<kInterval>::sC;         // 17
+constexpr int kStrideD = IvGeom<kInterval>::sD;
+constexpr int kRows = IvGeom<kInterval>::rows;          // 83521
+constexpr int kAllStrides = IvGeom<kInterval>::all;     // 5220
 
 MULUT_HD int imin(int a, int b) { return a < b ? a : b; }
 MULUT_HD int imax(int a, int b) { return a > b ? a : b; }
@@ -86,15 +103,19 @@ MULUT_HD void cmpx_desc(uint32_t &a, uint32_t &b) {
 }
 
 // One site: four key values (0..255) -> five table row indices along the monotone vertex path
-// 0000 -> ... -> 1111 and their integer weights (sum 16).  The fractional parts are sorted
-// descending by a 5-comparator network on (f << 16 | stride) keys; ties only ever reorder
-// zero-weight vertices, so any tie order reproduces the reference's 24-case cascade.
+// 0000 -> ... -> 1111 and their integer weights (q - f1, f1 - f2, f2 - f3, f3 - f4, f4), sum q.
+// h = v >> IV, f = v & (q - 1).  The fractional parts are sorted descending by a 5-comparator
+// network on (f << 16 | stride) keys; ties only ever reorder zero-weight vertices, so any tie
+// order reproduces the reference's 24-case cascade.
+template <int IV = kInterval>
 MULUT_HD void simplex4(int va, int vb, int vc, int vd, int (&idx)[5], int (&w)[5]) {
-    const int base = (va >> 4) * kStrideA + (vb >> 4) * kStrideB + (vc >> 4) * kStrideC + (vd >> 4);
-    uint32_t k0 = ((uint32_t)(va & 15) << 16) | kStrideA;
-    uint32_t k1 = ((uint32_t)(vb & 15) << 16) | kStrideB;
-    uint32_t k2 = ((uint32_t)(vc & 15) << 16) | kStrideC;
-    uint32_t k3 = ((uint32_t)(vd & 15) << 16) | kStrideD;
+    using G = IvGeom<IV>;
+    constexpr int mask = G::q - 1;
+    const int base = (va >> IV) * G::sA + (vb >> IV) * G::sB + (vc >> IV) * G::sC + (vd >> IV);
+    uint32_t k0 = ((uint32_t)(va & mask) << 16) | (uint32_t)G::sA;
+    uint32_t k1 = ((uint32_t)(vb & mask) << 16) | (uint32_t)G::sB;
+    uint32_t k2 = ((uint32_t)(vc & mask) << 16) | (uint32_t)G::sC;
+    uint32_t k3 = ((uint32_t)(vd & mask) << 16) | (uint32_t)G::sD;
     cmpx_desc(k0, k1);
     cmpx_desc(k2, k3);
     cmpx_desc(k0, k2);
@@ -105,8 +126,8 @@ MULUT_HD void simplex4(int va, int vb, int vc, int vd, int (&idx)[5], int (&w)[5
     idx[1] = idx[0] + (int)(k0 & 0xFFFFu);
     idx[2] = idx[1] + (int)(k1 & 0xFFFFu);
     idx[3] = idx[2] + (int)(k2 & 0xFFFFu);
-    idx[4] = base + kAllStrides;
-    w[0] = kQ - f1;
+    idx[4] = base + G::all;
+    w[0] = G::q - f1;
     w[1] = f1 - f2;
     w[2] = f2 - f3;
     w[3] = f3 - f4;
@@ -136,11 +157,12 @@ MULUT_HD uint32_t rhe_clip_u8(int n, DivMagic m) {
     return v > 255u ? 255u : v;
 }
 
-// Stage epilogue numerators: K = q * pred summed over modes x 4 rotations.
-//   non-final stage: out = clip(rhe((K + 127*64M) / 64M))   (avg = 4M, bias = 127, :286)
-//   final stage    : out = clip(rhe( K           / 16M))    (avg = M,  bias = 0,   :283)
+// Stage epilogue numerators: K = q * pred summed over modes x 4 rotations, q = 2^IV.
+//   non-final stage: out = clip(rhe((K + 127 q 4M) / (q 4M)))   (avg = 4M, bias = 127, :286)
+//   final stage    : out = clip(rhe( K             / (q M)))    (avg = M,  bias = 0,   :283)
 MULUT_HD int stage_divisor(int n_modes, bool is_last) { return is_last ? kQ * n_modes : kQ * 4 * n_modes; }
-MULUT_HD int stage_bias_num(int n_modes, bool is_last) { return is_last ? 0 : 127 * kQ * 4 * n_modes; }
+template <int IV = kInterval>
+MULUT_HD int stage_bias_num(int n_modes, bool is_last) { return is_last ? 0 : 127 * IvGeom<IV>::q * 4 * n_modes; }
 
 // ---- 16-bit SWAR accumulation of u*u-byte table rows (final-stage kernel) -------------------------
 // Device tables with v_num > 1 store value+128 as uint8, so every partial sum is non-negative.  A

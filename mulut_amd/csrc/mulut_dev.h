@@ -1,4 +1,5 @@
-// mulut_dev.h -- device helpers shared by the kernel translation units (mulut_kernels.hip, mulut_k1.hip, mulut_detail.hip):
+// mulut_dev.h -- device helpers shared by the kernel translation units (mulut_kernels.hip, mulut_k1.hip, mulut_detail.hip,
+// mulut_wide.hip, mulut_interval.hip):
 // image views and tile staging, pattern / rotation constants, packed 16-bit MAC and SDWA helpers, the per-rotation SWAR
 // accumulators of the final stage with their epilogues.  Device code only; see mulut_core.h for the per-site arithmetic.
 #ifndef MULUT_DEV_H_
@@ -63,6 +64,17 @@ __device__ __forceinline__ void load_tile_batched(const StageArgs &a, int n, int
     }
 }
 
+// The tile of the kernels that serve all six patterns (mulut_wide.hip, mulut_interval.hip): a halo of 3 px, the largest
+// pattern_reach().  64 x 64 pixels, 1024 threads, four horizontally adjacent pixels per thread; rows of 72 bytes (64 + 2 x 3
+// columns, padded to whole dwords) x 70.  Each of the two files stages it with its own copy of load_tile_batched (3-px halo, this
+// pitch, the caller's row reach): through one shared loader their kernels came out 2-3 instructions different and missed the
+// head-against-parent timing bar (profiles/shared_helpers_ab.json).
+constexpr int kHalo3 = 3;
+constexpr int K3_TW = 64, K3_TH = 64, K3_NT = 1024;
+constexpr int K3_PW = 72, K3_PH = K3_TH + 2 * kHalo3;
+static_assert(K3_PW >= K3_TW + 2 * kHalo3 && K3_PW % 4 == 0, "tile rows hold the halo and are dword-aligned");
+static_assert(K3_TW * K3_TH == 4 * K3_NT, "four adjacent pixels per thread");
+
 // same tile, stored as 16-bit pixel codes (mulut_core.h pixel_code) for the expanded-band kernel
 template <int TW, int TH, int NT>
 __device__ __forceinline__ void load_tile_code(const StageArgs &a, int n, int y0, int x0, uint16_t *s_img) {
@@ -97,11 +109,9 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-constexpr int kPatDi[3][3] = {{0, 1, 1}, {0, 2, 2}, {1, 1, 2}};   // s, d, y: row offsets of keys b, c, d (pattern_offsets)
-constexpr int kPatDj[3][3] = {{1, 0, 1}, {2, 0, 2}, {1, 2, 1}};
 // rows / columns of keys b, c, d per pattern id (mulut_capi.hip pattern_id: s, d, y, e, h, o) -- pattern_offsets() as constants
-constexpr int kWideDi[6][3] = {{0, 1, 1}, {0, 2, 2}, {1, 1, 2}, {0, 3, 3}, {2, 2, 3}, {2, 1, 3}};
-constexpr int kWideDj[6][3] = {{1, 0, 1}, {2, 0, 2}, {1, 2, 1}, {3, 0, 3}, {2, 3, 2}, {2, 3, 1}};
+constexpr int kPatDi[6][3] = {{0, 1, 1}, {0, 2, 2}, {1, 1, 2}, {0, 3, 3}, {2, 2, 3}, {2, 1, 3}};
+constexpr int kPatDj[6][3] = {{1, 0, 1}, {2, 0, 2}, {1, 2, 1}, {3, 0, 3}, {2, 3, 2}, {2, 3, 1}};
 constexpr int rot_dy(int r, int di, int dj) { return r == 0 ? di : r == 1 ? dj : r == 2 ? -di : -dj; }   // sample_offset
 constexpr int rot_dx(int r, int di, int dj) { return r == 0 ? dj : r == 1 ? -di : r == 2 ? -dj : di; }
 

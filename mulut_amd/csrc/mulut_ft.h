@@ -1,0 +1,141 @@
+// mulut_ft.h -- what the fine-tuning kernels of every sampling interval share (mulut_ft.hip: interval 4, mulut_ft_interval.hip: 5 and 6).
+//
+// First part, pure arithmetic compiled by hipcc into both files and by g++ into tests/host_emul/emul_ft_interval.cpp (a CPU unit
+// test, not a product path): the order of the four keys of a pass, their sorted LSBs and the five weights (the reference's
+// differentiable module, MuLUT.InterpTorchBatch, sr/model.py:78-121, 191-282).  The MSB / row-index part of the set-up stays per
+// family: ft_pass_setup() of mulut_ft.hip also derives tube slots and does not clamp, ft_iv_pass<IV>() of mulut_ft_interval.h clamps.
+// Both files include it under `#pragma clang fp contract(off)` (the reference's float expressions are not contracted); g++ gets
+// -ffp-contract=off from the test.
+// Second part (hipcc only): the kernel argument struct with its argument checks, and the LDS float add and DPP row helpers of the
+// backward kernels.
+#ifndef MULUT_FT_H_
+#define MULUT_FT_H_
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "../../include/mulut.h"
+#else
+#include <math.h>
+#endif
+
+#include "mulut_core.h"
+
+namespace mulut {
+
+MULUT_HD int ft_bits(float f) { return __builtin_bit_cast(int, f); }
+MULUT_HD float ft_float(int i) { return __builtin_bit_cast(float, i); }
+MULUT_HD int ft_lt(int x, int y) { return (int)((unsigned)(x - y) >> 31); }      // [x < y] for 0 <= x, y < 2^31
+
+// The reference orders the four keys by a 24-branch cascade of strict '>' comparisons (sr/model.py:191-282).  Inference's simplex4()
+// may order TIES differently (there only zero-weight vertices move); gradients depend on the order, so the backward uses this one.
+// For EVERY tie pattern that cascade equals the stable order "f descending, on equal f the key with the higher index first"
+// (exhaustive check over all orderings and ties, against this very function compiled by g++: tests/test_ft_order_cpu.py; the proof
+// does not depend on q), so the rank of key i is the number of keys that come before it:
+//   rank_i = #{ j > i : f_j >= f_i } + #{ j < i : f_j > f_i }.
+// f lies in [0, q): the int32 patterns of non-negative floats order like the floats, and [f_j < f_i] is the sign bit of their
+// difference -- the ranks are adds and shifts, no compare + select (a v_cndmask_b32 costs six full-rate instructions on this chip and
+// the cascade was ~20 of them per pass, the selects by rank another ~36).
+// Returns the keys by rank, two bits each: key of rank j in bits 2j, 2j + 1.
+MULUT_HD int ft_order_code(float fa, float fb, float fc, float fd) {
+    const int a = ft_bits(fa), b = ft_bits(fb), c = ft_bits(fc), d = ft_bits(fd);
+    const int s10 = ft_lt(b, a), s20 = ft_lt(c, a), s30 = ft_lt(d, a), s21 = ft_lt(c, b), s31 = ft_lt(d, b), s32 = ft_lt(d, c);
+    const int r1 = s10 + 2 - s21 - s31, r2 = s20 + s21 + 1 - s32, r3 = s30 + s31 + s32;      // (rank of key a: 3 - s10 - s20 - s30, contributes 0)
+    return (1 << (2 * r1)) | (2 << (2 * r2)) | (3 << (2 * r3));
+}
+
+// The LSBs by rank.  Only the VALUES are needed, and a min / max network sorts values whatever the ties (on the int32 patterns,
+// as the ranks: integer min / max need no NaN canonicalisation of their operands).
+MULUT_HD void ft_sort_lsb(const float (&f)[4], float (&fs)[4]) {
+    const int i0 = ft_bits(f[0]), i1 = ft_bits(f[1]), i2 = ft_bits(f[2]), i3 = ft_bits(f[3]);
+    const int a = imax(i0, i1), b = imin(i0, i1), c = imax(i2, i3), d = imin(i2, i3);
+    const int t1 = imin(a, c), t2 = imax(b, d);
+    fs[0] = ft_float(imax(a, c)); fs[1] = ft_float(imax(t1, t2)); fs[2] = ft_float(imin(t1, t2)); fs[3] = ft_float(imin(b, d));
+}
+// The five weights of a pass from its sorted LSBs
+MULUT_HD void ft_weights(float q, const float (&fs)[4], float (&wt)[5]) {
+    wt[0] = q - fs[0];
+    wt[1] = fs[0] - fs[1];
+    wt[2] = fs[1] - fs[2];
+    wt[3] = fs[2] - fs[3];
+    wt[4] = fs[3];
+}
+
+#if defined(__HIPCC__)
+// ---------------------------------------------------------------------------------------------------------------- hipcc only
+constexpr int kMaxFtModes = MULUT_MAX_MODES;
+
+struct FtArgs {
+    const float *w[kMaxFtModes];
+    float *gw[kMaxFtModes];
+    const float *x;     // [B][C][H][W], values 0..255
+    const float *gout;  // [B][C][H*u][W*u]
+    float *out;         // [B][C][H*u][W*u]
+    float *gx;          // [B][C][H][W]
+    uint16_t *inside;   // [B][C][H][W]: bit eo of a site = the stage's clamp lets gradient through at block position eo
+                        // (0 <= pred / avg + bias <= 255); the forward writes it, a backward that gets it skips the forward recomputation
+                        // (optional at interval 4)
+    int B, C, H, W, u, M, is_last;
+    int di[kMaxFtModes][3], dj[kMaxFtModes][3];
+};
+
+// float add into LDS as ds_add_f32: an atomicAdd on a pointer the compiler cannot prove to be LDS (here: one of two targets chosen
+// at run time) becomes flat_atomic_add_f32, which reaches the LDS through the texture path
+__device__ __forceinline__ void lds_add_f32(float *p, float v) {
+    // (as an instruction of its own: written as an atomic on an address_space(3) pointer it is still merged with the global
+    // atomic of the other branch into one flat atomic on a selected pointer.)  The compiler does not count this LDS operation:
+    // LDS returns in order, so its own waits can only get stricter, and lds_adds_done() drains before a barrier publishes the sums.
+    asm volatile("ds_add_f32 %0, %1" : : "v"((uint32_t)(uintptr_t)p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void lds_adds_done() { asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory"); }
+
+__device__ __forceinline__ float ft_sum16(float v) {      // sum over the 16 lanes of a DPP row; every lane gets it
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, true));      // row_ror:8
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xF, 0xF, true));      // row_ror:4
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xF, 0xF, true));      // row_ror:2
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xF, 0xF, true));      // row_ror:1
+    return v;
+}
+// lane K of every 16-lane row to all lanes of its row (v_mov_b32_dpp row_newbcast:K)
+template <int K> __device__ __forceinline__ int ft_bcast(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x150 + K, 0xF, 0xF, true); }
+template <int K> __device__ __forceinline__ float ft_bcast(float v) { return __int_as_float(ft_bcast<K>(__float_as_int(v))); }
+
+template <int U>
+__device__ __forceinline__ int eo_of_elem(int r, int e) {      // block position whose table element is e under rotation r (inverse of row_elem)
+    return r == 0 ? e : r == 1 ? U * (e % U) + (U - 1 - e / U) : r == 2 ? U * U - 1 - e : U * (U - 1 - e % U) + e / U;
+}
+
+// Argument checks of every fine-tuning entry point, decided before the device is touched; their order -- and so which MULUT_E* code a
+// bad call gets -- is part of the ABI (include/mulut.h).  need_mask: the entry point cannot do without `inside`; interval_ok: the
+// caller's own verdict on its interval argument (entry points without one pass true).  Args: FtArgs, or FtIvArgs of mulut_ft_interval.hip.
+template <class Args>
+static inline int ft_fill(Args &a, bool interval_ok, const float *const *weights, float *const *grad_wq, const char *modes, int is_last, int u,
+                   const float *x, const uint16_t *inside, bool need_mask, int B, int C, int H, int W) {
+    if (!weights || !modes || !x || (need_mask && !inside) || B <= 0 || C <= 0 || H <= 0 || W <= 0) return MULUT_EINVAL;
+    if (!interval_ok) return MULUT_EUNSUPPORTED;
+    const size_t M = strlen(modes);
+    if (M < 1 || M > (size_t)kMaxFtModes || u < 1 || u > 4) return MULUT_EUNSUPPORTED;
+    memset(&a, 0, sizeof(a));
+    for (size_t m = 0; m < M; ++m) {
+        int di[3], dj[3];
+        // the input-gradient tiles stage a 2-pixel halo: the 4 x 4 patterns e, h, o (reach 3) are not fine-tuned
+        if (!pattern_offsets(modes[m], di, dj) || pattern_reach(modes[m]) > 2) return MULUT_EMODE;
+        if (!weights[m] || (grad_wq && !grad_wq[m])) return MULUT_EINVAL;
+        a.w[m] = weights[m];
+        a.gw[m] = grad_wq ? grad_wq[m] : nullptr;
+        for (int k = 0; k < 3; ++k) {
+            a.di[m][k] = di[k];
+            a.dj[m][k] = dj[k];
+        }
+    }
+    a.x = x;
+    a.inside = const_cast<uint16_t *>(inside);
+    a.B = B; a.C = C; a.H = H; a.W = W; a.u = u; a.M = (int)M; a.is_last = is_last ? 1 : 0;
+    return MULUT_OK;
+}
+#endif  // __HIPCC__
+
+}  // namespace mulut
+#endif  // MULUT_FT_H_

@@ -20,32 +20,17 @@
 #include <cstring>
 #include <type_traits>
 
-#include "../../include/mulut.h"
-#include "mulut_core.h"
 #include "mulut_kernels.h"
 
 #pragma clang fp contract(off)
+
+#include "mulut_ft.h"
 
 #ifndef MULUT_FT_ABL
 #define MULUT_FT_ABL 0      // timing-only ablations (tools/ab_bench.py variants ftabl*): never in the product build
 #endif
 
 namespace mulut {
-
-constexpr int kMaxFtModes = MULUT_MAX_MODES;
-
-struct FtArgs {
-    const float *w[kMaxFtModes];
-    float *gw[kMaxFtModes];
-    const float *x;     // [B][C][H][W], values 0..255
-    const float *gout;  // [B][C][H*u][W*u]
-    float *out;         // [B][C][H*u][W*u]
-    float *gx;          // [B][C][H][W]
-    uint16_t *inside;   // optional [B][C][H][W]: bit eo of a site = the stage's clamp lets gradient through at block position eo
-                        // (0 <= pred / avg + bias <= 255); the forward writes it, a backward that gets it skips the forward recomputation
-    int B, C, H, W, u, M, is_last;
-    int di[kMaxFtModes][3], dj[kMaxFtModes][3];
-};
 
 // table row of every tube-band slot (-1: the slot holds no row), built at compile time: the flush of a workgroup's band sums walks the
 // slots instead of re-deriving (A, B, C, D) -> slot for 16 x 125 candidates per mode
@@ -61,22 +46,6 @@ constexpr FtTubeRows ft_make_tube_rows() {
     return t;
 }
 __device__ const FtTubeRows kFtTubeRows = ft_make_tube_rows();
-
-// The reference orders the four keys by a 24-branch cascade of strict '>' comparisons (sr/model.py:191-282).  For EVERY tie pattern that
-// cascade equals the stable order "f descending, on equal f the key with the higher index first" (exhaustive check over all orderings
-// and ties: tests/test_ft_order_cpu.py), so the rank of key i is the number of keys that come before it:
-//   rank_i = #{ j > i : f_j >= f_i } + #{ j < i : f_j > f_i }.
-// f lies in [0, 16): the int32 patterns of non-negative floats order like the floats, and [f_j < f_i] is the sign bit of their
-// difference -- the ranks are adds and shifts, no compare + select (a v_cndmask_b32 costs six full-rate instructions on this chip and
-// the cascade was ~20 of them per pass, the selects by rank below another ~36).
-// Returns the keys by rank, two bits each: key of rank j in bits 2j, 2j + 1.
-__device__ __forceinline__ int ft_order_code(float fa, float fb, float fc, float fd) {
-    const int a = __float_as_int(fa), b = __float_as_int(fb), c = __float_as_int(fc), d = __float_as_int(fd);
-    auto lt = [](int x, int y) { return (int)((unsigned)(x - y) >> 31); };      // [x < y] for 0 <= x, y < 2^31
-    const int s10 = lt(b, a), s20 = lt(c, a), s30 = lt(d, a), s21 = lt(c, b), s31 = lt(d, b), s32 = lt(d, c);
-    const int r1 = s10 + 2 - s21 - s31, r2 = s20 + s21 + 1 - s32, r3 = s30 + s31 + s32;      // (rank of key a: 3 - s10 - s20 - s30, contributes 0)
-    return (1 << (2 * r1)) | (2 << (2 * r2)) | (3 << (2 * r3));
-}
 
 struct FtPass {
     int idx[5];      // table rows of the five vertices
@@ -106,17 +75,10 @@ __device__ __forceinline__ void ft_pass_setup(const float *plane, int H, int W, 
         h[k] = (int)hf;
         f[k] = v[k] - (float)kQ * hf;                    // img % q
     }
-    const int ord = ft_order_code(f[0], f[1], f[2], f[3]);
+    const int ord = ft_order_code(f[0], f[1], f[2], f[3]);      // (mulut_ft.h, as the LSB sort and the weights)
     p.ord = ord;
-    // the LSBs by rank: only the VALUES are needed, and a min / max network sorts values whatever the ties
-    // (on the int32 patterns, as the ranks: integer min / max need no NaN canonicalisation of their operands)
     float fs[4];
-    {
-        const int i0 = __float_as_int(f[0]), i1 = __float_as_int(f[1]), i2 = __float_as_int(f[2]), i3 = __float_as_int(f[3]);
-        const int a = imax(i0, i1), b = imin(i0, i1), c = imax(i2, i3), d = imin(i2, i3);
-        const int t1 = imin(a, c), t2 = imax(b, d);
-        fs[0] = __int_as_float(imax(a, c)); fs[1] = __int_as_float(imax(t1, t2)); fs[2] = __int_as_float(imin(t1, t2)); fs[3] = __int_as_float(imin(b, d));
-    }
+    ft_sort_lsb(f, fs);
     // strides of the key of rank j: a shift of a packed constant by that key's id
     constexpr unsigned long long kRowStrides = (unsigned long long)kStrideA | ((unsigned long long)kStrideB << 16) | ((unsigned long long)kStrideC << 32) |
                                                ((unsigned long long)kStrideD << 48);
@@ -143,11 +105,7 @@ __device__ __forceinline__ void ft_pass_setup(const float *plane, int H, int W, 
     p.idx[2] = p.idx[1] + ss[1];
     p.idx[3] = p.idx[2] + ss[2];
     p.idx[4] = p.idx[3] + ss[3];
-    p.wt[0] = (float)kQ - fs[0];
-    p.wt[1] = fs[0] - fs[1];
-    p.wt[2] = fs[1] - fs[2];
-    p.wt[3] = fs[2] - fs[3];
-    p.wt[4] = fs[3];
+    ft_weights((float)kQ, fs, p.wt);
 }
 
 // pred after all passes of the stage for one site (the order of additions and roundings is the reference's)
@@ -228,27 +186,6 @@ __device__ __forceinline__ void ft_site_g(const FtArgs &a, const float *plane, l
     }
 }
 
-// float add into LDS as ds_add_f32: an atomicAdd on a pointer the compiler cannot prove to be LDS (here: one of two targets chosen
-// at run time) becomes flat_atomic_add_f32, which reaches the LDS through the texture path
-__device__ __forceinline__ void lds_add_f32(float *p, float v) {
-    // (as an instruction of its own: written as an atomic on an address_space(3) pointer it is still merged with the global
-    // atomic of the other branch into one flat atomic on a selected pointer.)  The compiler does not count this LDS operation:
-    // LDS returns in order, so its own waits can only get stricter, and lds_adds_done() drains before a barrier publishes the sums.
-    asm volatile("ds_add_f32 %0, %1" : : "v"((uint32_t)(uintptr_t)p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void lds_adds_done() { asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory"); }
-
-__device__ __forceinline__ float ft_sum16(float v) {      // sum over the 16 lanes of a DPP row; every lane gets it
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, true));      // row_ror:8
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xF, 0xF, true));      // row_ror:4
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xF, 0xF, true));      // row_ror:2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xF, 0xF, true));      // row_ror:1
-    return v;
-}
-// lane K of every 16-lane row to all lanes of its row (v_mov_b32_dpp row_newbcast:K)
-template <int K> __device__ __forceinline__ int ft_bcast(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x150 + K, 0xF, 0xF, true); }
-template <int K> __device__ __forceinline__ float ft_bcast(float v) { return __int_as_float(ft_bcast<K>(__float_as_int(v))); }
-
 // Backward of one stage.  A workgroup owns 256 consecutive sites.  Per site (one thread): recompute the stage forward for
 // the clamp mask, g = dL/d pred; then per pass the five rows' dot products with g give the input gradient (one atomic
 // per rank into the source pixel: adjacent sites hit adjacent floats, i.e. well-shaped 256-byte atomic instructions).
@@ -259,11 +196,6 @@ template <int K> __device__ __forceinline__ float ft_bcast(float v) { return __i
 //           per-workgroup LDS copy of the tube band with ds_add_f32 and flushed once per workgroup as contiguous
 //           atomics; items outside it go to global memory directly.
 constexpr int kFtGxTile = 1024;        // floats of a wave's input-gradient tile (ft_stage_bwd)
-template <int U>
-__device__ __forceinline__ int eo_of_elem(int r, int e) {      // block position whose table element is e under rotation r (inverse of row_elem)
-    return r == 0 ? e : r == 1 ? U * (e % U) + (U - 1 - e / U) : r == 2 ? U * U - 1 - e : U * (U - 1 - e % U) + e / U;
-}
-
 template <int U>
 __global__ void __launch_bounds__(256) ft_stage_bwd(FtArgs a) {
     constexpr int EL = U * U, EPL = EL <= 1 ? 1 : EL <= 4 ? 4 : 16, NT = 256;
@@ -651,29 +583,6 @@ static int ft_quantize(int device, const float *const *w, float *const *o, int M
     return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }
 
-static int ft_fill(FtArgs &a, const float *const *weights, float *const *grad_wq, const char *modes, int is_last, int u,
-                   const float *x, int B, int C, int H, int W) {
-    if (!weights || !modes || !x || B <= 0 || C <= 0 || H <= 0 || W <= 0) return MULUT_EINVAL;
-    const size_t M = strlen(modes);
-    if (M < 1 || M > (size_t)kMaxFtModes || u < 1 || u > 4) return MULUT_EUNSUPPORTED;
-    memset(&a, 0, sizeof(a));
-    for (size_t m = 0; m < M; ++m) {
-        int di[3], dj[3];
-        // the input-gradient tiles stage a 2-pixel halo: the 4 x 4 patterns e, h, o (reach 3) are not fine-tuned
-        if (!pattern_offsets(modes[m], di, dj) || pattern_reach(modes[m]) > 2) return MULUT_EMODE;
-        if (!weights[m] || (grad_wq && !grad_wq[m])) return MULUT_EINVAL;
-        a.w[m] = weights[m];
-        a.gw[m] = grad_wq ? grad_wq[m] : nullptr;
-        for (int k = 0; k < 3; ++k) {
-            a.di[m][k] = di[k];
-            a.dj[m][k] = dj[k];
-        }
-    }
-    a.x = x;
-    a.B = B; a.C = C; a.H = H; a.W = W; a.u = u; a.M = (int)M; a.is_last = is_last ? 1 : 0;
-    return MULUT_OK;
-}
-
 extern "C" {
 
 int mulut_ft_quantize(int device, const float *const *weights, float *const *weights_q, int M, long long n, void *stream) {
@@ -687,11 +596,10 @@ int mulut_ft_quantize_backward(int device, const float *const *weights, float *c
 static int ft_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                       int B, int C, int H, int W, float *out, uint16_t *inside, void *stream) {
     FtArgs a;
-    int rc = ft_fill(a, weights_q, nullptr, modes, is_last, u, x, B, C, H, W);
+    int rc = ft_fill(a, true, weights_q, nullptr, modes, is_last, u, x, inside, false, B, C, H, W);
     if (rc) return rc;
     if (!out) return MULUT_EINVAL;
     a.out = out;
-    a.inside = inside;
     if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
     hipError_t e = u == 1 ? launch_ft<1>(a, false, (hipStream_t)stream) : u == 2 ? launch_ft<2>(a, false, (hipStream_t)stream)
                  : u == 3 ? launch_ft<3>(a, false, (hipStream_t)stream) : launch_ft<4>(a, false, (hipStream_t)stream);
@@ -713,12 +621,11 @@ static int ft_backward(int device, const float *const *weights_q, const char *mo
                        const float *grad_out, const uint16_t *inside, int B, int C, int H, int W, float *const *grad_wq, float *grad_x,
                        void *stream) {
     FtArgs a;
-    int rc = ft_fill(a, weights_q, grad_wq, modes, is_last, u, x, B, C, H, W);
+    int rc = ft_fill(a, true, weights_q, grad_wq, modes, is_last, u, x, inside, false, B, C, H, W);
     if (rc) return rc;
     if (!grad_out || !grad_wq || !grad_x) return MULUT_EINVAL;
     a.gout = grad_out;
     a.gx = grad_x;
-    a.inside = const_cast<uint16_t *>(inside);
     if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
     hipError_t e = u == 1 ? launch_ft<1>(a, true, (hipStream_t)stream) : u == 2 ? launch_ft<2>(a, true, (hipStream_t)stream)
                  : u == 3 ? launch_ft<3>(a, true, (hipStream_t)stream) : launch_ft<4>(a, true, (hipStream_t)stream);

@@ -32,8 +32,6 @@
 
 #include <cstring>
 
-#include "../../include/mulut.h"
-#include "mulut_core.h"
 #include "mulut_kernels.h"
 
 #pragma clang fp contract(off)
@@ -42,23 +40,23 @@
 
 namespace mulut {
 
-constexpr int kFtIvMaxModes = MULUT_MAX_MODES;
 // The one LDS rule of this file: the stage's float tables (forward: all M of them) or one mode's gradient image (backward) live
 // in LDS when they take at most this many bytes; the rest of a CU's 160 KB is for what the kernel keeps beside them (at most
 // 24 KB + the u = 4 backward's 77 KB, which only ever meets the 40 KB image of interval 6).
 constexpr int kFtIvLdsBudget = 120 * 1024;
 
+// FtArgs (mulut_ft.h) with tiles_per_wg, and where it is.  Not FtArgs with the field appended: behind di / dj the backward kernels fetch it
+// with a scalar load of its own (next to is_last the two come as one), and in the middle of FtArgs it would move the argument
+// offsets of the interval-4 kernels.  `inside` is mandatory here.
 struct FtIvArgs {
-    const float *w[kFtIvMaxModes];
-    float *gw[kFtIvMaxModes];
-    const float *x;       // [B][C][H][W], values 0..255
-    const float *gout;    // [B][C][H*u][W*u]
-    float *out;           // [B][C][H*u][W*u]
-    float *gx;            // [B][C][H][W]
-    uint16_t *inside;     // [B][C][H][W]: bit eo of a site = the stage's clamp lets gradient through at block position eo
+    const float *w[kMaxFtModes];
+    float *gw[kMaxFtModes];
+    const float *x, *gout;
+    float *out, *gx;
+    uint16_t *inside;
     int B, C, H, W, u, M, is_last;
     int tiles_per_wg;     // backward: consecutive tiles of sites a workgroup walks
-    int di[kFtIvMaxModes][3], dj[kFtIvMaxModes][3];
+    int di[kMaxFtModes][3], dj[kMaxFtModes][3];
 };
 
 template <int IV>
@@ -134,26 +132,9 @@ __global__ void __launch_bounds__(kFtIvFwdNT) ft_interval_stage_fwd(FtIvArgs a) 
 }
 
 // --------------------------------------------------------------------------------------------------------------- backward
-// (the LDS float add, the DPP row sum and the row broadcast of mulut_ft.hip, which keeps its own copies: that file is not touched)
-__device__ __forceinline__ void ftiv_lds_add_f32(float *p, float v) {
-    asm volatile("ds_add_f32 %0, %1" : : "v"((uint32_t)(uintptr_t)p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void ftiv_lds_adds_done() { asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory"); }
-__device__ __forceinline__ float ftiv_sum16(float v) {      // sum over the 16 lanes of a DPP row; every lane gets it
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, true));      // row_ror:8
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xF, 0xF, true));      // row_ror:4
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xF, 0xF, true));      // row_ror:2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xF, 0xF, true));      // row_ror:1
-    return v;
-}
-template <int K> __device__ __forceinline__ int ftiv_bcast(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x150 + K, 0xF, 0xF, true); }
-template <int K> __device__ __forceinline__ float ftiv_bcast(float v) { return __int_as_float(ftiv_bcast<K>(__float_as_int(v))); }
-template <int U>
-__device__ __forceinline__ int ftiv_eo_of_elem(int r, int e) {      // block position whose table element is e under rotation r (inverse of row_elem)
-    return r == 0 ? e : r == 1 ? U * (e % U) + (U - 1 - e / U) : r == 2 ? U * U - 1 - e : U * (U - 1 - e % U) + e / U;
-}
-
-// g = dL/d pred of one site: the clamp's mask saved by the forward, then d(pred / avg)
+// (the LDS float add and the DPP row helpers: mulut_ft.h)
+// g = dL/d pred of one site: the clamp's mask saved by the forward, then d(pred / avg).  (The mask branch of mulut_ft.hip's
+// ft_site_g, which stays in place there: called as a helper it moved the code of three timed backward kernels.)
 template <int U, class F>
 __device__ __forceinline__ void ftiv_site_g(const FtIvArgs &a, long long bc, int y, int x, bool valid, F &&put) {
     const float avg = a.is_last ? (float)a.M : (float)(4 * a.M);
@@ -221,7 +202,7 @@ __global__ void __launch_bounds__(kFtIvNT) ft_interval_stage_bwd(FtIvArgs a) {
                 ftiv_pass_setup<IV>(plane, a.H, a.W, y, x, r, di, dj, p);
                 float gr[EL];      // g by TABLE element under this rotation
 #pragma unroll
-                for (int e = 0; e < EL; ++e) gr[e] = s_g[threadIdx.x][ftiv_eo_of_elem<U>(r, e)];
+                for (int e = 0; e < EL; ++e) gr[e] = s_g[threadIdx.x][eo_of_elem<U>(r, e)];
                 float dsum[5];     // sum_e g * p_j[e]
 #pragma unroll
                 for (int j = 0; j < 5; ++j) {
@@ -235,16 +216,16 @@ __global__ void __launch_bounds__(kFtIvNT) ft_interval_stage_bwd(FtIvArgs a) {
                     // element l) and added once, row-wide; the others add on their own.  (All 256 threads are here: the broadcast and
                     // the row sums read every lane.)
                     const float wq = valid ? p.wt[j] / (float)G::q : 0.0f;
-                    const int lead = ftiv_bcast<0>(p.idx[j]);
+                    const int lead = ft_bcast<0>(p.idx[j]);
                     const bool with_lead = p.idx[j] == lead;
                     float mine = 0.0f;
 #pragma unroll
                     for (int e = 0; e < EL; ++e) {
-                        const float sum = ftiv_sum16(with_lead ? wq * gr[e] : 0.0f);
+                        const float sum = ft_sum16(with_lead ? wq * gr[e] : 0.0f);
                         if (EL == 1 || l16 == e) mine = sum;
                     }
                     if (l16 < EL && mine != 0.0f) {
-                        if constexpr (RES) ftiv_lds_add_f32(&s_img[lead * EL + l16], mine);
+                        if constexpr (RES) lds_add_f32(&s_img[lead * EL + l16], mine);
                         else atomicAdd(&gtab[lead * EL + l16], mine);
                     }
                     if (!with_lead) {
@@ -252,7 +233,7 @@ __global__ void __launch_bounds__(kFtIvNT) ft_interval_stage_bwd(FtIvArgs a) {
                         for (int e = 0; e < EL; ++e) {
                             const float v = wq * gr[e];
                             if (v != 0.0f) {
-                                if constexpr (RES) ftiv_lds_add_f32(&s_img[p.idx[j] * EL + e], v);
+                                if constexpr (RES) lds_add_f32(&s_img[p.idx[j] * EL + e], v);
                                 else atomicAdd(&gtab[p.idx[j] * EL + e], v);
                             }
                         }
@@ -294,7 +275,7 @@ __global__ void __launch_bounds__(kFtIvNT) ft_interval_stage_bwd(FtIvArgs a) {
         }
         if constexpr (RES) {
             // the workgroup's image into the table gradient: contiguous floats, a wave adds 256 bytes at a time
-            ftiv_lds_adds_done();
+            lds_adds_done();
             __syncthreads();
             for (int i = threadIdx.x; i < IMG; i += NT) {
                 const float v = s_img[i];
@@ -354,10 +335,10 @@ __global__ void __launch_bounds__(kFtIvB4Sites) ft_interval_stage_bwd4(FtIvArgs 
     int *tags = s_tag + grp * 16;            // (row << 4 | corner) held by the entry of that corner, -1: none
     // an entry's sum leaves the cache: into the image; without one into the band, or, a row outside it, to memory as one 64-byte segment
     auto retire = [&](float *gtab, int tag, float v) {
-        if constexpr (RES) ftiv_lds_add_f32(&s_img[(tag >> 4) * EL + e], v);
+        if constexpr (RES) lds_add_f32(&s_img[(tag >> 4) * EL + e], v);
         else {
             const int slot = ftiv_band_slot<IV>(tag >> 4);      // (uniform in the group)
-            if (slot >= 0) ftiv_lds_add_f32(&s_img[slot * EL + e], v);
+            if (slot >= 0) lds_add_f32(&s_img[slot * EL + e], v);
             else if (v != 0.0f) atomicAdd(&gtab[(tag >> 4) * EL + e], v);
         }
     };
@@ -399,11 +380,11 @@ __global__ void __launch_bounds__(kFtIvB4Sites) ft_interval_stage_bwd4(FtIvArgs 
                     }
                     ord = p.ord;
                 }
-                const int eo = ftiv_eo_of_elem<U>(r, e);
+                const int eo = eo_of_elem<U>(r, e);
                 float rowv[16][5];
                 static_for<0, 16>([&](auto K) {
 #pragma unroll
-                    for (int j = 0; j < 5; ++j) rowv[K][j] = tab[(imax(ftiv_bcast<K>(tagv[j]), 0) >> 4) * EL + e];
+                    for (int j = 0; j < 5; ++j) rowv[K][j] = tab[(imax(ft_bcast<K>(tagv[j]), 0) >> 4) * EL + e];
                 });
                 float dm[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // g . row of this lane's site, per vertex
                 static_for<0, 16>([&](auto K) {
@@ -413,9 +394,9 @@ __global__ void __launch_bounds__(kFtIvB4Sites) ft_interval_stage_bwd4(FtIvArgs 
                     float v[5], d[5];
 #pragma unroll
                     for (int j = 0; j < 5; ++j) {
-                        tg[j] = ftiv_bcast<K>(tagv[j]);
-                        v[j] = ftiv_bcast<K>(wq[j]) * gv;
-                        d[j] = ftiv_sum16(gv * rowv[K][j]);
+                        tg[j] = ft_bcast<K>(tagv[j]);
+                        v[j] = ft_bcast<K>(wq[j]) * gv;
+                        d[j] = ft_sum16(gv * rowv[K][j]);
                     }
                     if (e == K) {
 #pragma unroll
@@ -476,7 +457,7 @@ __global__ void __launch_bounds__(kFtIvB4Sites) ft_interval_stage_bwd4(FtIvArgs 
             const int tg = tags[c];
             if (tg >= 0) retire(gtab, tg, cache[c * 16 + e]);
         }
-        ftiv_lds_adds_done();
+        lds_adds_done();
         __syncthreads();
         for (int i = threadIdx.x; i < IMG; i += NT) {      // (i % 16 == e: NT is a multiple of 16)
             const float v = s_img[i];
@@ -571,40 +552,13 @@ static hipError_t launch_ftiv(const FtIvArgs &a, bool backward, int num_cus, hip
 
 using namespace mulut;
 
-// argument checks of both entry points, in the order of ft_fill (mulut_ft.hip): everything here is decided before the device is touched
-static int ftiv_fill(FtIvArgs &a, int interval, const float *const *weights, float *const *grad_wq, const char *modes, int is_last, int u,
-                     const float *x, const uint16_t *inside, int B, int C, int H, int W) {
-    if (!weights || !modes || !x || !inside || B <= 0 || C <= 0 || H <= 0 || W <= 0) return MULUT_EINVAL;
-    if (interval != 5 && interval != 6) return MULUT_EUNSUPPORTED;      // (interval 4: mulut_ft_stage_*)
-    const size_t M = strlen(modes);
-    if (M < 1 || M > (size_t)kFtIvMaxModes || u < 1 || u > 4) return MULUT_EUNSUPPORTED;
-    memset(&a, 0, sizeof(a));
-    for (size_t m = 0; m < M; ++m) {
-        int di[3], dj[3];
-        // the input-gradient tiles stage a 2-pixel halo: the 4 x 4 patterns e, h, o (reach 3) are not fine-tuned
-        if (!pattern_offsets(modes[m], di, dj) || pattern_reach(modes[m]) > 2) return MULUT_EMODE;
-        if (!weights[m] || (grad_wq && !grad_wq[m])) return MULUT_EINVAL;
-        a.w[m] = weights[m];
-        a.gw[m] = grad_wq ? grad_wq[m] : nullptr;
-        for (int k = 0; k < 3; ++k) {
-            a.di[m][k] = di[k];
-            a.dj[m][k] = dj[k];
-        }
-    }
-    a.x = x;
-    a.inside = const_cast<uint16_t *>(inside);
-    a.B = B; a.C = C; a.H = H; a.W = W; a.u = u; a.M = (int)M; a.is_last = is_last ? 1 : 0;
-    a.tiles_per_wg = 1;
-    return MULUT_OK;
-}
-
 extern "C" {
 
 // MuLUT.forward's stage at interval 5 / 6 (sr/model.py:289-312 with :42-44, 78-80)
 int mulut_ft_interval_stage_forward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
                                     const float *x, int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
     FtIvArgs a;
-    const int rc = ftiv_fill(a, interval, weights_q, nullptr, modes, is_last, u, x, inside, B, C, H, W);
+    const int rc = ft_fill(a, interval == 5 || interval == 6, weights_q, nullptr, modes, is_last, u, x, inside, true, B, C, H, W);      // (interval 4: mulut_ft_stage_*)
     if (rc) return rc;
     if (!out) return MULUT_EINVAL;
     a.out = out;
@@ -620,7 +574,7 @@ int mulut_ft_interval_stage_backward(int device, int interval, const float *cons
                                      float *const *grad_wq, float *grad_x, void *stream) {
     if (!grad_wq) return MULUT_EINVAL;
     FtIvArgs a;
-    const int rc = ftiv_fill(a, interval, weights_q, grad_wq, modes, is_last, u, x, inside, B, C, H, W);
+    const int rc = ft_fill(a, interval == 5 || interval == 6, weights_q, grad_wq, modes, is_last, u, x, inside, true, B, C, H, W);
     if (rc) return rc;
     if (!grad_out || !grad_x) return MULUT_EINVAL;
     a.gout = grad_out;

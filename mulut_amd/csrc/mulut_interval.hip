@@ -7,8 +7,8 @@
 //                                      (M * iv_table_bytes <= kIvLdsBudget) are staged into LDS once per persistent workgroup
 //                                      next to the tile; LDS = false: the five rows of a pass are gathered from the tables in
 //                                      global memory (26-105 KB per mode: L2-resident), one vector load per row
-//   pass_interval_kernel<IV>           mulut_pass: q * out as int32, one thread per site
 // One template instance of the pass body per pattern, chosen by the mode letter (scalar switch), as in mulut_wide.hip.
+// mulut_pass at these intervals is pass_kernel<IV> of mulut_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include "mulut_dev.h"
@@ -16,11 +16,7 @@
 
 namespace mulut {
 
-constexpr int kIvHalo = 3;      // the largest pattern_reach()
-constexpr int KI_TW = 64, KI_TH = 64, KI_NT = 1024;
-constexpr int KI_PW = KI_TW + 2 * kIvHalo + 2, KI_PH = KI_TH + 2 * kIvHalo;      // 72 (rows padded to whole dwords) x 70
-constexpr int kIvImgBytes = 3 * KI_PH * KI_PW;                                    // 15,120 for C = 3
-static_assert(KI_TW * KI_TH == 4 * KI_NT, "four adjacent pixels per thread");
+constexpr int kIvImgBytes = 3 * K3_PH * K3_PW;      // the tile of mulut_dev.h (K3_*: 64 x 64, 3-px halo), 15,120 for C = 3
 static_assert(kIvLdsBudget + kIvImgBytes <= 160 * 1024, "tables and tile fit one CU's LDS");
 
 // one table row of U*U int8 values (U > 1): dwords of iv_row_bytes(U), from LDS or global memory
@@ -44,11 +40,11 @@ __device__ __forceinline__ int iv_elem(const uint32_t (&row)[RW]) {
 // pass (pattern PAT, rotation R) of the site whose anchor sits at ctr in the LDS tile: acc[block position] += q * pred
 template <int IV, int U, int PAT, int R>
 __device__ __forceinline__ void iv_pass(const uint8_t *tab, const uint8_t *ctr, int (&acc)[U * U]) {
-    constexpr int yb = rot_dy(R, kWideDi[PAT][0], kWideDj[PAT][0]), xb = rot_dx(R, kWideDi[PAT][0], kWideDj[PAT][0]);
-    constexpr int yc = rot_dy(R, kWideDi[PAT][1], kWideDj[PAT][1]), xc = rot_dx(R, kWideDi[PAT][1], kWideDj[PAT][1]);
-    constexpr int yd = rot_dy(R, kWideDi[PAT][2], kWideDj[PAT][2]), xd = rot_dx(R, kWideDi[PAT][2], kWideDj[PAT][2]);
+    constexpr int yb = rot_dy(R, kPatDi[PAT][0], kPatDj[PAT][0]), xb = rot_dx(R, kPatDi[PAT][0], kPatDj[PAT][0]);
+    constexpr int yc = rot_dy(R, kPatDi[PAT][1], kPatDj[PAT][1]), xc = rot_dx(R, kPatDi[PAT][1], kPatDj[PAT][1]);
+    constexpr int yd = rot_dy(R, kPatDi[PAT][2], kPatDj[PAT][2]), xd = rot_dx(R, kPatDi[PAT][2], kPatDj[PAT][2]);
     int idx[5], w[5];
-    simplex4_iv<IV>(ctr[0], ctr[yb * KI_PW + xb], ctr[yc * KI_PW + xc], ctr[yd * KI_PW + xd], idx, w);
+    simplex4_iv<IV>(ctr[0], ctr[yb * K3_PW + xb], ctr[yc * K3_PW + xc], ctr[yd * K3_PW + xd], idx, w);
     if constexpr (U == 1) {
 #pragma unroll
         for (int j = 0; j < 5; ++j) acc[0] += w[j] * (int)(int8_t)tab[idx[j]];
@@ -79,8 +75,8 @@ __device__ __forceinline__ void iv_mode(const uint8_t *tab, const uint8_t *ctr, 
 }
 
 template <int IV, int U, bool LDS>
-__global__ void __launch_bounds__(KI_NT) stage_interval_kernel(StageArgs a, IvArgs v) {
-    constexpr int TW = KI_TW, TH = KI_TH, NT = KI_NT, PW = KI_PW, PH = KI_PH, HALO = kIvHalo;
+__global__ void __launch_bounds__(K3_NT) stage_interval_kernel(StageArgs a, IvArgs v) {
+    constexpr int TW = K3_TW, TH = K3_TH, NT = K3_NT, PW = K3_PW, PH = K3_PH, HALO = kHalo3;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *s_img = smem + (LDS ? a.M * v.table_bytes : 0);
     if constexpr (LDS) {      // every table of the stage, once per workgroup (the first barrier of the tile loop publishes them)
@@ -163,44 +159,9 @@ __global__ void __launch_bounds__(KI_NT) stage_interval_kernel(StageArgs a, IvAr
     }
 }
 
-template <int IV>
-__global__ void __launch_bounds__(256) pass_interval_kernel(PassArgs a) {
-    const long long nsite = (long long)a.C * a.H * a.W;
-    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nsite) return;
-    const int x = (int)(s % a.W);
-    const int y = (int)((s / a.W) % a.H);
-    const int c = (int)(s / ((long long)a.W * a.H));
-    const uint8_t *pl = a.in + (long long)c * a.H * a.W;
-    int v[4];
-    v[0] = pl[(long long)y * a.W + x];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        int dy, dx;
-        sample_offset(a.r, a.di[k], a.dj[k], dy, dx);
-        const int yy = imin(imax(y + dy, 0), a.H - 1);
-        const int xx = imin(imax(x + dx, 0), a.W - 1);
-        v[k + 1] = pl[(long long)yy * a.W + xx];
-    }
-    int idx[5], w[5];
-    simplex4_iv<IV>(v[0], v[1], v[2], v[3], idx, w);
-    const int u = a.u, rb = iv_row_bytes(u);
-    const int Wo = a.W * u;
-    const int8_t *lut = (const int8_t *)a.lut;
-    int32_t *po = a.out + (long long)c * a.H * u * Wo;
-    for (int sy = 0; sy < u; ++sy)
-        for (int sx = 0; sx < u; ++sx) {
-            const int e = row_elem(a.r, sy, sx, u);
-            int acc = 0;
-#pragma unroll
-            for (int j = 0; j < 5; ++j) acc += w[j] * (int)lut[(long long)idx[j] * rb + e];
-            po[(long long)(y * u + sy) * Wo + (x * u + sx)] = acc;
-        }
-}
-
 void stage_interval_tile(int &tw, int &th) {
-    tw = KI_TW;
-    th = KI_TH;
+    tw = K3_TW;
+    th = K3_TH;
 }
 
 const char *stage_interval_name(int interval, int u, bool lds) {
@@ -230,7 +191,7 @@ static hipError_t launch_interval_t(const StageArgs &a, const IvArgs &v, int num
         const long long per_cu = tables + kIvImgBytes <= 80 * 1024 ? 2 : 1;
         nb = nt < per_cu * num_cus ? nt : per_cu * num_cus;
     }
-    hipLaunchKernelGGL((stage_interval_kernel<IV, U, LDS>), dim3((unsigned)nb), dim3(KI_NT), tables + (size_t)a.C * KI_PH * KI_PW, st, a, v);
+    hipLaunchKernelGGL((stage_interval_kernel<IV, U, LDS>), dim3((unsigned)nb), dim3(K3_NT), tables + (size_t)a.C * K3_PH * K3_PW, st, a, v);
     return hipGetLastError();
 }
 
@@ -250,22 +211,12 @@ static hipError_t launch_interval_iv(const StageArgs &a, const IvArgs &v, int u,
 }
 
 hipError_t launch_stage_interval(const StageArgs &a, const IvArgs &v, int interval, int u, bool lds, int num_cus, hipStream_t st) {
-    if (a.C < 1 || a.C > 3 || a.M < 1 || a.M > kMaxModes || v.reach < 2 || v.reach > kIvHalo || num_cus < 1) return hipErrorInvalidValue;
+    if (a.C < 1 || a.C > 3 || a.M < 1 || a.M > kMaxModes || v.reach < 2 || v.reach > kHalo3 || num_cus < 1) return hipErrorInvalidValue;
     for (int m = 0; m < a.M; ++m)
         if (v.pat[m] < 0 || v.pat[m] > 5) return hipErrorInvalidValue;
     if (interval == 5) return launch_interval_iv<5>(a, v, u, lds, num_cus, st);
     if (interval == 6) return launch_interval_iv<6>(a, v, u, lds, num_cus, st);
     return hipErrorInvalidValue;
-}
-
-hipError_t launch_pass_interval(const PassArgs &a, int interval, hipStream_t st) {
-    const long long nsite = (long long)a.C * a.H * a.W;
-    const long long nb = (nsite + 255) / 256;
-    if (nb <= 0 || nb > 0x7fffffffLL || a.u < 1 || a.u > 4) return hipErrorInvalidValue;
-    if (interval == 5) hipLaunchKernelGGL(pass_interval_kernel<5>, dim3((unsigned)nb), dim3(256), 0, st, a);
-    else if (interval == 6) hipLaunchKernelGGL(pass_interval_kernel<6>, dim3((unsigned)nb), dim3(256), 0, st, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
 }
 
 }  // namespace mulut

@@ -106,7 +106,8 @@ struct DetailArgs {
 // and first used concurrently).  Not a capturable operation: the first launch of a kernel must happen outside hipGraph capture.
 hipError_t raise_lds_limit(const void *kernel, int bytes);
 
-hipError_t launch_pass(const PassArgs &a, hipStream_t st);
+// mulut_pass at the context's sampling interval (4: value + 128 rows of row_dwords(u) dwords; 5 / 6: int8 rows of iv_row_bytes(u))
+hipError_t launch_pass(const PassArgs &a, int interval, hipStream_t st);
 // non-final (or u == 1 final) stage: tables staged in LDS, one byte out per site; window kernel (four adjacent pixels per thread,
 // neighbours from registers)
 hipError_t launch_stage_u1(const StageArgs &a, hipStream_t st);
@@ -161,10 +162,10 @@ const char *stage_up_name(int u, int out_mode);
 // repeat of the six patterns, up to kMaxModes modes; no tube band, work list or tile mark is involved.
 //   launch_stage_wide1   1-byte rows (non-final stages, a final stage with u == 1): one mode's whole table in LDS, swapped per mode
 //   launch_stage_wide_up u in {2,3,4}: rows gathered from the full tables in global memory, generic output layout
-struct WideArgs {
-    int pat[kMaxModes];   // pattern of mode m: 0..5 = s, d, y, e, h, o (from the mode letter: the kernel takes one instance per pattern)
+struct PatternArgs {
+    int pat[kMaxModes];   // pattern of mode m: 0..5 = s, d, y, e, h, o (from the mode letter: the kernel takes one instance of its pass body per pattern)
 };
-hipError_t launch_stage_wide1(const StageArgs &a, const WideArgs &w, hipStream_t st);
+hipError_t launch_stage_wide1(const StageArgs &a, const PatternArgs &w, hipStream_t st);
 hipError_t launch_stage_wide_up(const StageArgs &a, int u, hipStream_t st);
 void stage_wide_tile(int u, int &tw, int &th);
 const char *stage_wide_name(int u);
@@ -173,17 +174,14 @@ const char *stage_wide_name(int u);
 // runs here, any mode list, any u; tables are plain int8 rows (mulut_interval.h iv_row_bytes), no tube band, slab or work list.
 //   launch_stage_interval  lds: every table of the stage staged into LDS once per persistent workgroup (kIvLdsBudget), else rows
 //                          gathered from the tables in global memory; 64 x 64 tiles with a 3-px halo, 32-bit sums
-//   launch_pass_interval   mulut_pass: q * out as int32
 constexpr int kIvLdsBudget = 96 * 1024;      // the stage's tables (M * iv_table_bytes) go to LDS when they fit this
-struct IvArgs {
-    int pat[kMaxModes];   // pattern of mode m: 0..5 = s, d, y, e, h, o (one instance of the pass body per pattern)
+struct IvArgs : PatternArgs {
     int reach;            // rows beyond [oy0, oy1) the caller's band holds (2, or 3 for a list with e, h or o)
     DivMagic dm;          // epilogue divisor / 2^(interval - 1): 2 M (final stage) or 8 M (mulut_interval.h iv_div_modes)
     int bias_num;         // 127 q 4 M (non-final stage) or 0
     int table_bytes;      // iv_table_bytes of one mode's table
 };
 hipError_t launch_stage_interval(const StageArgs &a, const IvArgs &v, int interval, int u, bool lds, int num_cus, hipStream_t st);
-hipError_t launch_pass_interval(const PassArgs &a, int interval, hipStream_t st);
 void stage_interval_tile(int &tw, int &th);
 const char *stage_interval_name(int interval, int u, bool lds);
 

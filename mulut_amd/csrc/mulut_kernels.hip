@@ -1,6 +1,6 @@
 // mulut_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels for MuLUT LUT inference.
 //
-//   pass_kernel        one (table, mode, rotation) pass, q*out as int32 -- the unit-parity twin of
+//   pass_kernel<IV>    one (table, mode, rotation) pass at the sampling interval IV, q*out as int32 -- the unit-parity twin of
 //                      FourSimplexInterpFaster (reference sr/4_test_lut.py:14-237)
 //   stage_u1_kernel    K1: a whole stage with 1-byte rows (non-final stages): all modes x 4
 //                      rotations + average/bias/round/clip fused; the active 83.5 KB table lives
@@ -18,12 +18,22 @@
 #include <utility>
 
 #include "mulut_dev.h"
+#include "mulut_interval.h"
 
 namespace mulut {
 
 // ------------------------------------------------------------------------------------------
 // pass kernel (parity unit; not performance critical)
 // ------------------------------------------------------------------------------------------
+// one table value: interval 4 keeps value + 128 in rows of row_dwords(u) dwords when u > 1 (int8 rows when u == 1), intervals 5 / 6
+// plain int8 rows of iv_row_bytes(u)
+template <int IV>
+__device__ __forceinline__ int pass_value(const void *lut, int idx, int u, int e) {
+    if (IV == kInterval && u > 1) return (int)((const uint8_t *)lut)[(long long)idx * (row_dwords(u) * 4) + e] - 128;
+    return (int)((const int8_t *)lut)[(long long)idx * iv_row_bytes(u) + e];
+}
+
+template <int IV>
 __global__ void __launch_bounds__(256) pass_kernel(PassArgs a) {
     const long long nsite = (long long)a.C * a.H * a.W;
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -43,28 +53,18 @@ __global__ void __launch_bounds__(256) pass_kernel(PassArgs a) {
         v[k + 1] = pl[(long long)yy * a.W + xx];
     }
     int idx[5], w[5];
-    simplex4(v[0], v[1], v[2], v[3], idx, w);
+    simplex4<IV>(v[0], v[1], v[2], v[3], idx, w);
     const int u = a.u;
     const int Wo = a.W * u;
     int32_t *po = a.out + (long long)c * a.H * u * Wo;
-    if (u == 1) {
-        const int8_t *lut = (const int8_t *)a.lut;
-        int acc = 0;
+    for (int sy = 0; sy < u; ++sy)
+        for (int sx = 0; sx < u; ++sx) {
+            const int e = row_elem(a.r, sy, sx, u);
+            int acc = 0;
 #pragma unroll
-        for (int j = 0; j < 5; ++j) acc += w[j] * (int)lut[idx[j]];
-        po[(long long)y * Wo + x] = acc;
-    } else {
-        const uint8_t *lut = (const uint8_t *)a.lut;
-        const int rb = row_dwords(u) * 4;
-        for (int sy = 0; sy < u; ++sy)
-            for (int sx = 0; sx < u; ++sx) {
-                const int e = row_elem(a.r, sy, sx, u);
-                int acc = 0;
-#pragma unroll
-                for (int j = 0; j < 5; ++j) acc += w[j] * ((int)lut[(long long)idx[j] * rb + e] - 128);
-                po[(long long)(y * u + sy) * Wo + (x * u + sx)] = acc;
-            }
-    }
+            for (int j = 0; j < 5; ++j) acc += w[j] * pass_value<IV>(a.lut, idx[j], u, e);
+            po[(long long)(y * u + sy) * Wo + (x * u + sx)] = acc;
+        }
 }
 
 hipError_t raise_lds_limit(const void *kernel, int bytes) {
@@ -80,10 +80,14 @@ hipError_t raise_lds_limit(const void *kernel, int bytes) {
     return e;
 }
 
-hipError_t launch_pass(const PassArgs &a, hipStream_t st) {
+hipError_t launch_pass(const PassArgs &a, int interval, hipStream_t st) {
     const long long nsite = (long long)a.C * a.H * a.W;
-    const int nb = (int)((nsite + 255) / 256);
-    hipLaunchKernelGGL(pass_kernel, dim3(nb), dim3(256), 0, st, a);
+    const long long nb = (nsite + 255) / 256;
+    if (nb <= 0 || nb > 0x7fffffffLL || a.u < 1 || a.u > 4) return hipErrorInvalidValue;
+    if (interval == 4) hipLaunchKernelGGL(pass_kernel<4>, dim3((unsigned)nb), dim3(256), 0, st, a);
+    else if (interval == 5) hipLaunchKernelGGL(pass_kernel<5>, dim3((unsigned)nb), dim3(256), 0, st, a);
+    else if (interval == 6) hipLaunchKernelGGL(pass_kernel<6>, dim3((unsigned)nb), dim3(256), 0, st, a);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

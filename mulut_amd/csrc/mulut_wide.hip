@@ -13,8 +13,6 @@
 
 namespace mulut {
 
-constexpr int kWideHalo = 3;      // pattern_reach() of e, h, o
-
 // ------------------------------------------------------------------------------------------
 // 1-byte rows.  Tile 64 x 64, 1024 threads, a thread owns four horizontally adjacent pixels of a row.  LDS:
 //   [ table: kU1TableBytes = 83,536 ][ image: C x 70 rows x 72 bytes (64 + 2 x 3 columns, padded to whole dwords) = 15,120 for C = 3 ]
@@ -25,11 +23,7 @@ constexpr int kWideHalo = 3;      // pattern_reach() of e, h, o
 // of its first pixel x); every key of every pixel and rotation is then one v_perm_b32 of two window registers.  Rotations r and r + 2
 // run in packed 16-bit halves (simplex4_full_pair1) and their five table bytes each are combined by one v_dot2_i32_i16.
 // ------------------------------------------------------------------------------------------
-constexpr int KW1_TW = 64, KW1_TH = 64, KW1_NT = 1024;
-constexpr int KW1_PW = 72, KW1_PH = KW1_TH + 2 * kWideHalo;
-static_assert(KW1_PW >= KW1_TW + 2 * kWideHalo && KW1_PW % 4 == 0, "tile rows hold the halo and are dword-aligned");
-static_assert(KW1_TW * KW1_TH == 4 * KW1_NT, "four adjacent pixels per thread");
-constexpr int kWide1LdsMax = kU1TableBytes + 3 * KW1_PH * KW1_PW;      // 98,656
+constexpr int kWide1LdsMax = kU1TableBytes + 3 * K3_PH * K3_PW;      // 98,656 (the tile of mulut_dev.h, K3_*)
 
 // byte (Q1, J1) | byte (Q2, J2) << 16 of the 7 x 12-byte window
 template <int Q1, int J1, int Q2, int J2>
@@ -42,10 +36,10 @@ __device__ __forceinline__ uint32_t wwin_pair(const uint32_t (&win)[7][3]) {
 // rotations R and R + 2 of pixel I (window column I + 3) for pattern PAT; returns sum + q * (both passes)
 template <int PAT, int R, int I>
 __device__ __forceinline__ int wide1_pair(const int8_t *s_lut, const uint32_t (&win)[7][3], uint32_t k0, uint32_t ta, int sum) {
-    constexpr int H = kWideHalo;
-    constexpr int yb = rot_dy(R, kWideDi[PAT][0], kWideDj[PAT][0]), xb = rot_dx(R, kWideDi[PAT][0], kWideDj[PAT][0]);
-    constexpr int yc = rot_dy(R, kWideDi[PAT][1], kWideDj[PAT][1]), xc = rot_dx(R, kWideDi[PAT][1], kWideDj[PAT][1]);
-    constexpr int yd = rot_dy(R, kWideDi[PAT][2], kWideDj[PAT][2]), xd = rot_dx(R, kWideDi[PAT][2], kWideDj[PAT][2]);
+    constexpr int H = kHalo3;
+    constexpr int yb = rot_dy(R, kPatDi[PAT][0], kPatDj[PAT][0]), xb = rot_dx(R, kPatDi[PAT][0], kPatDj[PAT][0]);
+    constexpr int yc = rot_dy(R, kPatDi[PAT][1], kPatDj[PAT][1]), xc = rot_dx(R, kPatDi[PAT][1], kPatDj[PAT][1]);
+    constexpr int yd = rot_dy(R, kPatDi[PAT][2], kPatDj[PAT][2]), xd = rot_dx(R, kPatDi[PAT][2], kPatDj[PAT][2]);
     FullPair1 fp;      // rotation R + 2 displaces by the negated offsets
     simplex4_full_pair1(k0, wwin_pair<H + yb, I + H + xb, H - yb, I + H - xb>(win), wwin_pair<H + yc, I + H + xc, H - yc, I + H - xc>(win),
                         wwin_pair<H + yd, I + H + xd, H - yd, I + H - xd>(win), fp);
@@ -78,16 +72,16 @@ __device__ __forceinline__ void wide1_mode(const int8_t *s_lut, const uint8_t *s
     static_for<0, 3>([&](auto CC) {
         constexpr int c = CC;
         if (c < C) {          // workgroup-uniform
-            const uint32_t *row = (const uint32_t *)(s_img + c * (KW1_PH * KW1_PW) + ty * KW1_PW + x4);
+            const uint32_t *row = (const uint32_t *)(s_img + c * (K3_PH * K3_PW) + ty * K3_PW + x4);
             uint32_t win[7][3];
 #pragma unroll
             for (int q = 0; q < 7; ++q)
 #pragma unroll
-                for (int k = 0; k < 3; ++k) win[q][k] = row[q * (KW1_PW / 4) + k];
+                for (int k = 0; k < 3; ++k) win[q][k] = row[q * (K3_PW / 4) + k];
             static_for<0, 4>([&](auto II) {
                 constexpr int i = II;
-                constexpr int J = i + kWideHalo;      // the pixel's window column
-                const uint32_t va = (win[kWideHalo][J >> 2] >> (8 * (J & 3))) & 0xFFu;
+                constexpr int J = i + kHalo3;      // the pixel's window column
+                const uint32_t va = (win[kHalo3][J >> 2] >> (8 * (J & 3))) & 0xFFu;
                 uint32_t k0 = full1_anchor_key(va);
                 const uint32_t ta = (va >> 4) * (uint32_t)kStrideA;
                 int sum = wide1_pair<PAT, 0, i>(s_lut, win, k0, ta, acc[4 * c + i]);
@@ -98,8 +92,8 @@ __device__ __forceinline__ void wide1_mode(const int8_t *s_lut, const uint8_t *s
     });
 }
 
-__global__ void __launch_bounds__(KW1_NT) stage_wide1_kernel(StageArgs a, WideArgs wa) {
-    constexpr int TW = KW1_TW, TH = KW1_TH, NT = KW1_NT, PW = KW1_PW, PH = KW1_PH, HALO = kWideHalo;
+__global__ void __launch_bounds__(K3_NT) stage_wide1_kernel(StageArgs a, PatternArgs wa) {
+    constexpr int TW = K3_TW, TH = K3_TH, NT = K3_NT, PW = K3_PW, PH = K3_PH, HALO = kHalo3;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int8_t *s_lut = (const int8_t *)smem;
     uint8_t *s_img = smem + kU1TableBytes;
@@ -188,7 +182,7 @@ constexpr int KWU_TW = 32, KWU_TH = 8;
 
 template <int U, bool MERGED>
 __global__ void __launch_bounds__(KWU_TW * KWU_TH, 4) stage_wide_up_kernel(StageArgs a) {
-    constexpr int TW = KWU_TW, TH = KWU_TH, NT = TW * TH, HALO = kWideHalo;
+    constexpr int TW = KWU_TW, TH = KWU_TH, NT = TW * TH, HALO = kHalo3;
     constexpr int PW = TW + 2 * HALO, PH = TH + 2 * HALO;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *s_img = smem;
@@ -234,7 +228,7 @@ __global__ void __launch_bounds__(KWU_TW * KWU_TH, 4) stage_wide_up_kernel(Stage
 }
 
 void stage_wide_tile(int u, int &tw, int &th) {
-    if (u == 1) { tw = KW1_TW; th = KW1_TH; }
+    if (u == 1) { tw = K3_TW; th = K3_TH; }
     else { tw = KWU_TW; th = KWU_TH; }
 }
 
@@ -247,7 +241,7 @@ const char *stage_wide_name(int u) {
     }
 }
 
-hipError_t launch_stage_wide1(const StageArgs &a, const WideArgs &w, hipStream_t st) {
+hipError_t launch_stage_wide1(const StageArgs &a, const PatternArgs &w, hipStream_t st) {
     if (a.C < 1 || a.C > 3 || a.M < 1 || a.M > kMaxModes) return hipErrorInvalidValue;
     for (int m = 0; m < a.M; ++m)
         if (w.pat[m] < 0 || w.pat[m] > 5) return hipErrorInvalidValue;
@@ -258,14 +252,14 @@ hipError_t launch_stage_wide1(const StageArgs &a, const WideArgs &w, hipStream_t
     }
     const long long nb = (long long)a.N * a.tiles_x * a.tiles_y;
     if (nb <= 0 || nb > 0x7fffffffLL) return hipErrorInvalidValue;
-    const size_t lds = (size_t)kU1TableBytes + (size_t)a.C * KW1_PH * KW1_PW;
-    hipLaunchKernelGGL(stage_wide1_kernel, dim3((unsigned)nb), dim3(KW1_NT), lds, st, a, w);
+    const size_t lds = (size_t)kU1TableBytes + (size_t)a.C * K3_PH * K3_PW;
+    hipLaunchKernelGGL(stage_wide1_kernel, dim3((unsigned)nb), dim3(K3_NT), lds, st, a, w);
     return hipGetLastError();
 }
 
 template <int U, bool MERGED>
 static hipError_t launch_wide_up_t(const StageArgs &a, hipStream_t st) {
-    constexpr int tile_bytes = ((3 * (KWU_TH + 2 * kWideHalo) * (KWU_TW + 2 * kWideHalo) + 15) / 16) * 16;
+    constexpr int tile_bytes = ((3 * (KWU_TH + 2 * kHalo3) * (KWU_TW + 2 * kHalo3) + 15) / 16) * 16;
     auto kern = stage_wide_up_kernel<U, MERGED>;
     {
         const hipError_t e = raise_lds_limit((const void *)kern, tile_bytes);

@@ -1,6 +1,7 @@
-// CPU unit-test harness for mulut_amd/csrc/mulut_ft_interval.h -- TEST ONLY, never a product path.
+// CPU unit-test harness for mulut_amd/csrc/mulut_ft_interval.h and the host-compilable part of mulut_ft.h -- TEST ONLY, never a product path.
 // It runs the per-pass set-up of the interval-5 / 6 fine-tune kernels (ft_iv_pass: rows, weights, rank order, corner codes) over
-// an array of key quadruples.  Launch geometry, LDS images and the C ABI are covered by the -m gpu tests.
+// an array of key quadruples, and the order code every fine-tune kernel (interval 4 included) ranks its keys with.  Launch
+// geometry, LDS images and the C ABI are covered by the -m gpu tests.
 #include <cstddef>
 #include <cstdint>
 
@@ -29,4 +30,9 @@ extern "C" int emul_ft_interval_passes(int interval, const float *v, long n, int
     else if (interval == 6) passes_iv<6>(v, n, idx, wt, ord, corner);
     else return -2;
     return 0;
+}
+
+// ft_order_code of n quadruples of LSBs (f: n x 4, each >= 0): code[i] = the keys by rank, two bits each
+extern "C" void emul_ft_order_code(const float *f, long n, int *code) {
+    for (long i = 0; i < n; ++i) code[i] = ft_order_code(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3]);
 }

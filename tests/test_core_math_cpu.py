@@ -4,25 +4,18 @@ golden fixtures.  This is a test of shared source, NOT a CPU product path."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_emul_lib import load_emul
 from oracle import c_oracle
-
-HERE = os.path.join(ROOT, "tests", "host_emul")
 
 
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(HERE, "libemul.so")
-    src = os.path.join(HERE, "emul.cpp")
-    hdr = os.path.join(ROOT, "mulut_amd", "csrc", "mulut_core.h")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", so, src])
-    L = ctypes.CDLL(so)
+    L = load_emul("emul", ["mulut_core.h"])
     L.emul_stage.restype = ctypes.c_int
     return L
 

@@ -7,16 +7,15 @@
 import ctypes
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+from host_emul_lib import load_emul_ft_interval
 from oracle import ft_torch
 
-HERE = os.path.join(ROOT, "tests", "host_emul")
 CASES = ["A5_s2sdy_x4_u8", "A6_s2sdy_x4_u8", "C5_s2sd_x2_u8", "B6_s1s_x3_float", "E5_s3y_x1_grid"]
 
 
@@ -72,12 +71,7 @@ def test_ft_oracle_matches_reference_at_intervals_5_and_6(name):
 
 @pytest.fixture(scope="module")
 def emul_ft_iv():
-    so = os.path.join(HERE, "libemul_ft_interval.so")
-    src = os.path.join(HERE, "emul_ft_interval.cpp")
-    hdrs = [os.path.join(ROOT, "mulut_amd", "csrc", h) for h in ("mulut_core.h", "mulut_interval.h", "mulut_ft_interval.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so, src])
-    L = ctypes.CDLL(so)
+    L = load_emul_ft_interval()
     L.emul_ft_interval_passes.restype = ctypes.c_int
     L.emul_ft_interval_passes.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_long] + [ctypes.c_void_p] * 4
     return L

@@ -1,8 +1,14 @@
-"""The fine-tune kernels order the four keys of a pass by ranks computed from comparisons (mulut_amd/csrc/mulut_ft.hip: ft_order_code)
-instead of the reference's 24-branch cascade of strict '>' tests (sr/model.py:191-282).  Gradients depend on the order at TIES, so the two
-must agree for every tie pattern: checked here exhaustively on a restatement of both (the kernels themselves are held to reference-made
-fixtures with integer inputs -- ties everywhere -- in tests/test_gpu_finetune.py)."""
+"""The fine-tune kernels order the four keys of a pass by ranks computed from comparisons (mulut_amd/csrc/mulut_ft.h: ft_order_code, the
+one definition the kernels of every interval use) instead of the reference's 24-branch cascade of strict '>' tests (sr/model.py:191-282).
+Gradients depend on the order at TIES, so the two must agree for every tie pattern: checked here exhaustively on a restatement of both
+and on the function itself, compiled by g++ (tests/host_emul/emul_ft_interval.cpp).  The kernels themselves are held to reference-made
+fixtures with integer inputs -- ties everywhere -- in tests/test_gpu_finetune.py."""
+import ctypes
 import itertools
+
+import numpy as np
+
+from host_emul_lib import load_emul_ft_interval
 
 
 def cascade(fa, fb, fc, fd):
@@ -40,3 +46,18 @@ def test_rank_order_equals_the_reference_cascade_for_every_tie_pattern():
     assert n == 256
     for f in itertools.product((0.0, 0.5, 7.25, 15.999), repeat=4):
         assert by_ranks(f) == cascade(*f), f
+
+
+def test_compiled_order_code_equals_the_reference_cascade_for_every_tie_pattern():
+    """ft_order_code as the kernels compile it (sign bits of int32 differences of the float patterns), on the same cases"""
+    cases = list(itertools.product((0.0, 1.0, 2.0, 3.0), repeat=4)) + list(itertools.product((0.0, 0.5, 7.25, 15.999), repeat=4))
+    cases += list(itertools.product((0.0, 1e-30, 31.5, 63.999), repeat=4))      # the smallest and the largest LSBs of any interval (q <= 64)
+    f = np.ascontiguousarray(cases, np.float32)
+    code = np.empty(len(f), np.int32)
+    L = load_emul_ft_interval()
+    L.emul_ft_order_code.restype = None
+    L.emul_ft_order_code.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
+    L.emul_ft_order_code(f.ctypes.data, len(f), code.ctypes.data)
+    assert len(f) == 3 * 256
+    for row, c in zip(f, code):
+        assert tuple((int(c) >> (2 * j)) & 3 for j in range(4)) == cascade(*row.tolist()), row

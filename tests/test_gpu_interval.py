@@ -1,5 +1,5 @@
 """Sampling intervals 5 and 6 on the GPU (-m gpu): every stage of a context configured at those intervals runs on
-stage_interval_kernel (mulut_interval.hip), passes on pass_interval_kernel.  Checked bit-exactly against the C oracle (generic in the
+stage_interval_kernel (mulut_interval.hip), passes on pass_kernel<IV> (mulut_kernels.hip).  Checked bit-exactly against the C oracle (generic in the
 interval) for s, d, y lists and against the host emulator of mulut_interval.h (tests/host_emul/emul_interval.cpp) for lists with
 e, h, o."""
 import os

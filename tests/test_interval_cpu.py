@@ -4,28 +4,21 @@ writers' ``{interval}bit``, taken only with the interval's L^4 rows).  oracle/np
 dicts; e, h, o are added to them here for the test only."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_emul_lib import load_emul
 from oracle import c_oracle, np_port
 
 from mulut_amd import lut_io
 
-HERE = os.path.join(ROOT, "tests", "host_emul")
 WIDE_PATTERNS = {"e": ((0, 0), (0, 3), (3, 0), (3, 3)), "h": ((0, 0), (2, 2), (2, 3), (3, 2)), "o": ((0, 0), (2, 2), (1, 3), (3, 1))}
 
 
 @pytest.fixture(scope="module")
 def emul_iv():
-    so = os.path.join(HERE, "libemul_interval.so")
-    src = os.path.join(HERE, "emul_interval.cpp")
-    hdrs = [os.path.join(ROOT, "mulut_amd", "csrc", h) for h in ("mulut_core.h", "mulut_interval.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", so, src])
-    L = ctypes.CDLL(so)
+    L = load_emul("emul_interval", ["mulut_core.h", "mulut_interval.h"])
     L.emul_stage_interval.restype = ctypes.c_int
     L.emul_check_rhe_interval.restype = ctypes.c_long
     return L

@@ -2,6 +2,7 @@
 # usage: [MULUT_ASM_SRC=mulut_k1|mulut_detail|mulut_kernels] tools/asm_stats.sh <kernel-name-substring> [extra hipcc flags]
 #   compiles mulut_kernels.hip with -save-temps into build/asm, prints registers / scratch / spills of every kernel whose mangled
 #   name contains the substring, writes the first one's ISA to build/asm/kernel.s and prints its VALU instruction class histogram
+#   (tools/asm_compare.py holds the cutter, and compares two trees kernel by kernel)
 R=$(cd "$(dirname "$0")/.." && pwd)
 K=$1; shift
 D=$R/build/asm; mkdir -p $D
@@ -15,5 +16,5 @@ for N in $(grep -o "^_Z[A-Za-z0-9_]*$K[A-Za-z0-9_]*:" $S | tr -d ':'); do
   grep -A14 "\.name: *$N\$" $S | grep "private_segment\|vgpr_count\|sgpr_count\|spill_count" | tr -s ' ' | tr '\n' ' '; echo
 done
 [ -z "$first" ] && { echo "no kernel matches $K"; exit 1; }
-awk -v n="$first:" 'index($0,n)==1{p=1} p{print} /^\.Lfunc_end/{if(p){exit}}' $S > $D/kernel.s      # (a kernel may hold several s_endpgm: cut at the function's end label)
+python3 $R/tools/asm_compare.py cut $S $first > $D/kernel.s      # (the one cutter: label to .Lfunc_end; asm_compare.py compares two trees kernel by kernel)
 echo "ISA of $first: $(wc -l < $D/kernel.s) lines, scratch ops $(grep -c scratch_ $D/kernel.s), v_readlane/writelane $(grep -c 'v_readlane\|v_writelane' $D/kernel.s)"
