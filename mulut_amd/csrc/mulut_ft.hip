@@ -557,7 +557,7 @@ __global__ void __launch_bounds__(256) ft_quantize_kernel(FtQuantArgs a) {
     const int m = (int)blockIdx.y;
     const float r = rintf(a.w[m][i] * 127.0f);          // torch.round: half to even
     if (BACKWARD) a.o[m][i] = a.o[m][i] * ((r >= -127.0f && r <= 127.0f) ? 1.0f : 0.0f) * 127.0f;      // the clamp passes gradient inside [-127, 127] inclusive
-    else a.o[m][i] = fminf(fmaxf(r, -127.0f), 127.0f);
+    else a.o[m][i] = r != r ? r : fminf(fmaxf(r, -127.0f), 127.0f);      // torch.clamp keeps NaN (fminf / fmaxf drop it): a diverged run must show
 }
 
 }  // namespace mulut

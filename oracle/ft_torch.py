@@ -41,12 +41,13 @@ def _case_order(fa, fb, fc, fd):
     return w(fab & fbc, g1, w(fab & fac, g2, w(fab, g3, w(fac, g4, w(fbc, g5, g6)))))
 
 
-def interp_batch(weight, upscale, mode, img_in, bd, interval=4):
-    """InterpTorchBatch (sr/model.py:69-287): weight [L^4, u*u] (learnable, int8/127 scale), img_in [B,C,h+bd,w+bd]."""
+def interp_batch(weight, upscale, mode, img_in, bd, interval=4, quantised=False):
+    """InterpTorchBatch (sr/model.py:69-287): weight [L^4, u*u] (learnable, int8/127 scale), img_in [B,C,h+bd,w+bd].
+    quantised: `weight` already is the quantised table (what the stage kernels of the C ABI are handed)."""
     if mode not in PATTERNS:
         raise ValueError("Mode {} not implemented.".format(mode))
     q, L = 2 ** interval, 2 ** (8 - interval) + 1
-    wq = torch.clamp(round_bpda(weight * 127), -127, 127)
+    wq = weight if quantised else torch.clamp(round_bpda(weight * 127), -127, 127)
     B, C, Hp, Wp = img_in.shape
     h, w = Hp - bd, Wp - bd
     crops = [img_in[:, :, di:di + h, dj:dj + w] for di, dj in PATTERNS[mode]]
@@ -67,20 +68,26 @@ def interp_batch(weight, upscale, mode, img_in, bd, interval=4):
     return out / q
 
 
+def stage(tables, x, modes, is_last, u, interval=4, quantised=False):
+    """One stage of MuLUT.forward (sr/model.py:296-309) on x in 0..255: all modes x 4 rotations, pred rounded after every pass,
+    then the stage's clamp and round.  tables: one [L^4, u*u] tensor per mode, in the order of `modes`.  Returns (stage output,
+    un-clamped pred).  quantised: the tables are taken as quantised already (no * 127, round, clamp), so their gradients are those of
+    the quantised tables -- what the stage entry points of the C ABI produce."""
+    avg, bias = (len(modes), 0) if is_last else (len(modes) * 4, 127)
+    pred = 0
+    for mode, wgt in zip(modes, tables):
+        pad = PAD[mode]
+        for r in range(4):
+            t = F.pad(torch.rot90(x, r, [2, 3]), (0, pad, 0, pad), mode="replicate")
+            pred = pred + torch.rot90(interp_batch(wgt, u, mode, t, pad, interval, quantised), (4 - r) % 4, [2, 3])
+            pred = round_bpda(pred)
+    return round_bpda(torch.clamp(pred / avg + bias, 0, 255)), pred
+
+
 def forward(weights, x, stages, modes, upscale, interval=4):
     """MuLUT.forward (sr/model.py:289-312).  weights: dict 's{stage}_{mode}' -> tensor [L^4, u*u] (requires_grad ok)."""
     x = x * 255.0
     for s in range(stages):
-        stage = s + 1
-        last = stage == stages
-        avg, bias, scale = (len(modes), 0, upscale) if last else (len(modes) * 4, 127, 1)
-        pred = 0
-        for mode in modes:
-            pad = PAD[mode]
-            wgt = weights["s{}_{}".format(stage, mode)]
-            for r in range(4):
-                t = F.pad(torch.rot90(x, r, [2, 3]), (0, pad, 0, pad), mode="replicate")
-                pred = pred + torch.rot90(interp_batch(wgt, scale, mode, t, pad, interval), (4 - r) % 4, [2, 3])
-                pred = round_bpda(pred)
-        x = round_bpda(torch.clamp(pred / avg + bias, 0, 255))
+        last = s + 1 == stages
+        x, _ = stage([weights["s{}_{}".format(s + 1, mode)] for mode in modes], x, modes, last, upscale if last else 1, interval)
     return x / 255.0
