@@ -40,7 +40,8 @@ enum {
     MULUT_EMODE = -2,       /* mode not in {s,d,y,e,h,o}: reference raises ValueError, 4_test_lut.py:54 */
     MULUT_ENOLUT = -3,      /* table (stage,mode) not set: reference raises from np.load, :333  */
     MULUT_ESHAPE = -4,      /* table shape does not match (rows, v_num) expected for the stage */
-    MULUT_EUNSUPPORTED = -5,/* interval not in {4,5,6}, scale not in 1..4, stages/modes beyond limits */
+    MULUT_EUNSUPPORTED = -5,/* interval not in {4,5,6}, scale not in 1..4, stages/modes beyond limits, image sizes beyond the
+                               32-bit fields of a launch (mulut_pipeline, "Batch size") */
     MULUT_EHIP = -6,        /* a HIP runtime call failed (mulut_last_hip_error() has the text) */
     MULUT_ENODEVICE = -7,   /* no usable gfx950 device: there is no CPU path                   */
     MULUT_ENOTCONFIGURED = -8,
@@ -105,7 +106,17 @@ int mulut_stage(mulut_ctx *ctx, int stage, const uint8_t *in, int in_layout, uin
  * detailed-tile path of x4 final stages, 30-bit pixel ids, 32-bit site ids).  Every entry point -- this one, mulut_pipeline_rows,
  * mulut_stage -- runs a STAGE whose launch would exceed a width as sub-launches of whole images that fit (43 frames of 1080p RGB
  * per final-stage launch): same result, same kernels; no batch size falls to a slower path.  (The timing helpers then report the
- * last sub-launch of a stage.)  A single image beyond 2^28 bytes takes the gather kernels for its detailed tiles. */
+ * last sub-launch of a stage.)  A SINGLE image beyond a width (the widths count the logical image, H or H_full rows, not the rows
+ * of a strip) keeps its result and changes kernels:
+ *   - stage input of 2^28 bytes or more (x4 final stage): its detailed tiles take the gather kernel, not the anchor slabs;
+ *   - H * W >= 2^30 (x4 final stage): the whole stage runs on the gather kernel (stage_up_kernel), no tube kernel or fix-up list;
+ *   - C * H * W >= 2^32, C <= 3 the channels of one group (stages with 1-byte rows, x2 / x3 final stages): the window kernel
+ *     (stage_u1w_kernel) resp. the gather kernel on every tile.
+ * Planes of 2^31 bytes or more, in and out, are supported in both layouts (the image and channel strides are 64-bit).
+ * Refused with MULUT_EUNSUPPORTED, by this call, mulut_pipeline_rows, mulut_stage and mulut_reserve alike and before anything is
+ * allocated or launched: sizes that do not fit the 32-bit signed fields of the launch arguments -- a packed output row of
+ * W * scale * C bytes or H * scale output rows beyond 2^31 - 1, or more than 2^31 - 1 tiles of 32 x 8 sites in one call
+ * (N * ceil(W / 32) * ceil(rows / 8), rows = H, or the rows of the band handed to mulut_pipeline_rows). */
 int mulut_pipeline(mulut_ctx *ctx, const uint8_t *in, uint8_t *out, int N, int H, int W, int C, int layout,
                    void *stream);
 
@@ -113,7 +124,9 @@ int mulut_pipeline(mulut_ctx *ctx, const uint8_t *in, uint8_t *out, int N, int H
  * its rows [in_row0, in_row0 + in_rows) and `out` receives output rows for LR rows [y0, y1), i.e.
  * HR rows [y0*scale, y1*scale), stored from row 0 of `out`.  The input must cover the halo
  * [y0 - mulut_halo(ctx), y1 + mulut_halo(ctx)) clipped to the image; edge replication happens only
- * at true image borders, so strips tile bit-exactly. */
+ * at true image borders, so strips tile bit-exactly.  The index widths of "Batch size" (mulut_pipeline) are those of the LOGICAL
+ * image: sub-launches, the fall-backs of a single image beyond a width and the refusals are decided from H_full, whatever the
+ * band holds -- except the 2^28 bytes of the anchor-slab path, which count the band's bytes. */
 int mulut_pipeline_rows(mulut_ctx *ctx, const uint8_t *in, int in_row0, int in_rows, uint8_t *out, int y0, int y1,
                         int N, int H_full, int W, int C, int layout, void *stream);
 
@@ -139,7 +152,8 @@ int mulut_last_kernel_ms(mulut_ctx *ctx, float *ms, int cap);
 /* Work counters of the detailed-tile path of the last final-stage launch (scale 4; device -> host copy, synchronises with
  * `stream`): out[0..15] = samples (pixel x channel) per anchor MSB that went through the anchor-slab kernel,
  * out[16] = work items, out[17] = entries (samples, or border pixels with all their channels) on the fix-up list of that launch.  Returns the number of values written
- * (0 when the path has not run).  For tests and the bench report; the reference has no counterpart. */
+ * (0 when the path has not run; out[0..16] are zero after an x4 tube or hybrid launch whose detailed tiles took the gather kernel).
+ * For tests and the bench report; the reference has no counterpart. */
 int mulut_last_detail_counters(mulut_ctx *ctx, uint32_t *out, int cap, void *stream);
 /* Probe buffer of the context: MULUT_DEBUG_WORDS 64-bit words of device memory that only probe builds of the kernels
  * (-DMULUT_VARIANT_...prof: in-kernel clock stamps per phase) write to -- never an output buffer, and no output value is computed

@@ -184,7 +184,7 @@ const char *mulut_strerror(int err) {
         case MULUT_EMODE: return "Mode not implemented.";
         case MULUT_ENOLUT: return "LUT for (stage, mode) not set";
         case MULUT_ESHAPE: return "LUT shape does not match (L^4, v_num) for this stage (83521 rows at interval 4, 6561 at 5, 625 at 6)";
-        case MULUT_EUNSUPPORTED: return "unsupported configuration (interval must be 4, 5 or 6, scale 1..4)";
+        case MULUT_EUNSUPPORTED: return "unsupported configuration (interval must be 4, 5 or 6, scale 1..4, sizes within the 32-bit launch fields)";
         case MULUT_EHIP: return "HIP runtime error";
         case MULUT_ENODEVICE: return "no usable HIP device (there is no CPU path)";
         case MULUT_ENOTCONFIGURED: return "mulut_configure() has not been called";
@@ -403,6 +403,16 @@ int mulut_pass(mulut_ctx *ctx, int stage, char mode, int r, const uint8_t *in_ch
     return MULUT_OK;
 }
 
+// The launch arguments hold a row stride (W * u * C for a packed output), the output's row numbers (H * u) and the tile counts of a
+// launch (the smallest tiling is 32 x 8) in int fields: a call whose sizes would not fit them is refused by every entry point, before
+// anything is allocated or launched.  rows: the most rows of one image that a stage of the call computes
+static bool sizes_fit_int(const mulut_ctx *ctx, int N, int rows, int H, int W, int C) {
+    const long long lim = 0x7fffffffLL, u = ctx->scale;
+    if ((long long)W * u * C > lim || (long long)H * u > lim) return false;
+    const long long tiles = (long long)((W + 31) / 32) * ((rows + 7) / 8);      // (< 2^54; then N * tiles < 2^62)
+    return tiles <= lim && (long long)N * tiles <= lim;
+}
+
 static View make_view(const uint8_t *p, int layout, int rows, int W, int C, int row0) {
     View v;
     v.p = const_cast<uint8_t *>(p);
@@ -410,7 +420,7 @@ static View make_view(const uint8_t *p, int layout, int rows, int W, int C, int 
     if (layout == MULUT_LAYOUT_HWC) {
         v.sX = C; v.sC = 1; v.sY = W * C;
     } else {
-        v.sX = 1; v.sY = W; v.sC = rows * W;
+        v.sX = 1; v.sY = W; v.sC = (long long)rows * W;
     }
     v.sN = (long long)rows * W * C;
     return v;
@@ -541,7 +551,9 @@ static StagePlan plan_stage(const mulut_ctx *ctx, const Routing &r, int u, const
     // its three patterns; final_kernel 5 = on every tile, 0 / 6 = hybrid with the per-tile statistic
     p.tube2 = u == 4 && r.tube2 && stage_tube2_supported(a);
     p.wide4 = u == 4 && a.M > 4;
-    if (u != 4 || r.final_kernel == 1 || (a.M > 3 && !p.tube2)) {
+    // (a launch whose pixel ids would pass the 30 bits of the fix-up list -- one image that large: run_stage splits batches -- takes the
+    // gather kernel, as the 1-byte-row and x2 / x3 families fall back at 2^32 site ids)
+    if (u != 4 || r.final_kernel == 1 || (a.M > 3 && !p.tube2) || N * a.H * a.W >= (1ull << 30)) {
         tile_grid(a, stage_up_tile, p.tiles_x, p.tiles_y);
         p.route = kRouteGather;
         return p;
@@ -672,6 +684,8 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
         ctx->k1_out = out.p;
         return MULUT_OK;
     }
+    // (a launch without the slab path leaves none of an earlier launch's counters behind: mulut_last_detail_counters)
+    if (!p.slab && ctx->det_ctl) HIP_TRY(ctx, hipMemsetAsync(ctx->det_ctl, 0, kDetCtlDwords * sizeof(uint32_t), st));
     auto tube = [&]() {
         return p.tube2 ? launch_stage_tube2(a, b, p.out_mode, ctx->num_cus, st) : launch_stage_tube(a, b, p.out_mode, ctx->num_cus, st);
     };
@@ -752,6 +766,7 @@ static int ensure_workspace(mulut_ctx *ctx, size_t bytes) {
 int mulut_reserve(mulut_ctx *ctx, int N, int H, int W, int C) {
     if (!ctx || N <= 0 || H <= 0 || W <= 0 || C <= 0) return MULUT_EINVAL;
     if (!ctx->configured) return MULUT_ENOTCONFIGURED;
+    if (!sizes_fit_int(ctx, N, H, H, W, C)) return MULUT_EUNSUPPORTED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // the plans of every stage's largest launches -- all N images, and the sub-launch a batch beyond an index width runs as (run_stage)
     // -- under the default routes, which use every buffer any route does: a later call of at most this shape allocates nothing,
@@ -783,6 +798,7 @@ int mulut_stage(mulut_ctx *ctx, int stage, const uint8_t *in, int in_layout, uin
     if (!ctx || !in || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0) return MULUT_EINVAL;
     if (!ctx->configured) return MULUT_ENOTCONFIGURED;
     if (stage < 1 || stage > ctx->stages) return MULUT_EINVAL;
+    if (!sizes_fit_int(ctx, N, H, H, W, C)) return MULUT_EUNSUPPORTED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int u = stage_u(ctx, stage);
     // channels are independent planes through the same tables (sr/4_test_lut.py:14-237 is channel-count agnostic): more than three
@@ -801,7 +817,8 @@ int mulut_pipeline_rows(mulut_ctx *ctx, const uint8_t *in, int in_row0, int in_r
                         int N, int H, int W, int C, int layout, void *stream) {
     if (!ctx || !in || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0) return MULUT_EINVAL;
     if (!ctx->configured) return MULUT_ENOTCONFIGURED;
-    if (y0 < 0 || y1 > H || y0 >= y1 || in_row0 < 0 || in_rows <= 0 || in_row0 + in_rows > H) return MULUT_EINVAL;
+    if (y0 < 0 || y1 > H || y0 >= y1 || in_row0 < 0 || in_rows <= 0 || (long long)in_row0 + in_rows > H) return MULUT_EINVAL;
+    if (!sizes_fit_int(ctx, N, in_rows, H, W, C)) return MULUT_EUNSUPPORTED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int S = ctx->stages, reach = ctx->reach;
     // rows of each stage's output that the cascade needs

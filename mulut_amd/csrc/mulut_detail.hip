@@ -225,7 +225,7 @@ __global__ void __launch_bounds__(256) detail_fill_kernel(StageArgs a, DetailArg
         for (int k = 0; k < 4; ++k)
             if (fixr[k] != 0xFFFFFFFFu) {
                 const int s = (int)threadIdx.x + k * 256;
-                a.fix_list[s_fix[1] + fixr[k]] = (uint32_t)((n * a.H + y0 + ((s >> 6) & 15)) * a.W + x0 + (s & 63)) | (3u << 30);
+                a.fix_list[s_fix[1] + fixr[k]] = (((uint32_t)n * (uint32_t)a.H + (uint32_t)(y0 + ((s >> 6) & 15))) * (uint32_t)a.W + (uint32_t)(x0 + (s & 63))) | (3u << 30);
             }
 #pragma unroll
         for (int k = 0; k < PER; ++k)

@@ -785,7 +785,7 @@ __global__ void __launch_bounds__(u1t_threads(U, PATS), u1t_waves(U, PATS)) stag
                     const uint32_t bits = (bytes >> (4 * k)) & 0xFu;
                     if (bits == 0u) continue;
                     const int g = GB * t + k, cg = g % (TW / 4), row = (g / (TW / 4)) % TH, c = g / ((TW / 4) * TH);
-                    const uint32_t id0 = (uint32_t)(((n * a.C + c) * a.H + y0 + row) * a.W + x0 + 4 * cg);
+                    const uint32_t id0 = (((uint32_t)n * (uint32_t)a.C + (uint32_t)c) * (uint32_t)a.H + (uint32_t)(y0 + row)) * (uint32_t)a.W + (uint32_t)(x0 + 4 * cg);      // (reaches 2^32 - 1: unsigned throughout)
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         if ((bits >> i) & 1u) a.fix_list[at++] = id0 + (uint32_t)i;

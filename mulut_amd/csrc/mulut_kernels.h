@@ -17,8 +17,8 @@ constexpr int kU1TableBytes = (kRows + 15) & ~15;  // 83536: int8 rows of a v_nu
 //   addr(n, c, y, x) = p + n*sN + c*sC + (y - row0)*sY + x*sX      (y in logical image rows)
 struct View {
     uint8_t *p;
-    long long sN;
-    int sC, sY, sX;
+    long long sN, sC;       // (a plane may hold 2^31 bytes or more: the channel stride is 64-bit like the image stride)
+    int sY, sX;
     int row0;
 };
 

@@ -596,7 +596,7 @@ __global__ void __launch_bounds__(TW *TH) stage_tube_kernel(StageArgs a, BandArg
             if constexpr (OUT == kOutPackedRGBU4) store_rgb<4>(a, n, y, x, o0, o1, o2);
             // dirty samples (pixel, channel) go on the fix-up list: one atomic per wave and channel (rare), compacted by lane rank
             if (__ballot(dmask != 0u) != 0ull) {
-                const uint32_t pixel_id = (uint32_t)((n * a.H + y) * a.W + x);
+                const uint32_t pixel_id = ((uint32_t)n * (uint32_t)a.H + (uint32_t)y) * (uint32_t)a.W + (uint32_t)x;
                 for (int c = 0; c < a.C; ++c) {
                     const bool d = ((dmask >> c) & 1u) != 0u;
                     const unsigned long long dm = __ballot(d);
@@ -1130,7 +1130,7 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
             if (dmask == 0xFFFFFFFFu) a.fix_list[0] = 0u;
 #else
             if (__ballot(dmask != 0u) != 0ull) {
-                const uint32_t pixel_id = (uint32_t)((n * a.H + y) * a.W + x);
+                const uint32_t pixel_id = ((uint32_t)n * (uint32_t)a.H + (uint32_t)y) * (uint32_t)a.W + (uint32_t)x;
                 const unsigned long long m0 = __ballot((dmask & 1u) != 0u), m1 = __ballot((dmask & 2u) != 0u), m2 = __ballot((dmask & 4u) != 0u);
                 const uint32_t n0 = (uint32_t)__popcll(m0), n1 = (uint32_t)__popcll(m1), n2 = (uint32_t)__popcll(m2);
                 if (fix_have + n0 + n1 + n2 > (uint32_t)kT2FixCap) fix_flush();
