@@ -15,6 +15,19 @@
  *     workspace.  LUT rows passed to mulut_set_lut() are HOST pointers.
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); all work is
  *     stream-ordered and asynchronous with respect to the host.
+ *   - the set-up calls that overwrite or free device memory of the context WAIT FOR ALL WORK IN FLIGHT ON THE DEVICE first
+ *     (hipDeviceSynchronize: the caller's streams are not known to them, and a non-blocking stream is not ordered against the
+ *     null stream their copies run on): mulut_set_lut() on a slot that already holds a table, mulut_configure() when it
+ *     moves to another interval (it frees every table), mulut_destroy(), and any call that has to enlarge the workspace or a
+ *     work list (mulut_reserve(), or a compute call larger than every call before it).  Calls still queued on any stream therefore finish on the tables and buffers
+ *     they were issued with.  A compute call that allocates nothing never waits.
+ *   - image buffers need NO alignment: any byte address is accepted, in and out, in both layouts (4-aligned bases with
+ *     W % 4 == 0 take dword loads and stores, others the byte paths -- the same result), and nothing outside
+ *     [out, out + N * H*scale * W*scale * C) is written.
+ *   - a call refused for its arguments (MULUT_EINVAL, MULUT_EMODE, MULUT_ESHAPE or MULUT_EUNSUPPORTED from mulut_configure,
+ *     mulut_set_lut, mulut_set_tuning) leaves the context as it was.  MULUT_EHIP is no such refusal: a HIP failure part-way through
+ *     mulut_set_lut or through the table release of mulut_configure may leave that table (or its band / slab) half replaced; set the
+ *     tables again, or destroy the context.
  *   - one context per device; calls on one context must be serialised by the caller.
  *   - there is NO CPU fallback: without a usable HIP device mulut_create() fails.
  *
@@ -243,7 +256,11 @@ int mulut_eval_y(int device, const void *gt_hwc, const void *out_hwc, int H, int
  * buffers are then never reallocated by smaller calls; a LARGER later call reallocates them and invalidates graphs captured
  * before it.  Configuring the context at another interval frees every table, and mulut_set_lut() with a table of another size
  * reallocates that table: graphs captured before either would replay against freed table memory and must be captured again
- * (setting a table of the same shape rewrites it in place, so a captured graph then reads the new values).  Run the call to be
+ * (setting a table of the same shape rewrites it in place, so a captured graph then reads the new values).  The set-up calls
+ * that wait for the device (see the conventions above: mulut_set_lut, an interval change, mulut_destroy, a growing call) call
+ * hipDeviceSynchronize, which is not allowed while ANY stream of the process captures in the global capture mode (the default of
+ * hipStreamBeginCapture and of torch.cuda.graph): issued then, from this or another host thread, they fail with MULUT_EHIP and
+ * invalidate that capture.  Make them before the capture begins or after it ends.  Run the call to be
  * captured once outside capture first: the first launch of each kernel raises that kernel's
  * dynamic-LDS limit (hipFuncSetAttribute), which is not a capturable operation.  These one-time per-device set-ups are
  * serialised inside the library: contexts may be created and first used from several host threads. */

@@ -93,6 +93,15 @@ static int pattern_id(char m) {
         }                                                                                   \
     } while (0)
 
+// Set-up calls that overwrite or free device memory a kernel of an earlier call may still read (tables, bands, slabs, work lists,
+// the workspaces) wait for the device first: the caller's streams are unknown here, and a non-blocking stream is not ordered
+// against the null stream the copies run on.  Only mulut_set_lut, the releasing branch of mulut_configure, grow() when it
+// reallocates and mulut_destroy come through here -- never a compute call that allocates nothing
+static int wait_for_device(mulut_ctx *ctx) {
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return MULUT_OK;
+}
+
 // Device copy of a host image: the buffer is reallocated only when the size changes
 template <class P, class V>
 static int upload(mulut_ctx *ctx, P *&dev, size_t &bytes, const std::vector<V> &img) {
@@ -165,7 +174,11 @@ static std::vector<uint8_t> slab_pairs(const std::vector<uint8_t> &img) {
 template <class T>
 static int grow(mulut_ctx *ctx, T *&p, size_t &cap, size_t n) {
     if (n <= cap) return MULUT_OK;
-    if (p) HIP_TRY(ctx, hipFree(p));
+    if (p) {
+        const int rc = wait_for_device(ctx);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipFree(p));
+    }
     p = nullptr;
     cap = 0;
     HIP_TRY(ctx, hipMalloc((void **)&p, n * sizeof(T)));
@@ -218,6 +231,7 @@ int mulut_create(int device_id, mulut_ctx **out_ctx) {
 int mulut_destroy(mulut_ctx *ctx) {
     if (!ctx) return MULUT_EINVAL;
     (void)hipSetDevice(ctx->device);
+    (void)wait_for_device(ctx);     // kernels still queued read what is freed below
     for (auto &st : ctx->tab)
         for (auto &t : st)
         {
@@ -254,19 +268,23 @@ int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, in
     if ((interval != kInterval && interval != 5 && interval != 6) || scale < 1 || scale > 4) return MULUT_EUNSUPPORTED;
     // tiles of the s / d / y kernels always stage a 2-px halo (d / y patterns; s-only models use it too); a list with a 4 x 4
     // pattern (e, h, o) reaches 3 px per stage and runs on the wide kernels
+    // (a refused call leaves the context as it was: the whole list is checked before anything of the context is written)
     int reach = 2;
+    signed char di[MULUT_MAX_MODES][3], dj[MULUT_MAX_MODES][3];
     for (size_t m = 0; m < M; ++m) {
-        int di[3], dj[3];
-        if (!pattern_offsets(modes[m], di, dj)) return MULUT_EMODE;
+        int oi[3], oj[3];
+        if (!pattern_offsets(modes[m], oi, oj)) return MULUT_EMODE;
         reach = imax(reach, pattern_reach(modes[m]));
         for (int k = 0; k < 3; ++k) {
-            ctx->di[m][k] = (signed char)di[k];
-            ctx->dj[m][k] = (signed char)dj[k];
+            di[m][k] = (signed char)oi[k];
+            dj[m][k] = (signed char)oj[k];
         }
     }
     if (interval != ctx->tab_interval) {
         // tables of another interval have another row count: none of them can serve this one (MULUT_ENOLUT until set again)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const int wrc = wait_for_device(ctx);
+        if (wrc) return wrc;
         for (auto &st : ctx->tab)
             for (auto &t : st) {
                 int rc = release(ctx, t.dev, t.bytes);
@@ -277,6 +295,8 @@ int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, in
             }
         ctx->tab_interval = interval;
     }
+    memcpy(ctx->di, di, sizeof(di));
+    memcpy(ctx->dj, dj, sizeof(dj));
     ctx->stages = stages;
     ctx->n_modes = (int)M;
     ctx->scale = scale;
@@ -319,6 +339,10 @@ int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows,
     if (!u) return MULUT_ESHAPE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevTable &t = ctx->tab[stage - 1][pid];
+    if (t.dev) {        // a table of the same shape is rewritten in place, another one is freed; an empty slot has no reader
+        const int wrc = wait_for_device(ctx);
+        if (wrc) return wrc;
+    }
     if (iv != kInterval) {
         // intervals 5 / 6: the plain int8 rows, padded to iv_row_bytes(u) (stage_interval_kernel and pass_kernel<5 / 6> read nothing else)
         const int rb = iv_row_bytes(u);

@@ -49,6 +49,27 @@ def test_eval_set5_matches_reference_and_summary_line(eng, fx):
     assert "{:.2f} {:.4f}".format(*np.mean(vals, axis=0)) == "30.61 0.8656"
 
 
+@pytest.mark.parametrize("name", ["photo_1080p", "noisy_1080p", "tiles_plus_1", "tiles_minus_1"])
+def test_eval_frames_beyond_the_first_grid_stride_pass(eng, name):
+    """sse_y_kernel covers 1024 x 256 = 262,144 interior pixels in the first pass of its grid-stride loop and ssim_y_kernel has run
+    with at most 256 tiles in the tests above: full 1080p HR frames (2,058,624 interior pixels, 8 passes; 34 x 60 = 2,040 tiles)
+    and frames whose SSIM map ends one pixel after / before a tile edge.  Reference: mulut_amd/metrics.py, which
+    test_metrics_cpu.py holds to the reference's own numbers; its float32 mean and the kernel's float64 sums give the same float32 at
+    this size (test_float32_and_float64_means_agree_within_the_psnr_bar_on_full_frames), so the file's bars apply unchanged."""
+    from mulut_amd.metrics import psnr, rgb2ycbcr, ssim
+    from eval_pairs import big_pairs
+    gt, out, shave = big_pairs()[name]
+    H, W = gt.shape[:2]
+    assert (H - 2 * shave) * (W - 2 * shave) > 1024 * 256 and -(-(H - 10) // 32) * -(-(W - 10) // 32) > 256
+    if name.startswith("tiles"):
+        assert (H - 10) % 32 == (W - 10) % 32 and (H - 10) % 32 in (1, 31)
+    y_gt, y_out = rgb2ycbcr(gt)[:, :, 0], rgb2ycbcr(out)[:, :, 0]
+    p, s = eng.eval_y(dev(gt), dev(out), shave)
+    print(name, "psnr", p, "ssim", s)
+    assert p == pytest.approx(float(psnr(y_gt, y_out, shave)), abs=1e-4), name
+    assert s == pytest.approx(ssim(y_gt, y_out), abs=1e-10), name
+
+
 def test_eval_identical_images_and_errors(eng):
     a = dev(np.random.default_rng(0).integers(0, 256, (40, 50, 3), dtype=np.uint8))
     p, s = eng.eval_y(a, a, 4)

@@ -7,6 +7,7 @@ import pytest
 from PIL import Image
 
 from conftest import GOLDEN
+from eval_pairs import big_pairs
 
 from mulut_amd.metrics import modcrop, psnr, rgb2ycbcr, ssim
 
@@ -57,3 +58,20 @@ def test_scores_do_not_depend_on_concurrent_callers(fx):
     with ThreadPoolExecutor(4) as ex:
         for _ in range(40):
             assert list(ex.map(lambda p: _score(p[0], p[1], 4), pairs)) == want
+
+
+# ---------------------------------------------------------------------------------------------------------------- full frames
+def test_float32_and_float64_means_agree_within_the_psnr_bar_on_full_frames():
+    """The reference takes np.mean of a float32 array of squared differences (pairwise float32 sums); mulut_eval_y adds the same
+    float32 squares in float64 and rounds the mean to float32.  At 2 M pixels the two must still agree within the 1e-4 dB bar that
+    test_gpu_eval.py holds the device to.  Measured: no difference at all on these four pairs (the two means round to the same float32; printed below)."""
+    for name, (gt, out, shave) in big_pairs().items():
+        d = rgb2ycbcr(out)[:, :, 0].astype(np.float32) - rgb2ycbcr(gt)[:, :, 0].astype(np.float32)
+        d = d[shave:-shave, shave:-shave]
+        sq = np.power(d, 2)
+        assert sq.dtype == np.float32 and sq.size > 262144
+        p32 = 20 * np.log10(255.0 / np.sqrt(np.mean(sq)))
+        p64 = 20 * np.log10(255.0 / np.sqrt(np.float32(np.mean(sq, dtype=np.float64))))
+        assert p32 == psnr(rgb2ycbcr(gt)[:, :, 0], rgb2ycbcr(out)[:, :, 0], shave)
+        print(name, sq.size, "pixels: float32 mean %.9f dB, float64 mean %.9f dB, difference %.3g dB" % (p32, p64, abs(p32 - p64)))
+        assert abs(p32 - p64) < 1e-5, name            # a tenth of the device test's bar
