@@ -178,7 +178,8 @@ int mulut_debug_read(mulut_ctx *ctx, unsigned long long *out, int cap, int reset
 /* ---- LUT-aware fine-tuning (the differentiable twin; stateless, float32) -----------------------------
  * One stage of MuLUT.forward (sr/model.py:289-312) = InterpTorchBatch (:69-287) over all modes x 4 rotations
  * with the per-pass BPDA rounding (:308) and the stage's clamp/round (:309).  Modes s, d, y only: e, h, o return MULUT_EMODE
- * (the input-gradient tiles stage a 2-pixel halo; the reference's module raises for them too, sr/model.py:121).
+ * from the six functions below, as the reference's module raises for them (sr/model.py:121) -- their backward kernels stage a
+ * 2-pixel halo of the input gradient.  A list with e, h or o goes to mulut_ft_wide_stage_forward / _backward further down.
  *   weights_q : M device pointers, the QUANTISED tables clamp(round(w*127),-127,127) as float32 [83521][u*u]
  *               (sr/model.py:74-76 -- done by the caller, which also applies that step's backward)
  *   x         : device float32 [B][C][H][W] in 0..255 (the module multiplies its input by 255, :290)
@@ -216,6 +217,19 @@ int mulut_ft_interval_stage_forward(int device, int interval, const float *const
 int mulut_ft_interval_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
                                      const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
                                      float *const *grad_wq, float *grad_x, void *stream);
+/* The masked pair for ANY list over the six sampling patterns s, d, y, e, h, o, at interval 4, 5 or 6: MuLUT.forward's stage
+ * (sr/model.py:69-312) with the 4 x 4 patterns the reference's module leaves out ("more sampling modes can be implemented
+ * similarly", sr/model.py:119-121; their taps are the network's, common/network.py:173-215, edge pad 3).  weights_q are float32
+ * [L^4][u*u], already quantised, as above.  A list with e, h or o runs the backward kernels built with a 3-pixel halo of the input
+ * gradient; a list without is forwarded to what mulut_ft_stage_*_mask (interval 4) / mulut_ft_interval_stage_* (5, 6) launch, so
+ * the results are theirs bit for bit.  `inside` is required in both calls (there is no recomputing form).  interval outside 4..6,
+ * u outside 1..4 and more than MULUT_MAX_MODES modes return MULUT_EUNSUPPORTED; any other letter MULUT_EMODE; a NULL pointer or a
+ * non-positive size MULUT_EINVAL -- decided before the device is touched, in the order of the functions above. */
+int mulut_ft_wide_stage_forward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                const float *x, int B, int C, int H, int W, float *out, unsigned short *inside, void *stream);
+int mulut_ft_wide_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                 const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
+                                 float *const *grad_wq, float *grad_x, void *stream);
 
 /* ---- device-side evaluation (not on the inference path) ---------------------------------------------------
  * Y-channel PSNR and SSIM of a super-resolved frame against its ground truth, exactly as the test script scores

@@ -8,6 +8,6 @@ from .lut_io import lut_file_name, load_lut_dict, synthetic_lut  # noqa: F401
 from .engine import MuLUTEngine, MuLUTError  # noqa: F401
 from .interp import FourSimplexInterpFaster  # noqa: F401
 from . import finetune_lut  # noqa: F401
-from .finetune import MuLUTInterval  # noqa: F401
+from .finetune import MuLUTInterval, MuLUTWide  # noqa: F401
 
 __version__ = "0.1.0"

@@ -21,6 +21,7 @@ EXPORTS = [
     "mulut_pipeline_rows", "mulut_halo", "mulut_reserve", "mulut_set_stage_timing", "mulut_last_stage_ms", "mulut_last_kernel_ms",
     "mulut_set_tuning", "mulut_kernel_name", "mulut_ft_stage_forward", "mulut_ft_stage_backward", "mulut_ft_quantize", "mulut_ft_quantize_backward",
     "mulut_ft_stage_forward_mask", "mulut_ft_stage_backward_mask", "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward",
+    "mulut_ft_wide_stage_forward", "mulut_ft_wide_stage_backward",
     "mulut_eval_ws_doubles", "mulut_eval_y", "mulut_last_detail_counters", "mulut_debug_read",
 ]
 
@@ -173,6 +174,8 @@ def load(path=None):
     L.mulut_ft_stage_backward_mask.argtypes = [i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p]
     L.mulut_ft_interval_stage_forward.argtypes = [i, i, p, c_char_p, i, i, p, i, i, i, i, p, p, p]
     L.mulut_ft_interval_stage_backward.argtypes = [i, i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p]
+    L.mulut_ft_wide_stage_forward.argtypes = [i, i, p, c_char_p, i, i, p, i, i, i, i, p, p, p]
+    L.mulut_ft_wide_stage_backward.argtypes = [i, i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p]
     L.mulut_kernel_name.restype = c_char_p
     L.mulut_ft_quantize.argtypes = [i, p, p, i, ctypes.c_longlong, p]
     L.mulut_ft_quantize_backward.argtypes = [i, p, p, i, ctypes.c_longlong, p]
@@ -185,7 +188,8 @@ def load(path=None):
                  "mulut_pipeline", "mulut_pipeline_rows", "mulut_halo", "mulut_reserve", "mulut_set_stage_timing",
                  "mulut_last_stage_ms", "mulut_last_kernel_ms", "mulut_set_tuning", "mulut_ft_stage_forward", "mulut_ft_stage_backward",
                  "mulut_ft_quantize", "mulut_ft_quantize_backward", "mulut_ft_stage_forward_mask", "mulut_ft_stage_backward_mask",
-                 "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward"):
+                 "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward", "mulut_ft_wide_stage_forward",
+                 "mulut_ft_wide_stage_backward"):
         getattr(L, name).restype = i
     _libs[path] = L
     return L

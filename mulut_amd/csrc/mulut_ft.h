@@ -109,10 +109,12 @@ __device__ __forceinline__ int eo_of_elem(int r, int e) {      // block position
 
 // Argument checks of every fine-tuning entry point, decided before the device is touched; their order -- and so which MULUT_E* code a
 // bad call gets -- is part of the ABI (include/mulut.h).  need_mask: the entry point cannot do without `inside`; interval_ok: the
-// caller's own verdict on its interval argument (entry points without one pass true).  Args: FtArgs, or FtIvArgs of mulut_ft_interval.hip.
+// caller's own verdict on its interval argument (entry points without one pass true); max_reach: the largest pattern reach the entry
+// point accepts, i.e. the largest HALO its backward kernels are instantiated for (2: s, d, y; 3: e, h, o as well).
+// Args: FtArgs, or FtIvArgs of mulut_ft_interval.hip.
 template <class Args>
 static inline int ft_fill(Args &a, bool interval_ok, const float *const *weights, float *const *grad_wq, const char *modes, int is_last, int u,
-                   const float *x, const uint16_t *inside, bool need_mask, int B, int C, int H, int W) {
+                   const float *x, const uint16_t *inside, bool need_mask, int max_reach, int B, int C, int H, int W) {
     if (!weights || !modes || !x || (need_mask && !inside) || B <= 0 || C <= 0 || H <= 0 || W <= 0) return MULUT_EINVAL;
     if (!interval_ok) return MULUT_EUNSUPPORTED;
     const size_t M = strlen(modes);
@@ -120,8 +122,8 @@ static inline int ft_fill(Args &a, bool interval_ok, const float *const *weights
     memset(&a, 0, sizeof(a));
     for (size_t m = 0; m < M; ++m) {
         int di[3], dj[3];
-        // the input-gradient tiles stage a 2-pixel halo: the 4 x 4 patterns e, h, o (reach 3) are not fine-tuned
-        if (!pattern_offsets(modes[m], di, dj) || pattern_reach(modes[m]) > 2) return MULUT_EMODE;
+        // the input-gradient tiles of the backward kernels stage a halo of HALO pixels: a pattern must not reach beyond the one launched
+        if (!pattern_offsets(modes[m], di, dj) || pattern_reach(modes[m]) > max_reach) return MULUT_EMODE;
         if (!weights[m] || (grad_wq && !grad_wq[m])) return MULUT_EINVAL;
         a.w[m] = weights[m];
         a.gw[m] = grad_wq ? grad_wq[m] : nullptr;
@@ -135,6 +137,23 @@ static inline int ft_fill(Args &a, bool interval_ok, const float *const *weights
     a.B = B; a.C = C; a.H = H; a.W = W; a.u = u; a.M = (int)M; a.is_last = is_last ? 1 : 0;
     return MULUT_OK;
 }
+
+// The halo a filled argument struct needs: the largest key offset of its modes, at least 2 (the s, d, y instances)
+template <class Args>
+static inline int ft_halo(const Args &a) {
+    int r = 2;
+    for (int m = 0; m < a.M; ++m)
+        for (int k = 0; k < 3; ++k) r = imax(r, imax(a.di[m][k], a.dj[m][k]));
+    return r;
+}
+
+// Interval 4 of mulut_ft_wide_stage_forward / _backward (defined in mulut_ft.hip next to the kernels; the entry points themselves are
+// in mulut_ft_interval.hip).  The arguments have passed ft_fill there; these fill an FtArgs and launch HALO = 3, or HALO = 2 for a
+// list of s, d, y alone.
+int ft_wide4_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x, int B, int C, int H, int W,
+                     float *out, uint16_t *inside, void *stream);
+int ft_wide4_backward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x, const float *grad_out,
+                      const uint16_t *inside, int B, int C, int H, int W, float *const *grad_wq, float *grad_x, void *stream);
 #endif  // __HIPCC__
 
 }  // namespace mulut

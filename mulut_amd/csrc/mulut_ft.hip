@@ -195,9 +195,13 @@ __device__ __forceinline__ void ft_site_g(const FtArgs &a, const float *plane, l
 //   u == 1: one float per item: items inside the tube (991 rows, the ones smooth content uses) are summed into a
 //           per-workgroup LDS copy of the tube band with ds_add_f32 and flushed once per workgroup as contiguous
 //           atomics; items outside it go to global memory directly.
+// HALO (2 or 3): the pixels the tiles of the input gradient stage around their sites, i.e. the largest key offset of the stage's
+// patterns -- 2 for s, d, y, 3 with one of e, h, o in the list.  A compile-time constant: the instances of HALO = 2 are the kernels
+// as they were before the 4 x 4 patterns, instruction for instruction (tools/asm_compare.py).
 constexpr int kFtGxTile = 1024;        // floats of a wave's input-gradient tile (ft_stage_bwd)
-template <int U>
+template <int U, int HALO>
 __global__ void __launch_bounds__(256) ft_stage_bwd(FtArgs a) {
+    static_assert(HALO == 2 || HALO == 3, "halo of the input-gradient tile");
     constexpr int EL = U * U, EPL = EL <= 1 ? 1 : EL <= 4 ? 4 : 16, NT = 256;
     __shared__ float s_g[NT][EL + 1];
     __shared__ int s_idx[5][NT];
@@ -214,21 +218,22 @@ __global__ void __launch_bounds__(256) ft_stage_bwd(FtArgs a) {
     float *gplane = a.gx + bc * a.H * a.W;
     // The input gradient: a pass gives d/d f of each key to that key's pixel.  The site's own pixel (key a) is summed in a register; for
     // key b, c or d the target is the site's pixel plus an offset that is the same for every site of the pass, so the 64 consecutive
-    // sites of a WAVE hit 64 different positions of the wave's private tile -- the rows its sites lie in plus two on either side, each
+    // sites of a WAVE hit 64 different positions of the wave's private tile -- the rows its sites lie in plus HALO on either side, each
     // plane with its own halo rows and columns (unclamped coordinates: replicate padding is applied when the tile is folded onto the
     // image at the end): a plain LDS read + add + write per key, no atomic (36 LDS float adds per site before, 83 % of this kernel's
-    // launch with the LDS pipeline busy).  When the tile does not fit (crops wider than ~140) the adds go to memory.
+    // launch with the LDS pipeline busy).  When the tile does not fit (crops wider than ~140; a single row of 64 sites needs
+    // (rows + 2 HALO) * (W + 2 HALO) <= 1024 floats) the adds go to memory.
     const int lane = (int)threadIdx.x & 63;
     float *tile = s_gxt[threadIdx.x >> 6];
-    const int PWd = a.W + 4, PHt = a.H + 4;
-    auto padded_row = [&](long long R) { return R + 4 * (R / a.H) + 2; };      // stacked image row (plane * H + y) -> row of the padded stack
+    const int PWd = a.W + 2 * HALO, PHt = a.H + 2 * HALO;
+    auto padded_row = [&](long long R) { return R + 2 * HALO * (R / a.H) + HALO; };      // stacked image row (plane * H + y) -> row of the padded stack
     const long long w0 = (long long)blockIdx.x * NT + (threadIdx.x & ~63u);
     const long long R0 = (w0 < nsite ? w0 : nsite - 1) / a.W, R1 = (w0 + 63 < nsite ? w0 + 63 : nsite - 1) / a.W;
-    const long long pr0 = padded_row(R0) - 2;
-    const long long t_rows = padded_row(R1) + 2 - pr0 + 1;
+    const long long pr0 = padded_row(R0) - HALO;
+    const long long t_rows = padded_row(R1) + HALO - pr0 + 1;
     const int t_n = t_rows * PWd <= kFtGxTile ? (int)(t_rows * PWd) : 0;      // 0: does not fit
     for (int i = lane; i < t_n; i += 64) tile[i] = 0.0f;                      // (wave-private, and LDS serves a wave in order: no barrier)
-    const int t_own = (int)(padded_row(bc * a.H + y) - pr0) * PWd + x + 2;
+    const int t_own = (int)(padded_row(bc * a.H + y) - pr0) * PWd + x + HALO;
     if constexpr (U == 1)
         for (int i = threadIdx.x; i < a.M * kTubeSlots; i += NT) s_band[i] = 0.0f;
     float g[EL];
@@ -322,7 +327,7 @@ __global__ void __launch_bounds__(256) ft_stage_bwd(FtArgs a) {
             const float v = tile[i];
             if (v == 0.0f) continue;
             const long long pr = pr0 + i / PWd;
-            const int cx = i % PWd - 2, yy = (int)(pr % PHt) - 2;
+            const int cx = i % PWd - HALO, yy = (int)(pr % PHt) - HALO;
             const long long pl = pr / PHt;
             if (pl < (long long)a.B * a.C) atomicAdd(&a.gx[(pl * a.H + imin(imax(yy, 0), a.H - 1)) * a.W + imin(imax(cx, 0), a.W - 1)], v);
         }
@@ -364,23 +369,31 @@ __global__ void __launch_bounds__(256) ft_stage_bwd(FtArgs a) {
 // the entries (one broadcast read each).  No barrier inside a mode.
 // The INPUT gradient: a pass gives d/d f of each key to that key's pixel.  The site's own pixel (key a) is summed in a register; for
 // key b, c or d the target is the site's pixel plus an offset that is the same for every site of the pass, so the 16 sites of a
-// group hit 16 DIFFERENT positions of the group's 8 x 8 tile (its 4 x 4 block and a halo of two, unclamped): a plain LDS read + add
+// group hit 16 DIFFERENT positions of the group's tile (its 4 x 4 block and a halo of HALO, unclamped: 8 x 8 floats, 10 x 10 at
+// HALO = 3): a plain LDS read + add
 // + write per key, no atomic.  The tile goes to memory once, at the end, folded onto the image (replicate padding: a position
 // outside the plane belongs to the border pixel) -- 4 memory-side atomics per site instead of 37.
 // LDS: [ band gradient 1041 x 16 f32 ][ g of the sites, 17 floats each ][ caches: 16 x 16 f32 per group ][ tags: 16 per group ]
-//      [ input-gradient tiles: 8 x 8 f32 per group ]
+//      [ input-gradient tiles: (4 + 2 HALO)^2 f32 per group ]
 constexpr int kFtB4Sites = 512, kFtB4Groups = kFtB4Sites / 16;
-constexpr int kFtB4Lds = kTubeSlots * 16 * 4 + kFtB4Sites * 17 * 4 + kFtB4Groups * 16 * 16 * 4 + kFtB4Groups * 16 * 4 + kFtB4Groups * 64 * 4;
-static_assert(kFtB4Lds <= 160 * 1024, "ft_stage_bwd4: LDS");
+constexpr int ft_b4_tile(int halo) { return (4 + 2 * halo) * (4 + 2 * halo); }      // floats of a group's input-gradient tile
+constexpr int ft_b4_lds(int halo) {
+    return kTubeSlots * 16 * 4 + kFtB4Sites * 17 * 4 + kFtB4Groups * 16 * 16 * 4 + kFtB4Groups * 16 * 4 + kFtB4Groups * ft_b4_tile(halo) * 4;
+}
+constexpr int kFtB4Lds = ft_b4_lds(2);
+static_assert(kFtB4Lds == 144448 && kFtB4Lds <= 160 * 1024, "ft_stage_bwd4: LDS");
+static_assert(ft_b4_lds(3) == 149056 && ft_b4_lds(3) <= 160 * 1024, "ft_stage_bwd4, HALO = 3: LDS");      // one workgroup per CU either way
 
+template <int HALO>
 __global__ void __launch_bounds__(kFtB4Sites) ft_stage_bwd4(FtArgs a) {
-    constexpr int U = 4, EL = 16, NT = kFtB4Sites, NG = kFtB4Groups;
+    static_assert(HALO == 2 || HALO == 3, "halo of the input-gradient tile");
+    constexpr int U = 4, EL = 16, NT = kFtB4Sites, NG = kFtB4Groups, TW = 4 + 2 * HALO, TN = ft_b4_tile(HALO);
     extern __shared__ __attribute__((aligned(16))) uint8_t ft_smem[];
     float *s_band = (float *)ft_smem;
     float (*s_g)[17] = (float (*)[17])(ft_smem + kTubeSlots * 16 * 4);
     float *s_cache = (float *)(ft_smem + kTubeSlots * 16 * 4 + NT * 17 * 4);
     int *s_tag = (int *)(s_cache + NG * 256);             // [NG][16]
-    float *s_gxt = (float *)(s_tag + NG * 16);            // [NG][8][8]
+    float *s_gxt = (float *)(s_tag + NG * 16);            // [NG][TW][TW]
     // a group's 16 sites are a 4x4 block of one plane (lane = 4 * row + column): neighbours in both directions share MSB cells, so
     // the group's cache sees fewer cell changes than with 16 sites along a row; lanes beyond the plane shadow its last site
     const int e = (int)threadIdx.x & 15, grp = (int)threadIdx.x >> 4, first = grp * 16;
@@ -394,10 +407,11 @@ __global__ void __launch_bounds__(kFtB4Sites) ft_stage_bwd4(FtArgs a) {
     const int y = imin(y0, a.H - 1), x = imin(x0, a.W - 1);
     const float *plane = a.x + bc * a.H * a.W;
     float *gplane = a.gx + bc * a.H * a.W;
-    float *gxt = s_gxt + grp * 64;
+    float *gxt = s_gxt + grp * TN;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) gxt[e + 16 * i] = 0.0f;      // (only this group touches its tile, and LDS serves a wave in order)
-    float *gxt_own = gxt + (2 + (e >> 2)) * 8 + 2 + (e & 3);
+    for (int i = 0; i < (TN + 15) / 16; ++i)
+        if (TN % 16 == 0 || e + 16 * i < TN) gxt[e + 16 * i] = 0.0f;      // (only this group touches its tile, and LDS serves a wave in order)
+    float *gxt_own = gxt + (HALO + (e >> 2)) * TW + HALO + (e & 3);
     ft_site_g<U>(a, plane, bc, y, x, valid, [&](int eo, float v) { s_g[threadIdx.x][eo] = v; });
     float *cache = s_cache + grp * 256;      // [16 entries][16 elements]
     int *tags = s_tag + grp * 16;            // slot held by entry c, -1: none
@@ -491,7 +505,7 @@ __global__ void __launch_bounds__(kFtB4Sites) ft_stage_bwd4(FtArgs a) {
                 else {
                     int dy, dx;
                     sample_offset(r, di[k - 1], dj[k - 1], dy, dx);
-                    float *t = gxt_own + dy * 8 + dx;
+                    float *t = gxt_own + dy * TW + dx;
                     *t = *t + dk;
                 }
 #endif
@@ -512,35 +526,47 @@ __global__ void __launch_bounds__(kFtB4Sites) ft_stage_bwd4(FtArgs a) {
         }
         __syncthreads();
     }
-    // the tile onto the image: position (ty, tx) is pixel (4 by - 2 + ty, 4 bx - 2 + tx) clamped into the plane
+    // the tile onto the image: position (ty, tx) is pixel (4 by - HALO + ty, 4 bx - HALO + tx) clamped into the plane
     *gxt_own += valid ? own : 0.0f;
     if (block < nblock) {
-        const int ty0 = (brem / bw) * 4 - 2, tx0 = (brem % bw) * 4 - 2;
+        const int ty0 = (brem / bw) * 4 - HALO, tx0 = (brem % bw) * 4 - HALO;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < (TN + 15) / 16; ++i) {
             const int q = e + 16 * i;
+            if (TN % 16 != 0 && q >= TN) continue;
             const float v = gxt[q];
-            if (v != 0.0f) atomicAdd(&gplane[imin(imax(ty0 + (q >> 3), 0), a.H - 1) * a.W + imin(imax(tx0 + (q & 7), 0), a.W - 1)], v);
+            // (row and column of q written as shift and mask where TW is 8: from q / TW and q % TW the compiler no longer hoists the column's
+            // clamp out of the unrolled loop, and the HALO = 2 instance would not be the kernel it was)
+            if (v != 0.0f)
+                atomicAdd(&gplane[imin(imax(ty0 + (HALO == 2 ? q >> 3 : q / TW), 0), a.H - 1) * a.W + imin(imax(tx0 + (HALO == 2 ? q & 7 : q % TW), 0), a.W - 1)], v);
         }
     }
 }
 
-template <int U>
+// HALO: 2 for the lists of s, d, y, 3 when the list holds one of e, h, o (ft_halo()); the forward kernels read their keys through
+// clamped gathers with run-time offsets and have no halo
+template <int U, int HALO>
 static hipError_t launch_ft(const FtArgs &a, bool backward, hipStream_t st) {
     const long long nsite = (long long)a.B * a.C * a.H * a.W;
     const long long nb = (nsite + 255) / 256;
     if (nb <= 0 || nb > 0x7fffffffLL) return hipErrorInvalidValue;
     if (backward && U == 4) {
         {
-            const hipError_t e = mulut::raise_lds_limit((const void *)ft_stage_bwd4, 160 * 1024);
+            const hipError_t e = mulut::raise_lds_limit((const void *)ft_stage_bwd4<HALO>, 160 * 1024);
             if (e != hipSuccess) return e;
         }
         const long long nblock4 = (long long)a.B * a.C * ((a.H + 3) / 4) * ((a.W + 3) / 4);      // 4x4 site blocks, one per 16-lane group
         const long long nb4 = (nblock4 + kFtB4Groups - 1) / kFtB4Groups;
-        hipLaunchKernelGGL(ft_stage_bwd4, dim3((unsigned)nb4), dim3(kFtB4Sites), (size_t)kFtB4Lds, st, a);
-    } else if (backward) hipLaunchKernelGGL(ft_stage_bwd<U>, dim3((unsigned)nb), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(ft_stage_bwd4<HALO>, dim3((unsigned)nb4), dim3(kFtB4Sites), (size_t)ft_b4_lds(HALO), st, a);
+    } else if (backward) hipLaunchKernelGGL((ft_stage_bwd<U, HALO>), dim3((unsigned)nb), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(ft_stage_fwd<U>, dim3((unsigned)nb), dim3(256), 0, st, a);
     return hipGetLastError();
+}
+
+template <int HALO>
+static hipError_t launch_ft_u(const FtArgs &a, bool backward, hipStream_t st) {
+    return a.u == 1 ? launch_ft<1, HALO>(a, backward, st) : a.u == 2 ? launch_ft<2, HALO>(a, backward, st)
+         : a.u == 3 ? launch_ft<3, HALO>(a, backward, st) : launch_ft<4, HALO>(a, backward, st);
 }
 
 // The module's quantisation step and its backward (sr/model.py:74-76: weight = clamp(round_func(weight * 127), -127, 127), round_func a
@@ -593,56 +619,65 @@ int mulut_ft_quantize_backward(int device, const float *const *weights, float *c
     return ft_quantize(device, weights, grad, M, n, true, stream);
 }
 
+// max_reach: 2 for the entry points of this file (s, d, y), 3 for mulut_ft_wide_stage_* (mulut_ft_interval.hip)
 static int ft_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
-                      int B, int C, int H, int W, float *out, uint16_t *inside, void *stream) {
+                      int B, int C, int H, int W, float *out, uint16_t *inside, int max_reach, void *stream) {
     FtArgs a;
-    int rc = ft_fill(a, true, weights_q, nullptr, modes, is_last, u, x, inside, false, B, C, H, W);
+    int rc = ft_fill(a, true, weights_q, nullptr, modes, is_last, u, x, inside, false, max_reach, B, C, H, W);
     if (rc) return rc;
     if (!out) return MULUT_EINVAL;
     a.out = out;
     if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    hipError_t e = u == 1 ? launch_ft<1>(a, false, (hipStream_t)stream) : u == 2 ? launch_ft<2>(a, false, (hipStream_t)stream)
-                 : u == 3 ? launch_ft<3>(a, false, (hipStream_t)stream) : launch_ft<4>(a, false, (hipStream_t)stream);
+    const hipError_t e = launch_ft_u<2>(a, false, (hipStream_t)stream);      // (the forward kernels have no halo)
     return e == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }
 
 int mulut_ft_stage_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                            int B, int C, int H, int W, float *out, void *stream) {
-    return ft_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, nullptr, stream);
+    return ft_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, nullptr, 2, stream);
 }
 
 int mulut_ft_stage_forward_mask(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                                 int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
     if (!inside) return MULUT_EINVAL;
-    return ft_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, stream);
+    return ft_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, 2, stream);
 }
 
 static int ft_backward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                        const float *grad_out, const uint16_t *inside, int B, int C, int H, int W, float *const *grad_wq, float *grad_x,
-                       void *stream) {
+                       int max_reach, void *stream) {
     FtArgs a;
-    int rc = ft_fill(a, true, weights_q, grad_wq, modes, is_last, u, x, inside, false, B, C, H, W);
+    int rc = ft_fill(a, true, weights_q, grad_wq, modes, is_last, u, x, inside, false, max_reach, B, C, H, W);
     if (rc) return rc;
     if (!grad_out || !grad_wq || !grad_x) return MULUT_EINVAL;
     a.gout = grad_out;
     a.gx = grad_x;
     if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    hipError_t e = u == 1 ? launch_ft<1>(a, true, (hipStream_t)stream) : u == 2 ? launch_ft<2>(a, true, (hipStream_t)stream)
-                 : u == 3 ? launch_ft<3>(a, true, (hipStream_t)stream) : launch_ft<4>(a, true, (hipStream_t)stream);
+    const hipError_t e = ft_halo(a) > 2 ? launch_ft_u<3>(a, true, (hipStream_t)stream) : launch_ft_u<2>(a, true, (hipStream_t)stream);
     return e == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }
 
 int mulut_ft_stage_backward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                             const float *grad_out, int B, int C, int H, int W, float *const *grad_wq, float *grad_x,
                             void *stream) {
-    return ft_backward(device, weights_q, modes, is_last, u, x, grad_out, nullptr, B, C, H, W, grad_wq, grad_x, stream);
+    return ft_backward(device, weights_q, modes, is_last, u, x, grad_out, nullptr, B, C, H, W, grad_wq, grad_x, 2, stream);
 }
 
 int mulut_ft_stage_backward_mask(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                                  const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
                                  float *const *grad_wq, float *grad_x, void *stream) {
     if (!inside) return MULUT_EINVAL;
-    return ft_backward(device, weights_q, modes, is_last, u, x, grad_out, inside, B, C, H, W, grad_wq, grad_x, stream);
+    return ft_backward(device, weights_q, modes, is_last, u, x, grad_out, inside, B, C, H, W, grad_wq, grad_x, 2, stream);
 }
 
 }  // extern "C"
+
+// interval 4 of mulut_ft_wide_stage_* (mulut_ft.h)
+int mulut::ft_wide4_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x, int B, int C, int H,
+                            int W, float *out, uint16_t *inside, void *stream) {
+    return ft_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, 3, stream);
+}
+int mulut::ft_wide4_backward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x, const float *grad_out,
+                             const uint16_t *inside, int B, int C, int H, int W, float *const *grad_wq, float *grad_x, void *stream) {
+    return ft_backward(device, weights_q, modes, is_last, u, x, grad_out, inside, B, C, H, W, grad_wq, grad_x, 3, stream);
+}

@@ -11,12 +11,14 @@
 // is an LDS image wherever rows * u*u floats fit kFtIvLdsBudget -- all of interval 6, interval 5 at u = 1 and 2 -- and the
 // forward stages the stage's tables themselves into LDS under the same rule.
 //   ft_interval_stage_fwd<IV, U, LDS>   one site per thread, persistent workgroups when the tables are staged (LDS)
-//   ft_interval_stage_bwd<IV, U, RES>   one site per thread (u = 1, 2, 3).  Modes are walked one at a time, so one image serves
+//   ft_interval_stage_bwd<IV, U, RES, HALO>
+//                                       one site per thread (u = 1, 2, 3).  Modes are walked one at a time, so one image serves
 //                                       any number of modes.  Per vertex the lanes of a 16-lane row that share the row leader's
 //                                       table row are summed by DPP and added once, row-wide (lane l adds element l); the
 //                                       others add on their own.  RES: into the image, flushed once per workgroup and mode as
 //                                       contiguous memory-side atomics; else (interval 5, u = 3) straight to memory.
-//   ft_interval_stage_bwd4<IV, RES>     u = 4: the design of ft_stage_bwd4 -- 16 lanes (= row elements) own a 4 x 4 block of
+//   ft_interval_stage_bwd4<IV, RES, HALO>
+//                                       u = 4: the design of ft_stage_bwd4 -- 16 lanes (= row elements) own a 4 x 4 block of
 //                                       sites and a private 16-entry cache of gradient rows, read + add + write, no atomic -- with
 //                                       the cache keyed by the CORNER of the MSB cell (ft_iv_corner): cells are 32 / 64 grey
 //                                       levels wide, so a block of smooth content stays in one cell and its 16 corners never
@@ -27,7 +29,8 @@
 //                                       (Measured without the band, every eviction a memory-side atomic: 2.28 ms per launch on
 //                                       config 4's batch against 1.24 ms at interval 6 -- the hot rows serialise.)
 // Both backward kernels run persistent workgroups over several tiles of sites: the image is zeroed and flushed once per
-// workgroup and mode, not once per 256 sites.
+// workgroup and mode, not once per 256 sites.  HALO (2 or 3) is the halo of their input-gradient tiles, as in mulut_ft.hip: 2 for
+// lists of s, d, y, 3 with one of e, h, o in the list; the HALO = 2 instances are the kernels as they were before the 4 x 4 patterns.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -151,12 +154,13 @@ constexpr int kFtIvNT = 256;           // threads = sites of a tile (ft_interval
 constexpr int kFtIvGxTile = 1024;      // floats of a wave's input-gradient tile
 template <int U> constexpr int ftiv_bwd_lds(int image_floats) { return (image_floats + (kFtIvNT / 64) * kFtIvGxTile + kFtIvNT * (U * U + 1)) * 4; }
 
-// One site per thread.  The input gradient uses the wave-private padded tile of ft_stage_bwd (the offsets of s, d, y are the
-// same <= 2 pixels at every interval): a pass gives d/d f of each key to that key's pixel; the site's own pixel is summed in a
+// One site per thread.  The input gradient uses the wave-private padded tile of ft_stage_bwd (the key offsets of a pattern are the
+// same <= HALO pixels at every interval): a pass gives d/d f of each key to that key's pixel; the site's own pixel is summed in a
 // register, keys b, c, d hit 64 different positions of the wave's tile -- a plain LDS read + add + write, folded onto the image
 // (replicate padding) at the end of the tile; crops too wide for the tile add to memory.
-template <int IV, int U, bool RES>
+template <int IV, int U, bool RES, int HALO>
 __global__ void __launch_bounds__(kFtIvNT) ft_interval_stage_bwd(FtIvArgs a) {
+    static_assert(HALO == 2 || HALO == 3, "halo of the input-gradient tile");
     using G = IvGeom<IV>;
     constexpr int EL = U * U, NT = kFtIvNT, IMG = RES ? G::rows * EL : 0;
     extern __shared__ __attribute__((aligned(16))) float ftiv_smem[];
@@ -168,8 +172,8 @@ __global__ void __launch_bounds__(kFtIvNT) ft_interval_stage_bwd(FtIvArgs a) {
     const long long t0 = (long long)blockIdx.x * a.tiles_per_wg, t1 = t0 + a.tiles_per_wg < ntile ? t0 + a.tiles_per_wg : ntile;
     const int lane = (int)threadIdx.x & 63, l16 = (int)threadIdx.x & 15;
     float *tile = s_gxt + (threadIdx.x >> 6) * kFtIvGxTile;
-    const int PWd = a.W + 4, PHt = a.H + 4;
-    auto padded_row = [&](long long R) { return R + 4 * (R / a.H) + 2; };      // stacked image row (plane * H + y) -> row of the padded stack
+    const int PWd = a.W + 2 * HALO, PHt = a.H + 2 * HALO;
+    auto padded_row = [&](long long R) { return R + 2 * HALO * (R / a.H) + HALO; };      // stacked image row (plane * H + y) -> row of the padded stack
     for (int m = 0; m < a.M; ++m) {
         const float *tab = a.w[m];
         float *gtab = a.gw[m];
@@ -188,11 +192,11 @@ __global__ void __launch_bounds__(kFtIvNT) ft_interval_stage_bwd(FtIvArgs a) {
             float *gplane = a.gx + bc * a.H * a.W;
             const long long w0 = t * NT + (threadIdx.x & ~63u);
             const long long R0 = (w0 < nsite ? w0 : nsite - 1) / a.W, R1 = (w0 + 63 < nsite ? w0 + 63 : nsite - 1) / a.W;
-            const long long pr0 = padded_row(R0) - 2;
-            const long long t_rows = padded_row(R1) + 2 - pr0 + 1;
+            const long long pr0 = padded_row(R0) - HALO;
+            const long long t_rows = padded_row(R1) + HALO - pr0 + 1;
             const int t_n = t_rows * PWd <= kFtIvGxTile ? (int)(t_rows * PWd) : 0;      // 0: does not fit
             for (int i = lane; i < t_n; i += 64) tile[i] = 0.0f;                        // (wave-private, and LDS serves a wave in order: no barrier)
-            const int t_own = (int)(padded_row(bc * a.H + y) - pr0) * PWd + x + 2;
+            const int t_own = (int)(padded_row(bc * a.H + y) - pr0) * PWd + x + HALO;
             // (own row of s_g only: written and read by this thread)
             ftiv_site_g<U>(a, bc, y, x, valid, [&](int eo, float v) { s_g[threadIdx.x][eo] = v; });
             float own = 0.0f;
@@ -267,7 +271,7 @@ __global__ void __launch_bounds__(kFtIvNT) ft_interval_stage_bwd(FtIvArgs a) {
                     const float v = tile[i];
                     if (v == 0.0f) continue;
                     const long long pr = pr0 + i / PWd;
-                    const int cx = i % PWd - 2, yy = (int)(pr % PHt) - 2;
+                    const int cx = i % PWd - HALO, yy = (int)(pr % PHt) - HALO;
                     const long long pl = pr / PHt;
                     if (pl < (long long)a.B * a.C) atomicAdd(&a.gx[(pl * a.H + imin(imax(yy, 0), a.H - 1)) * a.W + imin(imax(cx, 0), a.W - 1)], v);
                 }
@@ -287,12 +291,15 @@ __global__ void __launch_bounds__(kFtIvNT) ft_interval_stage_bwd(FtIvArgs a) {
 }
 
 // u = 4: 16 lanes per table row.  LDS: [ image rows x 16 f32 (RES) or band 121 x 16 f32 ][ g of the sites, 17 floats each ][ caches: 16 x 16 f32 per group ]
-//        [ tags: 16 per group ][ input-gradient tiles: 8 x 8 f32 per group ]
+//        [ tags: 16 per group ][ input-gradient tiles: (4 + 2 HALO)^2 f32 per group ]
 constexpr int kFtIvB4Sites = 512, kFtIvB4Groups = kFtIvB4Sites / 16;
-constexpr int ftiv_bwd4_lds(int image_floats) {
-    return image_floats * 4 + kFtIvB4Sites * 17 * 4 + kFtIvB4Groups * 16 * 16 * 4 + kFtIvB4Groups * 16 * 4 + kFtIvB4Groups * 64 * 4;
+constexpr int ftiv_b4_tile(int halo) { return (4 + 2 * halo) * (4 + 2 * halo); }      // floats of a group's input-gradient tile
+constexpr int ftiv_bwd4_lds(int image_floats, int halo) {
+    return image_floats * 4 + kFtIvB4Sites * 17 * 4 + kFtIvB4Groups * 16 * 16 * 4 + kFtIvB4Groups * 16 * 4 + kFtIvB4Groups * ftiv_b4_tile(halo) * 4;
 }
-static_assert(ftiv_bwd4_lds(IvGeom<6>::rows * 16) <= 160 * 1024 && kFtIvLdsBudget + ftiv_bwd_lds<2>(0) <= 160 * 1024, "LDS");
+static_assert(ftiv_bwd4_lds(IvGeom<6>::rows * 16, 2) <= 160 * 1024 && kFtIvLdsBudget + ftiv_bwd_lds<2>(0) <= 160 * 1024, "LDS");
+static_assert(ftiv_bwd4_lds(IvGeom<6>::rows * 16, 3) == ftiv_bwd4_lds(IvGeom<6>::rows * 16, 2) + 32 * 144 &&
+              ftiv_bwd4_lds(IvGeom<6>::rows * 16, 3) <= 160 * 1024, "LDS, HALO = 3");
 
 // The band of a table that does not fit: the rows whose four MSBs span at most one step -- (L - 1) * 15 + 1 of them, 121 at
 // interval 5, the rows a batch of natural crops touches (smooth content lives next to the diagonal of the grid).  Slot of a row:
@@ -313,24 +320,26 @@ __device__ __forceinline__ int ftiv_band_row(int slot) {
     return n * G::all + ((mask >> 3) & 1) * G::sA + ((mask >> 2) & 1) * G::sB + ((mask >> 1) & 1) * G::sC + (mask & 1);
 }
 
-template <int IV, bool RES>
+template <int IV, bool RES, int HALO>
 __global__ void __launch_bounds__(kFtIvB4Sites) ft_interval_stage_bwd4(FtIvArgs a) {
+    static_assert(HALO == 2 || HALO == 3, "halo of the input-gradient tile");
     using G = IvGeom<IV>;
     constexpr int U = 4, EL = 16, NT = kFtIvB4Sites, NG = kFtIvB4Groups, IMG = (RES ? G::rows : kFtIvBandRows<IV>) * EL;
+    constexpr int TW = 4 + 2 * HALO, TN = ftiv_b4_tile(HALO);
     extern __shared__ __attribute__((aligned(16))) float ftiv_smem[];
     float *s_img = ftiv_smem;
     float (*s_g)[17] = (float (*)[17])(ftiv_smem + IMG);
     float *s_cache = ftiv_smem + IMG + NT * 17;
     int *s_tag = (int *)(s_cache + NG * 256);             // [NG][16]
-    float *s_gxt = (float *)(s_tag + NG * 16);            // [NG][8][8]
+    float *s_gxt = (float *)(s_tag + NG * 16);            // [NG][TW][TW]
     // a group's 16 sites are a 4x4 block of one plane (lane = 4 * row + column); lanes beyond the plane shadow its last site
     const int e = (int)threadIdx.x & 15, grp = (int)threadIdx.x >> 4, first = grp * 16;
     const int bw = (a.W + 3) / 4, bh = (a.H + 3) / 4;
     const long long nblock = (long long)a.B * a.C * bh * bw;
     const long long ntile = (nblock + NG - 1) / NG;
     const long long t0 = (long long)blockIdx.x * a.tiles_per_wg, t1 = t0 + a.tiles_per_wg < ntile ? t0 + a.tiles_per_wg : ntile;
-    float *gxt = s_gxt + grp * 64;
-    float *gxt_own = gxt + (2 + (e >> 2)) * 8 + 2 + (e & 3);
+    float *gxt = s_gxt + grp * TN;
+    float *gxt_own = gxt + (HALO + (e >> 2)) * TW + HALO + (e & 3);
     float *cache = s_cache + grp * 256;      // [16 corners][16 elements]
     int *tags = s_tag + grp * 16;            // (row << 4 | corner) held by the entry of that corner, -1: none
     // an entry's sum leaves the cache: into the image; without one into the band, or, a row outside it, to memory as one 64-byte segment
@@ -360,7 +369,8 @@ __global__ void __launch_bounds__(kFtIvB4Sites) ft_interval_stage_bwd4(FtIvArgs 
             const float *plane = a.x + bc * a.H * a.W;
             float *gplane = a.gx + bc * a.H * a.W;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) gxt[e + 16 * i] = 0.0f;      // (only this group touches its tile and its rows of s_g, and LDS serves a wave in order)
+            for (int i = 0; i < (TN + 15) / 16; ++i)
+                if (TN % 16 == 0 || e + 16 * i < TN) gxt[e + 16 * i] = 0.0f;      // (only this group touches its tile and its rows of s_g, and LDS serves a wave in order)
             ftiv_site_g<U>(a, bc, y, x, valid, [&](int eo, float v) { s_g[threadIdx.x][eo] = v; });
             float own = 0.0f;
 #pragma unroll 1
@@ -434,20 +444,24 @@ __global__ void __launch_bounds__(kFtIvB4Sites) ft_interval_stage_bwd4(FtIvArgs 
                     else {
                         int dy, dx;
                         sample_offset(r, di[k - 1], dj[k - 1], dy, dx);
-                        float *tp = gxt_own + dy * 8 + dx;
+                        float *tp = gxt_own + dy * TW + dx;
                         *tp = *tp + (valid ? dk : 0.0f);
                     }
                 }
             }
-            // the tile onto the image: position (ty, tx) is pixel (4 by - 2 + ty, 4 bx - 2 + tx) clamped into the plane
+            // the tile onto the image: position (ty, tx) is pixel (4 by - HALO + ty, 4 bx - HALO + tx) clamped into the plane
             *gxt_own += valid ? own : 0.0f;
             if (block < nblock) {
-                const int ty0 = (brem / bw) * 4 - 2, tx0 = (brem % bw) * 4 - 2;
+                const int ty0 = (brem / bw) * 4 - HALO, tx0 = (brem % bw) * 4 - HALO;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
+                for (int i = 0; i < (TN + 15) / 16; ++i) {
                     const int q = e + 16 * i;
+                    if (TN % 16 != 0 && q >= TN) continue;
                     const float v = gxt[q];
-                    if (v != 0.0f) atomicAdd(&gplane[imin(imax(ty0 + (q >> 3), 0), a.H - 1) * a.W + imin(imax(tx0 + (q & 7), 0), a.W - 1)], v);
+                    // (row and column of q written as shift and mask where TW is 8: from q / TW and q % TW the compiler no longer hoists the column's
+                    // clamp out of the unrolled loop, and the HALO = 2 instance would not be the kernel it was)
+                    if (v != 0.0f)
+                        atomicAdd(&gplane[imin(imax(ty0 + (HALO == 2 ? q >> 3 : q / TW), 0), a.H - 1) * a.W + imin(imax(tx0 + (HALO == 2 ? q & 7 : q % TW), 0), a.W - 1)], v);
                 }
             }
         }
@@ -498,7 +512,7 @@ static hipError_t launch_ftiv_fwd(const FtIvArgs &a, int num_cus, hipStream_t st
     return hipGetLastError();
 }
 
-template <int IV, int U>
+template <int IV, int U, int HALO>
 static hipError_t launch_ftiv_bwd(FtIvArgs a, int num_cus, hipStream_t st) {
     constexpr int image = IvGeom<IV>::rows * U * U;
     constexpr bool RES = image * 4 <= kFtIvLdsBudget;
@@ -508,7 +522,7 @@ static hipError_t launch_ftiv_bwd(FtIvArgs a, int num_cus, hipStream_t st) {
     if (ntile <= 0 || ntile > 0x7fffffffLL) return hipErrorInvalidValue;
     // a workgroup walks `per` consecutive tiles, so that the image is zeroed and flushed once per that many: of one to four
     // workgroups per slot (a CU holds `fit` of them at a time) the split whose last round wastes least, the coarser one on a tie
-    constexpr int lds_bytes = U == 4 ? ftiv_bwd4_lds(RES ? image : kFtIvBandRows<IV> * 16) : ftiv_bwd_lds<U>(RES ? image : 0);
+    constexpr int lds_bytes = U == 4 ? ftiv_bwd4_lds(RES ? image : kFtIvBandRows<IV> * 16, HALO) : ftiv_bwd_lds<U>(RES ? image : 0);
     constexpr int fit = U == 4 ? 1 : (160 * 1024 / lds_bytes < 8 ? 160 * 1024 / lds_bytes : 8);
     const long long slots = (long long)num_cus * fit;
     long long per = 0, best = 0;
@@ -521,31 +535,43 @@ static hipError_t launch_ftiv_bwd(FtIvArgs a, int num_cus, hipStream_t st) {
     const long long nb = (ntile + per - 1) / per;
     if constexpr (U == 4) {
         constexpr int lds = lds_bytes;
-        const hipError_t e = raise_lds_limit((const void *)ft_interval_stage_bwd4<IV, RES>, lds);
+        const hipError_t e = raise_lds_limit((const void *)ft_interval_stage_bwd4<IV, RES, HALO>, lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ft_interval_stage_bwd4<IV, RES>), dim3((unsigned)nb), dim3(kFtIvB4Sites), (size_t)lds, st, a);
+        hipLaunchKernelGGL((ft_interval_stage_bwd4<IV, RES, HALO>), dim3((unsigned)nb), dim3(kFtIvB4Sites), (size_t)lds, st, a);
     } else {
         constexpr int lds = lds_bytes;
-        const hipError_t e = raise_lds_limit((const void *)ft_interval_stage_bwd<IV, U, RES>, lds);
+        const hipError_t e = raise_lds_limit((const void *)ft_interval_stage_bwd<IV, U, RES, HALO>, lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ft_interval_stage_bwd<IV, U, RES>), dim3((unsigned)nb), dim3(kFtIvNT), (size_t)lds, st, a);
+        hipLaunchKernelGGL((ft_interval_stage_bwd<IV, U, RES, HALO>), dim3((unsigned)nb), dim3(kFtIvNT), (size_t)lds, st, a);
     }
     return hipGetLastError();
 }
 
-template <int IV>
+// HALO: 2 for the lists of s, d, y, 3 when the list holds one of e, h, o (ft_halo()); the forward kernels have no halo
+template <int IV, int HALO>
 static hipError_t launch_ftiv(const FtIvArgs &a, bool backward, int num_cus, hipStream_t st) {
     switch (a.u * 2 + (backward ? 1 : 0)) {
         case 2: return launch_ftiv_fwd<IV, 1>(a, num_cus, st);
-        case 3: return launch_ftiv_bwd<IV, 1>(a, num_cus, st);
+        case 3: return launch_ftiv_bwd<IV, 1, HALO>(a, num_cus, st);
         case 4: return launch_ftiv_fwd<IV, 2>(a, num_cus, st);
-        case 5: return launch_ftiv_bwd<IV, 2>(a, num_cus, st);
+        case 5: return launch_ftiv_bwd<IV, 2, HALO>(a, num_cus, st);
         case 6: return launch_ftiv_fwd<IV, 3>(a, num_cus, st);
-        case 7: return launch_ftiv_bwd<IV, 3>(a, num_cus, st);
+        case 7: return launch_ftiv_bwd<IV, 3, HALO>(a, num_cus, st);
         case 8: return launch_ftiv_fwd<IV, 4>(a, num_cus, st);
-        case 9: return launch_ftiv_bwd<IV, 4>(a, num_cus, st);
+        case 9: return launch_ftiv_bwd<IV, 4, HALO>(a, num_cus, st);
         default: return hipErrorInvalidValue;
     }
+}
+
+// one stage, forward or backward, of a filled FtIvArgs at interval 5 or 6
+static int ftiv_run(FtIvArgs &a, int device, int interval, bool backward, void *stream) {
+    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
+    const int cus = ftiv_num_cus(device);
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    if (backward && ft_halo(a) > 2) e = interval == 5 ? launch_ftiv<5, 3>(a, true, cus, st) : launch_ftiv<6, 3>(a, true, cus, st);
+    else e = interval == 5 ? launch_ftiv<5, 2>(a, backward, cus, st) : launch_ftiv<6, 2>(a, backward, cus, st);
+    return e == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }
 
 }  // namespace mulut
@@ -558,14 +584,11 @@ extern "C" {
 int mulut_ft_interval_stage_forward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
                                     const float *x, int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
     FtIvArgs a;
-    const int rc = ft_fill(a, interval == 5 || interval == 6, weights_q, nullptr, modes, is_last, u, x, inside, true, B, C, H, W);      // (interval 4: mulut_ft_stage_*)
+    const int rc = ft_fill(a, interval == 5 || interval == 6, weights_q, nullptr, modes, is_last, u, x, inside, true, 2, B, C, H, W);      // (interval 4: mulut_ft_stage_*)
     if (rc) return rc;
     if (!out) return MULUT_EINVAL;
     a.out = out;
-    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    const int cus = ftiv_num_cus(device);
-    const hipError_t e = interval == 5 ? launch_ftiv<5>(a, false, cus, (hipStream_t)stream) : launch_ftiv<6>(a, false, cus, (hipStream_t)stream);
-    return e == hipSuccess ? MULUT_OK : MULUT_EHIP;
+    return ftiv_run(a, device, interval, false, stream);
 }
 
 // autograd's backward of that stage: gradients of the quantised tables and of the input
@@ -574,15 +597,41 @@ int mulut_ft_interval_stage_backward(int device, int interval, const float *cons
                                      float *const *grad_wq, float *grad_x, void *stream) {
     if (!grad_wq) return MULUT_EINVAL;
     FtIvArgs a;
-    const int rc = ft_fill(a, interval == 5 || interval == 6, weights_q, grad_wq, modes, is_last, u, x, inside, true, B, C, H, W);
+    const int rc = ft_fill(a, interval == 5 || interval == 6, weights_q, grad_wq, modes, is_last, u, x, inside, true, 2, B, C, H, W);
     if (rc) return rc;
     if (!grad_out || !grad_x) return MULUT_EINVAL;
     a.gout = grad_out;
     a.gx = grad_x;
-    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    const int cus = ftiv_num_cus(device);
-    const hipError_t e = interval == 5 ? launch_ftiv<5>(a, true, cus, (hipStream_t)stream) : launch_ftiv<6>(a, true, cus, (hipStream_t)stream);
-    return e == hipSuccess ? MULUT_OK : MULUT_EHIP;
+    return ftiv_run(a, device, interval, true, stream);
+}
+
+// The same stage for any list over s, d, y, e, h, o at interval 4, 5 or 6 (sr/model.py:69-312; the reference's module stops at s, d, y
+// with "more sampling modes can be implemented similarly", :119-121 -- the 4 x 4 taps are common/network.py:173-215).  A list with one
+// of e, h, o runs the backward kernels' HALO = 3 instances; a list without runs what mulut_ft_stage_*_mask / mulut_ft_interval_stage_*
+// run, so the two families agree bit for bit there.
+int mulut_ft_wide_stage_forward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                const float *x, int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
+    FtIvArgs a;
+    const int rc = ft_fill(a, interval >= 4 && interval <= 6, weights_q, nullptr, modes, is_last, u, x, inside, true, 3, B, C, H, W);
+    if (rc) return rc;
+    if (!out) return MULUT_EINVAL;
+    if (interval == 4) return ft_wide4_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, stream);
+    a.out = out;
+    return ftiv_run(a, device, interval, false, stream);
+}
+
+int mulut_ft_wide_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                 const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
+                                 float *const *grad_wq, float *grad_x, void *stream) {
+    if (!grad_wq) return MULUT_EINVAL;
+    FtIvArgs a;
+    const int rc = ft_fill(a, interval >= 4 && interval <= 6, weights_q, grad_wq, modes, is_last, u, x, inside, true, 3, B, C, H, W);
+    if (rc) return rc;
+    if (!grad_out || !grad_x) return MULUT_EINVAL;
+    if (interval == 4) return ft_wide4_backward(device, weights_q, modes, is_last, u, x, grad_out, inside, B, C, H, W, grad_wq, grad_x, stream);
+    a.gout = grad_out;
+    a.gx = grad_x;
+    return ftiv_run(a, device, interval, true, stream);
 }
 
 }  // extern "C"

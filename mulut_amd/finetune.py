@@ -5,7 +5,8 @@ names (``weight_s{stage}_{mode}``, float32 [83521, u*u] = int8/127, sr/model.py:
 (x float32 [B,C,H,W] in 0..1 -> [B,C,H*u,W*u] in 0..1, :289-312), so ``sr/3_finetune_lut.py`` can train it with
 the same Adam / cosine schedule and write ``LUT_ft_*.npy`` the same way (:162-169).  Each stage runs as one
 forward and one backward HIP kernel (mulut_amd/csrc/mulut_ft.hip) through the C ABI; torch provides autograd
-plumbing, parameters and the optimiser only.
+plumbing, parameters and the optimiser only.  ``MuLUTInterval`` is the same module at intervals 5 and 6, ``MuLUTWide`` the one
+for mode lists with the 4 x 4 patterns e, h, o (intervals 4, 5 and 6).
 """
 import ctypes
 import os
@@ -25,7 +26,7 @@ class _StageFn(torch.autograd.Function):
     """One stage: all modes x 4 rotations, per-pass BPDA rounding, clamp/round of the stage output."""
 
     @staticmethod
-    def forward(ctx, x, modes, is_last, u, interval, *weights):
+    def forward(ctx, x, modes, is_last, u, interval, wide, *weights):
         lib = _native.load()
         x = x.contiguous()
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
@@ -43,7 +44,10 @@ class _StageFn(torch.autograd.Function):
         out = torch.empty((B, C, H * u, W * u), dtype=torch.float32, device=x.device)
         # where the stage's clamp passes gradient, 16 bits per site: saves the backward a recomputation of the stage forward
         inside = torch.empty((B, C, H, W), dtype=torch.int16, device=x.device)
-        if interval == 4:
+        if wide:    # any list over s, d, y, e, h, o at interval 4, 5 or 6
+            rc = lib.mulut_ft_wide_stage_forward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                                 x.data_ptr(), B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
+        elif interval == 4:
             rc = lib.mulut_ft_stage_forward_mask(x.device.index, _ptr_array(wq), modes.encode(), int(is_last), int(u), x.data_ptr(),
                                                  B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
         else:       # intervals 5 and 6: mulut_ft_interval.hip
@@ -52,13 +56,13 @@ class _StageFn(torch.autograd.Function):
         if rc:
             raise (ValueError if rc == -2 else RuntimeError)(lib.mulut_strerror(rc).decode())
         ctx.save_for_backward(x, wq_all, inside, *ws)
-        ctx.cfg = (modes, is_last, u, interval)
+        ctx.cfg = (modes, is_last, u, interval, wide)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         lib = _native.load()
-        modes, is_last, u, interval = ctx.cfg
+        modes, is_last, u, interval, wide = ctx.cfg
         x, wq_all, inside, *ws = ctx.saved_tensors
         wq = [wq_all[m].view(w.shape) for m, w in enumerate(ws)]
         gout = gout.contiguous()
@@ -67,7 +71,11 @@ class _StageFn(torch.autograd.Function):
         gwq = [g_all[m].view(w.shape) for m, w in enumerate(ws)]
         gx = torch.zeros_like(x)
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        if interval == 4:
+        if wide:
+            rc = lib.mulut_ft_wide_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                                  x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
+                                                  gx.data_ptr(), stream)
+        elif interval == 4:
             rc = lib.mulut_ft_stage_backward_mask(x.device.index, _ptr_array(wq), modes.encode(), int(is_last), int(u), x.data_ptr(),
                                                   gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq), gx.data_ptr(), stream)
         else:
@@ -80,12 +88,15 @@ class _StageFn(torch.autograd.Function):
         rc = lib.mulut_ft_quantize_backward(x.device.index, _ptr_array(ws), _ptr_array(gwq), len(ws), ws[0].numel(), stream)
         if rc:
             raise RuntimeError(lib.mulut_strerror(rc).decode())
-        return (gx, None, None, None, None) + tuple(gwq)
+        return (gx, None, None, None, None, None) + tuple(gwq)
 
 
 class MuLUT(nn.Module):
     """PyTorch module for LUT-aware fine-tuning on the GPU (twin of sr/model.py:39-312), sampling interval 4.
-    Intervals 5 and 6 are ``MuLUTInterval``."""
+    Intervals 5 and 6 are ``MuLUTInterval``; mode lists with e, h or o are ``MuLUTWide``."""
+
+    MODES = "sdy"       # the patterns the class takes
+    WIDE = False        # stages through mulut_ft_wide_stage_* (any of the six patterns) instead of the s, d, y entry points
 
     def __init__(self, lut_folder, stages, modes, upscale=4, interval=4):
         super().__init__()
@@ -93,9 +104,9 @@ class MuLUT(nn.Module):
         self.interval, self.upscale, self.stages = interval, upscale, stages
         self.modes = "".join(modes)
         for mode in self.modes:
-            # the device fine-tuning kernels cover s, d and y (the 4 x 4 patterns e, h, o run in inference only);
+            # this class and MuLUTInterval keep to the reference module's s, d and y (the 4 x 4 patterns e, h, o are MuLUTWide);
             # the reference raises the same way for any mode it does not implement (sr/model.py:121)
-            if mode not in "sdy":
+            if mode not in self.MODES:
                 raise ValueError("Mode {} not implemented.".format(mode))
         for s in range(stages):
             stage = s + 1
@@ -114,7 +125,7 @@ class MuLUT(nn.Module):
             stage = s + 1
             last = stage == self.stages
             weights = [getattr(self, "weight_s{}_{}".format(stage, m)) for m in self.modes]
-            x = _StageFn.apply(x, self.modes, last, self.upscale if last else 1, self.interval, *weights)
+            x = _StageFn.apply(x, self.modes, last, self.upscale if last else 1, self.interval, self.WIDE, *weights)
         return x / 255.0
 
     @staticmethod
@@ -147,3 +158,20 @@ class MuLUTInterval(MuLUT):
         if interval not in (5, 6):
             raise ValueError("mulut_amd.finetune.MuLUTInterval takes interval 5 or 6 (got {}); interval 4 is "
                              "mulut_amd.finetune.MuLUT".format(interval))
+
+
+class MuLUTWide(MuLUT):
+    """The same module for any list over the six sampling patterns s, d, y, e, h, o, at interval 4, 5 or 6.  The reference's
+    module ends its pattern cascade at s, d, y with "more sampling modes can be implemented similarly" (sr/model.py:119-121) while
+    its network and trainer define all six (common/network.py:173-215): this class fine-tunes the tables transfer_to_lut writes
+    for them, same file names, parameter names and forward contract.  The stages run through mulut_ft_wide_stage_forward /
+    _backward: the backward kernels with a 3-pixel halo of the input gradient when the list holds e, h or o, and exactly what
+    ``MuLUT`` / ``MuLUTInterval`` run when it does not."""
+
+    MODES = "sdyeho"
+    WIDE = True
+
+    @staticmethod
+    def _check_interval(interval):
+        if interval not in (4, 5, 6):
+            raise ValueError("mulut_amd.finetune.MuLUTWide takes interval 4, 5 or 6 (got {})".format(interval))

@@ -5,7 +5,8 @@
 Reads the transferred tables ``LUT_x{scale}_{interval}bit_int8_s{stage}_{mode}.npy`` from expDir (sr/model.py:51-53),
 optimises them with Adam + the reference's cosine LambdaLR on random single-channel crops with the reference's
 rigid augmentation (sr/data.py:96-124), and writes ``LUT_ft_x{scale}_{interval}bit_int8_s{stage}_{mode}.npy``
-(sr/3_finetune_lut.py:162-169).  The model is ``mulut_amd.finetune.MuLUT``, at ``--interval 5`` / ``6`` ``MuLUTInterval`` (HIP forward/backward kernels).
+(sr/3_finetune_lut.py:162-169).  The model is ``mulut_amd.finetune.MuLUT``, at ``--interval 5`` / ``6`` ``MuLUTInterval``, and ``MuLUTWide`` at any of the three
+intervals when ``--modes`` holds one of the 4 x 4 patterns e, h, o (HIP forward/backward kernels).
 Training pairs: ``{trainDir}/HR/<stem>.png`` with ``{trainDir}/LR/X{scale}/<stem>x{scale}.png`` (DIV2K layout) or
 ``{trainDir}/LR_bicubic/X{scale}/<stem>.png`` (benchmark layout).  ``valid_steps`` is the reference's validation loop
 (:23-65): every ``--valStep`` iterations (and at iteration 1) each benchmark image goes through the module, the result is
@@ -23,7 +24,7 @@ import torch
 import torch.nn.functional as F
 from PIL import Image
 
-from .finetune import MuLUT, MuLUTInterval
+from .finetune import MuLUT, MuLUTInterval, MuLUTWide
 
 
 class CropProvider:
@@ -142,7 +143,8 @@ def build_parser():
 
 
 def finetune(opt, log=print):
-    net = (MuLUTInterval if opt.interval in (5, 6) else MuLUT)(opt.expDir, opt.stages, list(opt.modes), upscale=opt.scale, interval=opt.interval).cuda()
+    wide = any(m in "eho" for m in opt.modes)      # the reference's module stops at s, d, y (sr/model.py:119-121)
+    net = (MuLUTWide if wide else MuLUTInterval if opt.interval in (5, 6) else MuLUT)(opt.expDir, opt.stages, list(opt.modes), upscale=opt.scale, interval=opt.interval).cuda()
     params = [p for p in net.parameters() if p.requires_grad]
     optim = torch.optim.Adam(params, lr=opt.lr0, betas=(0.9, 0.999), eps=1e-8, weight_decay=opt.weightDecay, amsgrad=False,
                              fused=True)      # the same update as one launch over the six tables (the default is ~10 per step)

@@ -9,6 +9,10 @@ Prints, per tensor, max |diff|, max |ref| and the largest element-wise relative 
                                                     tests/test_gpu_ft_interval.py with the 256 crops in the given order, reversed
                                                     and in one seeded shuffle -- what a different order of the same float32 sums
                                                     is worth; the bars of that test are twice the worst figure printed here
+    tools/ft_err_probe.py --modes eho ...           the same two forms for a list with the 4 x 4 patterns e, h, o (any interval):
+                                                    mulut_amd.finetune.MuLUTWide against the oracle with the taps of e, h, o added
+                                                    to its PATTERNS / PAD at run time, on the seeded tables and batches of
+                                                    tests/test_gpu_ft_wide.py (whose bs-256 bars come from --orderings)
 """
 import argparse, os, sys, tempfile
 import numpy as np, torch
@@ -56,10 +60,23 @@ def oracle_grads(tabs, x, tgt, stages, modes, scale, interval):
     return xc.grad.numpy(), {k: w.grad.numpy() for k, w in wcpu.items()}
 
 
-def case(interval, shape, kind):
+WIDE_PATTERNS = {"e": ((0, 0), (0, 3), (3, 0), (3, 3)), "h": ((0, 0), (2, 2), (2, 3), (3, 2)), "o": ((0, 0), (2, 2), (1, 3), (3, 1))}
+
+
+def extend_oracle():
+    """the taps of e, h, o (common/network.py:173-215), edge pad 3, for this process (tests/ft_wide_cases.py does it per test)"""
+    ft_torch.PATTERNS = dict(ft_torch.PATTERNS, **WIDE_PATTERNS)
+    ft_torch.PAD = dict(ft_torch.PAD, e=3, h=3, o=3)
+
+
+def case(interval, shape, kind, modes="sdy"):
     """(tables, x, target) of one batch: the test files' own draws."""
-    stages, modes, scale = 2, "sdy", 4
-    if interval == 4:
+    stages, scale = 2, 4
+    if modes != "sdy":      # tests/test_gpu_ft_wide.py: seeded tables at every interval
+        rng = np.random.default_rng(stages * 100 + scale * 10 + len(modes) + interval)
+        tabs = {"s%d_%s" % (s + 1, m): synthetic_lut_iv(interval, s + 1, m, scale * scale if s + 1 == stages else 1) for s in range(stages) for m in modes}
+        x = natural_batch(np.random.default_rng(1), shape) if kind == "smooth" else rng.integers(0, 256, shape).astype(np.float32) / np.float32(255)
+    elif interval == 4:
         rng = np.random.default_rng(241)
         tabs = {"s%d_%s" % (s + 1, m): synthetic_lut(3 * s + ord(m), scale * scale if s + 1 == stages else 1) for s in range(stages) for m in modes}
         x = natural_batch(rng, shape) if kind == "smooth" else rng.integers(0, 256, shape).astype(np.float32) / np.float32(255)
@@ -78,11 +95,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--interval", type=int, default=4, choices=(4, 5, 6))
     ap.add_argument("--orderings", action="store_true")
+    ap.add_argument("--modes", default="sdy", help="sdy: the batches of the s, d, y tests; any other list over sdyeho: MuLUTWide")
     opt = ap.parse_args()
-    stages, modes, scale = 2, "sdy", 4
+    stages, modes, scale = 2, opt.modes, 4
+    if any(m in "eho" for m in modes):
+        extend_oracle()
     if opt.orderings:
         shape = (256, 1, 48, 48)
-        tabs, x, tgt = case(opt.interval, shape, "smooth")
+        tabs, x, tgt = case(opt.interval, shape, "smooth", modes)
         perms = [np.arange(256), np.arange(256)[::-1].copy(), np.random.default_rng(7).permutation(256)]
         res = []
         for p in perms:
@@ -98,14 +118,15 @@ def main():
                 worst = [max(worst[0], n), max(worst[1], e)]
         print("interval %d worst over the table gradients: norm-wise %.3e element-wise %.3e" % (opt.interval, worst[0], worst[1]))
         return
-    from mulut_amd.finetune import MuLUT, MuLUTInterval
+    from mulut_amd.finetune import MuLUT, MuLUTInterval, MuLUTWide
+    cls = MuLUTWide if modes != "sdy" else MuLUT if opt.interval == 4 else MuLUTInterval
     for shape, kind in (((256, 1, 48, 48), "smooth"), ((16, 1, 48, 48), "u8"), ((256, 1, 48, 48), "u8")):
-        tabs, x, tgt = case(opt.interval, shape, kind)
+        tabs, x, tgt = case(opt.interval, shape, kind, modes)
         tmp = tempfile.mkdtemp()
         for k, t in tabs.items():
             np.save(os.path.join(tmp, "LUT_x%d_%dbit_int8_%s.npy" % (scale, opt.interval, k)), t)
         gxc, gwc = oracle_grads(tabs, x, tgt, stages, modes, scale, opt.interval)
-        net = (MuLUT if opt.interval == 4 else MuLUTInterval)(tmp, stages, modes, upscale=scale, interval=opt.interval).cuda()
+        net = cls(tmp, stages, modes, upscale=scale, interval=opt.interval).cuda()
         xg = torch.from_numpy(x).cuda().requires_grad_(True)
         yg = net(xg)
         torch.nn.functional.mse_loss(yg, torch.from_numpy(tgt).cuda()).backward()
