@@ -760,10 +760,11 @@ __device__ __forceinline__ float t2_f32_of_i16(uint32_t x) {
 }
 
 template <int PAT>
-__device__ __forceinline__ void t2_index(uint32_t k0, uint32_t ha, uint32_t base_a0, uint32_t pb, uint32_t pc, uint32_t pd, T2Pair &o, uint32_t &dirty) {
+// TEST (wave-uniform): false where the wave's whole image of the channel is known to lie on two adjacent MSB levels (stash's flat
+// predicate) -- every pass is then in the tube and the test is skipped by a scalar branch
+__device__ __forceinline__ void t2_index(uint32_t k0, uint32_t ha, uint32_t base_a0, uint32_t pb, uint32_t pc, uint32_t pd, T2Pair &o, uint32_t &dirty, bool test) {
     constexpr uint32_t SB = kTubeSB * 16, SC = kTubeSC * 16, SD = kTubeSD * 16;
     uint32_t k1 = pb | pk_dup(SB), k2 = pc | pk_dup(SC), k3 = pd | pk_dup(SD);
-    const uint32_t hb = pb & 0x000F000Fu, hc = pc & 0x000F000Fu, hd = pd & 0x000F000Fu;
     pk_cmpx_desc(k0, k1);
     pk_cmpx_desc(k2, k3);
     pk_cmpx_desc(k0, k2);
@@ -780,9 +781,13 @@ __device__ __forceinline__ void t2_index(uint32_t k0, uint32_t ha, uint32_t base
     o.w2 = f2 - f3;
     o.w3 = f3 - f4;
     o.w4 = f4;
-    const uint32_t mx = pk_max(pk_max(hb, hc), pk_max(hd, ha));
-    const uint32_t mn = pk_min(pk_min(hb, hc), pk_min(hd, ha));
-    dirty |= (mx - mn) & 0xFFFEFFFEu;       // in the tube iff the MSBs span at most one step
+    if (test) {
+        asm volatile("; MULUT_T2_TUBE_TEST");      // (a side effect: the block stays behind its branch, it is not turned into selects)
+        const uint32_t hb = pb & 0x000F000Fu, hc = pc & 0x000F000Fu, hd = pd & 0x000F000Fu;
+        const uint32_t mx = pk_max(pk_max(hb, hc), pk_max(hd, ha));
+        const uint32_t mn = pk_min(pk_min(hb, hc), pk_min(hd, ha));
+        dirty |= (mx - mn) & 0xFFFEFFFEu;       // in the tube iff the MSBs span at most one step
+    }
 }
 
 #define T2_ACC_OPS(lo, hi) [l0] "+v"(lo[0]), [l1] "+v"(lo[1]), [l2] "+v"(lo[2]), [l3] "+v"(lo[3]), [h0] "+v"(hi[0]), [h1] "+v"(hi[1]), [h2] "+v"(hi[2]), [h3] "+v"(hi[3])
@@ -828,7 +833,8 @@ template <int OUT, int PATS>
 __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_eu(TUBE2_WAVES_PER_EU, TUBE2_WAVES_PER_EU))) stage_tube2_kernel(StageArgs a, BandArgs b) {
     constexpr int TW = KB_TW, TH = KB_TH, PW = kT2PW, PH = kT2PH, NT = TW * TH;
     constexpr int M = t2_modes(PATS), NP = 2 * M;
-    constexpr int DW = PW / 4, PER4 = (3 * PH * DW + 63) / 64;         // aligned dwords per image row / per lane
+    constexpr int DW = PW / 4, PER4 = 3;         // aligned dwords per image row / per lane: channel k in register k of lanes 0 .. PH * DW - 1
+    static_assert(PH * DW <= 64, "a channel of the wave's image is one dword per lane");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t *s_next = (uint32_t *)(smem + kTube2LdsBytes - 16);       // the workgroup's next work item
     if (lds_addr_of(smem) != 0u) __builtin_trap();      // every LDS address below is absolute: the dynamic block must start at 0 (no static LDS here)
@@ -876,15 +882,18 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
         asm volatile("" : "+v"(lane));
 #pragma unroll
         for (int k = 0; k < PER4; ++k) {
-            const int i = lane + 64 * k;
-            const int q = i % DW, py = (i / DW) % PH, c = imin(i / (DW * PH), a.C - 1);
+            // (lanes PH * DW .. 63 repeat the first rows, channels past the last repeat the last: every register holds pixels of ITS channel's image)
+            const int q = lane % DW, py = (lane / DW) % PH, c = imin(k, a.C - 1);
             const int gy = imin(imax(y0 + py - kHalo, ylo), yhi);
             const int gx = imin(imax(x0 - kTubeHaloX + 4 * q, 0), a.W - 4);
             v[k] = *(const uint32_t *)view_addr(a.in, n, c, gy, gx);
         }
     };
-    auto stash = [&](int j, const uint32_t (&v)[PER4]) {
-        if (j < 0) return;
+    // Returns the flat bits of the image, bit c: every MSB of channel c lies on one of two adjacent levels, so no pass of the tile can leave
+    // the tube (the image holds every pixel the tile's windows read).  Wave-uniform; the byte path reports "not flat".
+    auto stash = [&](int j, const uint32_t (&v)[PER4]) -> uint32_t {
+        if (j < 0) return 0u;
+        uint32_t flat = 0u;
         int n, y0, x0;
         origin(j, n, y0, x0);
         int lane = (int)(threadIdx.x & 63);
@@ -895,8 +904,16 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
             const bool edge = __builtin_amdgcn_readfirstlane((int)(x0 - kTubeHaloX < 0 || x0 - kTubeHaloX + 4 * (DW - 1) > a.W - 4)) != 0;
 #pragma unroll
             for (int k = 0; k < PER4; ++k) {
-                const int i = lane + 64 * k;
-                if (i < a.C * PH * DW) {
+                const int i = lane + PH * DW * k;
+                // the four MSBs of the dword against those of the image's first pixel r, per byte and carry-free: h + 16 - r is 16 or 17 iff h
+                // is r or r + 1, h + 17 - r iff h is r - 1 or r.  Every lane votes (a dword clamped at an edge holds pixels of the image or of
+                // the frame beside it: a superset); flat iff one of the two holds for all of them.
+                const uint32_t r = ((uint32_t)__builtin_amdgcn_readfirstlane((int)v[k]) >> 4) & 15u;
+                const uint32_t h4 = (v[k] >> 4) & 0x0F0F0F0Fu;
+                const bool up = ((h4 + (16u - r) * 0x01010101u) & 0xFEFEFEFEu) != 0x10101010u;
+                const bool dn = ((h4 + (17u - r) * 0x01010101u) & 0xFEFEFEFEu) != 0x10101010u;
+                if (__ballot(up) == 0ull || __ballot(dn) == 0ull) flat |= 1u << k;
+                if (lane < PH * DW && k < a.C) {
                     // bytes (b0,b1) / (b2,b3) into 16-bit lanes; a dword clamped at an image edge replicates the edge byte
                     uint32_t lo, hi;
                     if (!edge) {
@@ -922,6 +939,7 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
                 ((uint16_t *)img)[i] = (uint16_t)pixel_code1(*view_addr(a.in, n, c, gy, gx));
             }
         }
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)flat);
     };
 
 #if defined(MULUT_VARIANT_t2prof)   /* probe build: shader-clock ticks per phase, summed over all waves into the context's probe buffer */
@@ -955,10 +973,12 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
 
     // the wave's share of the fix-up list in the making (entries in LDS, their number in a scalar register)
     uint32_t *fix_buf = (uint32_t *)(smem + kT2FixOff) + wave * kT2FixCap;
+    // (the number is only ever changed where the whole wave is converged: a count advanced under the site's "inside the image" mask would be
+    // per-lane state, stale in the lanes a partial tile leaves out)
     uint32_t fix_have = 0u;
     auto fix_flush = [&]() {
         if (fix_have == 0u) return;      // wave-uniform
-        // called where lanes outside the image are masked off: the copy is shared out among the ACTIVE lanes
+        // the copy is shared out among the active lanes
         const unsigned long long act = __ballot(true);
         const uint32_t rank = (uint32_t)__popcll(act & ((1ull << (threadIdx.x & 63)) - 1ull)), nact = (uint32_t)__popcll(act);
         uint32_t at = 0u;
@@ -972,7 +992,7 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
     uint32_t pix[PER4];
     int item = grab();
     fetch(item, pix);
-    stash(item, pix);
+    uint32_t flat = stash(item, pix);      // of the tile being computed; re-derived with every tile's image
     while (item >= 0) {
         const int nxt_item = grab();
         fetch(nxt_item, pix);
@@ -989,6 +1009,7 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
         int n, y, x, lx, ly;
         site(n, y, x, lx, ly);
         T2_STAMP(0);       // work item drawn, next tile's fetch issued
+        uint32_t dmask = 0u;      // bit c: the sample of channel c left the tube (stays 0 in lanes outside the image)
         if (y < a.oy1 && x < a.W) {
             // LDS byte address of the 5x5 window corner (y-2, x-2) of this site, channel 0
             uint32_t win = (uint32_t)(3 * kTubeBandBytes + wave * kT2WaveTileBytes + 2 * (ly * PW + lx + kTubeHaloX - kHalo));
@@ -999,7 +1020,7 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
                 asm volatile("" : "+v"(t));
                 return (uint4 *)(smem + 3 * kTubeBandBytes + 16 * kT2WaveTileBytes) + t;
             };
-            uint32_t dmask = 0u, dirty = 0u, dirty_n = 0u;
+            uint32_t dirty = 0u, dirty_n = 0u;
             uint32_t o[4] = {0u, 0u, 0u, 0u};
             uint32_t pb, pc, pd, ca;
             uint32_t k0, ha, ba0;
@@ -1014,11 +1035,11 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
                 uint32_t t0, t1, t2;
                 asm volatile(TUBE2_ASM_LOAD_NB_ANCHOR : T2_NBOUT_OPS, [ca] "=&v"(ca) : [win] "v"(win), T2_NB_OPS(p0, 0, 0) : TUBE2_CLOBBERS);
                 anchor(ca);
-                t2_index<p0>(k0, ha, ba0, pb, pc, pd, cur, dirty);
+                t2_index<p0>(k0, ha, ba0, pb, pc, pd, cur, dirty, (flat & 1u) == 0u);
                 asm volatile(TUBE2_ASM_LOAD_NB : T2_NBOUT_OPS : [win] "v"(win), T2_NB_OPS(p0, 1, 0) : TUBE2_CLOBBERS);
                 uint32_t a0, a1, a2, a3;
                 asm volatile(TUBE2_ASM_FIRST_ROWS : T2_TMP_OPS : T2_ADDR_OPS(cur), T2_IMM_OPS(p0) : TUBE2_CLOBBERS);
-                t2_index<p0>(k0, ha, ba0, pb, pc, pd, nxt, dirty);
+                t2_index<p0>(k0, ha, ba0, pb, pc, pd, nxt, dirty, (flat & 1u) == 0u);
             }
             RotAcc<4> acc;
             // the (0,2) fields start at -unbias (the rows are value + 128: unbias = 128 * 16 * 4 M <= 24576) where the epilogue works on K
@@ -1038,6 +1059,8 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
 #pragma clang loop unroll(disable)
             for (int c = 0; c < a.C; ++c, win += kT2Chan) {
                 const bool more = c + 1 < a.C;       // wave-uniform
+                // pairs 2 .. of this channel are tested here, pairs 0 and 1 of the next (indexed inside this channel's last two pairs) with ITS bit
+                const bool test = ((flat >> c) & 1u) == 0u, test_n = ((flat >> (c + 1)) & 1u) == 0u;
                 asm volatile("; MULUT_T2_STREAM_BEGIN (tools/ubench/gen_stream_ubench.py cuts the ISA here)");
                 static_for<0, NP>([&](auto PI) {
                     constexpr int p = PI;
@@ -1055,8 +1078,8 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
                     if (t_here || more) {      // (then the next pair exists too: t_here implies n_here)
                         t2_block_b<npat, (tp == 0 ? 7 : 6), tpat, tr, toff, false>(lo, hi, cur, nxt, win, pb, pc, pd, ca);
                         if constexpr (tp == 0) anchor(ca);
-                        if constexpr (t_here) t2_index<tpat>(k0, ha, ba0, pb, pc, pd, nn, dirty);
-                        else t2_index<tpat>(k0, ha, ba0, pb, pc, pd, nn, dirty_n);
+                        if constexpr (t_here) t2_index<tpat>(k0, ha, ba0, pb, pc, pd, nn, dirty, test);
+                        else t2_index<tpat>(k0, ha, ba0, pb, pc, pd, nn, dirty_n, test_n);
                     } else {
                         if constexpr (n_here) t2_block_b<npat, 0, 0, 0, 0, false>(lo, hi, cur, nxt, win, pb, pc, pd, ca);
                         else t2_block_b<npat, 0, 0, 0, 0, true>(lo, hi, cur, nxt, win, pb, pc, pd, ca);
@@ -1118,18 +1141,21 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
                 dirty_n = 0u;
             }
             T2_STAMP(2);   // the channels: 12 passes + epilogue each
-            site(n, y, x, lx, ly);
             if constexpr (OUT == kOutPackedRGBU4) {
+                site(n, y, x, lx, ly);
                 const uint4 r = park()[0], g = park()[NT];
                 const uint32_t oR[4] = {r.x, r.y, r.z, r.w}, oG[4] = {g.x, g.y, g.z, g.w};
                 store_rgb<4>(a, n, y, x, oR, oG, o);
             }
+        }
+        {
             // dirty samples (pixel, channel) are collected in the wave's LDS buffer and appended to the fix-up list when it is full (and
             // when the wave runs out of work): one memory-side atomic per ~190 flagged samples instead of one per wave tile and channel
 #if defined(MULUT_VARIANT_nofixlist)    /* timing-only: nothing is listed (flagged samples stay wrong) */
             if (dmask == 0xFFFFFFFFu) a.fix_list[0] = 0u;
 #else
-            if (__ballot(dmask != 0u) != 0ull) {
+            if (__ballot(dmask != 0u) != 0ull) {       // the whole wave is here: lanes outside the image hold dmask 0
+                site(n, y, x, lx, ly);
                 const uint32_t pixel_id = ((uint32_t)n * (uint32_t)a.H + (uint32_t)y) * (uint32_t)a.W + (uint32_t)x;
                 const unsigned long long m0 = __ballot((dmask & 1u) != 0u), m1 = __ballot((dmask & 2u) != 0u), m2 = __ballot((dmask & 4u) != 0u);
                 const uint32_t n0 = (uint32_t)__popcll(m0), n1 = (uint32_t)__popcll(m1), n2 = (uint32_t)__popcll(m2);
@@ -1138,12 +1164,12 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
                 if (dmask & 1u) fix_buf[fix_have + (uint32_t)__popcll(m0 & below)] = pixel_id;
                 if (dmask & 2u) fix_buf[fix_have + n0 + (uint32_t)__popcll(m1 & below)] = pixel_id | (1u << 30);
                 if (dmask & 4u) fix_buf[fix_have + n0 + n1 + (uint32_t)__popcll(m2 & below)] = pixel_id | (2u << 30);
-                fix_have += n0 + n1 + n2;
+                fix_have = (uint32_t)__builtin_amdgcn_readfirstlane((int)(fix_have + n0 + n1 + n2));
             }
 #endif
         }
         T2_STAMP(3);       // output stores, fix-up list
-        stash(nxt_item, pix);      // the wave's image is its own: every read of the current tile has returned (the pipeline drained)
+        flat = stash(nxt_item, pix);      // the wave's image is its own: every read of the current tile has returned (the pipeline drained)
         T2_STAMP(4);       // next tile's pixel codes into LDS (waits for its fetch)
         item = nxt_item;
     }

@@ -31,6 +31,19 @@ def shifted(h, dy, dx):
     return h[ys][:, xs]
 
 
+def flat_share(h, left, right, tw=16, th=4, halo=2):
+    """Share of (tile, channel) pairs with max - min <= 1 over rows y0 - halo .. y0 + th + halo - 1, columns x0 - left .. x0 + right - 1 (clamped)."""
+    H, W, C = h.shape
+    flat = total = 0
+    for y0 in range(0, H, th):
+        rows = h[np.clip(np.arange(y0 - halo, y0 + th + halo), 0, H - 1)]
+        for x0 in range(0, W, tw):
+            blk = rows[:, np.clip(np.arange(x0 - left, x0 + right), 0, W - 1)]
+            flat += int(((blk.max((0, 1)) - blk.min((0, 1))) <= 1).sum())
+            total += C
+    return round(flat / total, 5)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dist", default="real")
@@ -54,7 +67,10 @@ def main():
             out_cnt += (mx - mn > 1)
     dirty = out_cnt > 0
     rec = {"dist": a.dist, "stage_input": a.stage, "frame": [H, W, C], "passes_in_tube": round(1 - out_cnt.sum() / (12.0 * H * W * C), 5),
-           "samples_clean": round(1 - dirty.mean(), 5), "tiles": {}}
+           "samples_clean": round(1 - dirty.mean(), 5),
+           # share of the (16x4 wave tile, channel) pairs whose MSBs span at most one step: over the pixels the tile's windows read, and over
+           # the whole 24x8 image of aligned dwords a stage_tube2_kernel wave stashes (the predicate it skips its tube tests on)
+           "flat_tile_share_windows": flat_share(h, 2, 18), "flat_tile_share_stash_image": flat_share(h, 4, 20), "tiles": {}}
     for name, (tw, th) in (("64x16", (64, 16)), ("16x4", (16, 4)), ("16x16", (16, 16)), ("64x64", (64, 64))):
         Hp, Wp = -(-H // th) * th, -(-W // tw) * tw
         d = np.zeros((Hp, Wp, C), np.float64); d[:H, :W] = dirty
