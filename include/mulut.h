@@ -263,7 +263,8 @@ int mulut_eval_y(int device, const void *gt_hwc, const void *out_hwc, int H, int
  *   tile, 3 = tube kernel on every tile.  (1: the first one-read-per-neighbour kernel, retired: MULUT_EINVAL.)
  * "first_stage_detail_per_1024": tile threshold of first_stage_kernel 0 (default 24).
  * Wide mode lists (e, h, o): every key above is accepted and stored, but does not change their route -- all their stages run on
- *   the wide kernels (stage_wide1_kernel, stage_wide_up_kernel), which have no tube, hybrid, slab or work-list variants.
+ *   the 3-px-halo instances of the two full-table kernels (mulut_kernel_name: stage_wide1_kernel = stage_u1w_kernel at halo 3,
+ *   stage_wide_up_kernel<u> = stage_up_kernel at halo 3), which have no tube, hybrid, slab or work-list variants.
  * Intervals 5 and 6: the same -- every key is accepted and stored, and their stages run on stage_interval_kernel regardless.
  * Unknown key or value: MULUT_EINVAL.
  * hipGraph capture: call mulut_reserve() for the largest (N, H, W, C) first -- the context's workspace, verdict and work-list

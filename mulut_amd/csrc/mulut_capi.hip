@@ -43,7 +43,7 @@ struct mulut_ctx {
     char modes[MULUT_MAX_MODES + 1] = {0};
     signed char di[MULUT_MAX_MODES][3], dj[MULUT_MAX_MODES][3];
     int reach = 2;  // LR rows one stage looks beyond its output rows
-    bool wide = false;  // the mode list holds a 4 x 4 pattern (e, h, o): reach 3, every stage on the wide kernels (mulut_wide.hip)
+    bool wide = false;  // the mode list holds a 4 x 4 pattern (e, h, o): reach 3, every stage on the halo-3 instances of the full-table kernels
     DevTable tab[MULUT_MAX_STAGES][6];  // [stage-1][pattern id s,d,y,e,h,o]
     uint8_t *ws[2] = {nullptr, nullptr};
     size_t ws_cap[2] = {0, 0};
@@ -454,8 +454,8 @@ static View make_view(const uint8_t *p, int layout, int rows, int W, int C, int 
 enum Route {
     kRouteIvLds,    // interval 5 / 6: stage_interval_kernel with the stage's tables in LDS
     kRouteIvGlobal, // interval 5 / 6: stage_interval_kernel gathering rows from the tables in global memory
-    kRouteWide1,    // a list with a 4 x 4 pattern (e, h, o), 1-byte rows: stage_wide1_kernel
-    kRouteWideUp,   // the same, u > 1: stage_wide_up_kernel
+    kRouteWide1,    // a list with a 4 x 4 pattern (e, h, o), 1-byte rows: stage_u1w_kernel at halo 3 ("stage_wide1_kernel")
+    kRouteWideUp,   // the same, u > 1: stage_up_kernel at halo 3 ("stage_wide_up_kernel<u>")
     kRouteU1Full,   // 1-byte rows: window kernel (full table in LDS) on every tile
     kRouteU1Tube,   // 1-byte rows: tube kernel (+ window kernel on the tiles it marks, when routed) + site fix-up
     kRouteUpTube,   // x2 / x3: tube-band kernel + site fix-up (+ gather kernel on the tiles it marks, when routed)
@@ -538,11 +538,8 @@ static StagePlan plan_stage(const mulut_ctx *ctx, const Routing &r, int u, const
     if (ctx->wide) {
         // a list with a 4 x 4 pattern: every stage on the wide kernels, before any tube / hybrid / slab / fix-up / tile-statistic
         // path (they all stage a 2-px halo or assume the s / d / y offsets); no work lists
-        int tw, th;
-        stage_wide_tile(u, tw, th);
         p.route = u == 1 ? kRouteWide1 : kRouteWideUp;
-        p.tiles_x = (a.W + tw - 1) / tw;
-        p.tiles_y = ((int)rows + th - 1) / th;
+        tile_grid(a, u == 1 ? stage_u1_tile : stage_up_tile, p.tiles_x, p.tiles_y);
         return p;
     }
     if (u == 1) {
@@ -624,7 +621,7 @@ static int ensure_plan(mulut_ctx *ctx, const StagePlan &p) {
     return rc;
 }
 
-// pattern id of every mode of the list (kernels that take one instance of their pass body per pattern)
+// pattern id of every mode of the list (stage_interval_kernel takes one instance of its pass body per pattern)
 static void fill_patterns(const mulut_ctx *ctx, PatternArgs &p) {
     for (int m = 0; m < kMaxModes; ++m) p.pat[m] = m < ctx->n_modes ? pattern_id(ctx->modes[m]) : 0;
 }
@@ -658,9 +655,7 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
     }
     if (p.route == kRouteWide1 || p.route == kRouteWideUp) {
         ctx->k1_valid = false;      // (no tile marks are left for the next stage)
-        PatternArgs wa;
-        fill_patterns(ctx, wa);
-        if (p.route == kRouteWide1) MAIN_KERNEL(ctx, stage, st, launch_stage_wide1(a, wa, st));
+        if (p.route == kRouteWide1) MAIN_KERNEL(ctx, stage, st, launch_stage_wide1(a, st));
         else MAIN_KERNEL(ctx, stage, st, launch_stage_wide_up(a, u, st));
         return MULUT_OK;
     }

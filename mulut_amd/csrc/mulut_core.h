@@ -67,6 +67,13 @@ MULUT_HD bool pattern_offsets(char mode, int (&di)[3], int (&dj)[3]) {
     }
 }
 
+// Pattern id (0..5 = s, d, y, e, h, o) of a mode from the offsets above: the first offset separates s, d, y and e; h and o share
+// (2, 2) and differ in the row of key c, 2 against 1.  For kernels that hold one instance of their pass body per pattern and are
+// handed the offsets only.
+MULUT_HD constexpr int pattern_id_of(int di0, int dj0, int di1) {
+    return di0 == 0 ? (dj0 == 1 ? 0 : dj0 == 2 ? 1 : 3) : di0 == 1 ? 2 : di1 == 2 ? 4 : 5;
+}
+
 // Reach of a pattern: the largest key offset, i.e. how many pixels one pass looks beyond its site in any direction
 // over the four rotations (= the reference's edge pad, sr/model.py:12).  0 for an unknown mode.
 MULUT_HD int pattern_reach(char mode) {

@@ -1,5 +1,5 @@
 // mulut_dev.h -- device helpers shared by the kernel translation units (mulut_kernels.hip, mulut_k1.hip, mulut_detail.hip,
-// mulut_wide.hip, mulut_interval.hip):
+// mulut_interval.hip):
 // image views and tile staging, pattern / rotation constants, packed 16-bit MAC and SDWA helpers, the per-rotation SWAR
 // accumulators of the final stage with their epilogues.  Device code only; see mulut_core.h for the per-site arithmetic.
 #ifndef MULUT_DEV_H_
@@ -20,41 +20,41 @@ __device__ __forceinline__ const uint8_t *view_addr(const View &v, int n, int c,
     return v.p + (long long)n * v.sN + (long long)c * v.sC + (long long)(y - v.row0) * v.sY + (long long)x * v.sX;
 }
 
-// Fill the LDS image tile [C][PH][PW] (TH x TW pixels + halo) with edge replication at the TRUE
-// image borders only (clamp to [0,H-1] x [0,W-1]); rows outside the band held by `in` are never
+// Fill the LDS image tile [C][PH][PW] (TH x TW pixels + a halo of HALO px, rows PW bytes apart) with edge replication at the
+// TRUE image borders only (clamp to [0,H-1] x [0,W-1]); rows outside the band held by `in` are never
 // touched because the host checks halo coverage.
-template <int TW, int TH, int NT>
+template <int TW, int TH, int NT, int HALO = kHalo, int PW = TW + 2 * HALO>
 __device__ __forceinline__ void load_tile(const StageArgs &a, int n, int y0, int x0, uint8_t *s_img) {
-    constexpr int PW = TW + 2 * kHalo, PH = TH + 2 * kHalo;
+    constexpr int PH = TH + 2 * HALO;
     const int total = a.C * PH * PW;
     for (int i = threadIdx.x; i < total; i += NT) {
         const int px = i % PW;
         const int py = (i / PW) % PH;
         const int c = i / (PW * PH);
-        // clamping to [oy0-2, oy1+1] as well is an identity for every row a valid site reads, and
+        // clamping to [oy0 - HALO, oy1 + HALO) as well is an identity for every row a valid site reads, and
         // keeps tiles that overhang the band from touching rows the caller's buffer does not hold
-        const int ylo = imax(a.oy0 - kHalo, 0), yhi = imin(a.oy1 + kHalo, a.H) - 1;
-        const int gy = imin(imax(y0 + py - kHalo, ylo), yhi);
-        const int gx = imin(imax(x0 + px - kHalo, 0), a.W - 1);
+        const int ylo = imax(a.oy0 - HALO, 0), yhi = imin(a.oy1 + HALO, a.H) - 1;
+        const int gy = imin(imax(y0 + py - HALO, ylo), yhi);
+        const int gx = imin(imax(x0 + px - HALO, 0), a.W - 1);
         s_img[i] = *view_addr(a.in, n, c, gy, gx);
     }
 }
 
 // The same copy with every byte load of a thread in flight before the first LDS store: a workgroup that owns
 // the whole CU (K1) has nobody to hide a dependent load chain behind, so the chain must not exist.
-template <int TW, int TH, int NT>
+template <int TW, int TH, int NT, int HALO = kHalo, int PW = TW + 2 * HALO>
 __device__ __forceinline__ void load_tile_batched(const StageArgs &a, int n, int y0, int x0, uint8_t *s_img) {
-    constexpr int PW = TW + 2 * kHalo, PH = TH + 2 * kHalo;
+    constexpr int PH = TH + 2 * HALO;
     constexpr int PER = (3 * PH * PW + NT - 1) / NT;
     const int total = a.C * PH * PW;
-    const int ylo = imax(a.oy0 - kHalo, 0), yhi = imin(a.oy1 + kHalo, a.H) - 1;
+    const int ylo = imax(a.oy0 - HALO, 0), yhi = imin(a.oy1 + HALO, a.H) - 1;
     uint8_t v[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         const int i = (int)threadIdx.x + k * NT;
         const int px = i % PW, py = (i / PW) % PH, c = imin(i / (PW * PH), a.C - 1);   // past the end: a valid address, never stored
-        const int gy = imin(imax(y0 + py - kHalo, ylo), yhi);
-        const int gx = imin(imax(x0 + px - kHalo, 0), a.W - 1);
+        const int gy = imin(imax(y0 + py - HALO, ylo), yhi);
+        const int gx = imin(imax(x0 + px - HALO, 0), a.W - 1);
         v[k] = *view_addr(a.in, n, c, gy, gx);
     }
 #pragma unroll
@@ -64,10 +64,11 @@ __device__ __forceinline__ void load_tile_batched(const StageArgs &a, int n, int
     }
 }
 
-// The tile of the kernels that serve all six patterns (mulut_wide.hip, mulut_interval.hip): a halo of 3 px, the largest
-// pattern_reach().  64 x 64 pixels, 1024 threads, four horizontally adjacent pixels per thread; rows of 72 bytes (64 + 2 x 3
-// columns, padded to whole dwords) x 70.  Each of the two files stages it with its own copy of load_tile_batched (3-px halo, this
-// pitch, the caller's row reach): through one shared loader their kernels came out 2-3 instructions different and missed the
+// The tile of the kernels that serve all six patterns: a halo of 3 px, the largest pattern_reach().  64 x 64 pixels, 1024
+// threads, four horizontally adjacent pixels per thread; rows of 72 bytes (64 + 2 x 3 columns, padded to whole dwords) x 70.
+// stage_u1w_kernel at HALO = 3 (mulut_k1.hip) derives the same sizes from its template parameters and stages the tile with
+// load_tile_batched<.., 3, 72>; the K3_* names are what stage_interval_kernel (mulut_interval.hip) uses, with a loader of its own
+// (the caller's row reach instead of the halo in the band clamp): sharing one loader with it moved its code and missed the
 // head-against-parent timing bar (profiles/shared_helpers_ab.json).
 constexpr int kHalo3 = 3;
 constexpr int K3_TW = 64, K3_TH = 64, K3_NT = 1024;
@@ -112,6 +113,12 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
 // rows / columns of keys b, c, d per pattern id (mulut_capi.hip pattern_id: s, d, y, e, h, o) -- pattern_offsets() as constants
 constexpr int kPatDi[6][3] = {{0, 1, 1}, {0, 2, 2}, {1, 1, 2}, {0, 3, 3}, {2, 2, 3}, {2, 1, 3}};
 constexpr int kPatDj[6][3] = {{1, 0, 1}, {2, 0, 2}, {1, 2, 1}, {3, 0, 3}, {2, 3, 2}, {2, 3, 1}};
+constexpr bool pattern_id_matches_tables() {
+    for (int p = 0; p < 6; ++p)
+        if (pattern_id_of(kPatDi[p][0], kPatDj[p][0], kPatDi[p][1]) != p) return false;
+    return true;
+}
+static_assert(pattern_id_matches_tables(), "pattern_id_of() recovers each of the six pattern ids from its offsets");
 constexpr int rot_dy(int r, int di, int dj) { return r == 0 ? di : r == 1 ? dj : r == 2 ? -di : -dj; }   // sample_offset
 constexpr int rot_dx(int r, int di, int dj) { return r == 0 ? dj : r == 1 ? -di : r == 2 ? -dj : di; }
 

@@ -7,7 +7,7 @@
 //                                      (M * iv_table_bytes <= kIvLdsBudget) are staged into LDS once per persistent workgroup
 //                                      next to the tile; LDS = false: the five rows of a pass are gathered from the tables in
 //                                      global memory (26-105 KB per mode: L2-resident), one vector load per row
-// One template instance of the pass body per pattern, chosen by the mode letter (scalar switch), as in mulut_wide.hip.
+// One template instance of the pass body per pattern, chosen by the mode letter (scalar switch), as stage_u1w_kernel of mulut_k1.hip does from the offsets.
 // mulut_pass at these intervals is pass_kernel<IV> of mulut_kernels.hip.
 #include <hip/hip_runtime.h>
 

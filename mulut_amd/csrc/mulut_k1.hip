@@ -1,6 +1,7 @@
 // mulut_k1.hip -- stages with 1-byte rows (non-final stages, and a final stage with u == 2 on the same kernel family):
 //   stage_u1t_kernel     tube band of every mode + the tile as pixel codes in LDS; smooth tiles (the default)
-//   stage_u1w_kernel     the whole 83.5 KB table of one mode in LDS, swapped per mode: detailed tiles (list mode) and the fallback
+//   stage_u1w_kernel     the whole 83.5 KB table of one mode in LDS, swapped per mode: detailed tiles (list mode) and the fallback;
+//                        at HALO = 3 every stage with 1-byte rows of a list that holds a 4 x 4 pattern (e, h, o)
 //   stage_u1_fix_kernel  sites the tube kernel flagged, recomputed from the full tables
 #include <hip/hip_runtime.h>
 
@@ -33,19 +34,24 @@ __device__ __forceinline__ int win_byte(const uint32_t (&win)[5][2]) {
 // pass instead of 49.  A neighbour pair is one v_perm_b32 of two window registers; the row offsets are rebuilt per pass from
 // the packed running sums (one SDWA add per row; the anchor's 13-bit stride rides as a marker bit that the pair math turns
 // into the stride for both halves at once); the two passes' values of a row are packed by a v_perm_b32 and accumulated by one v_dot2_i32_i16.
-template <int Q1, int J1, int Q2, int J2>
-__device__ __forceinline__ uint32_t win_byte_pair(const uint32_t (&win)[5][2]) {      // byte (Q1, J1) | byte (Q2, J2) << 16
+template <int Q1, int J1, int Q2, int J2, int NR, int NW>
+__device__ __forceinline__ uint32_t win_byte_pair(const uint32_t (&win)[NR][NW]) {      // byte (Q1, J1) | byte (Q2, J2) << 16
+    static_assert(Q1 >= 0 && Q1 < NR && Q2 >= 0 && Q2 < NR && J1 >= 0 && J1 < 4 * NW && J2 >= 0 && J2 < 4 * NW, "window is NR rows x 4 NW bytes");
     constexpr uint32_t sel = 0x0C000C00u | ((uint32_t)(4 + (J2 & 3)) << 16) | (uint32_t)(J1 & 3);
     return __builtin_amdgcn_perm(win[Q2][J2 >> 2], win[Q1][J1 >> 2], sel);
 }
-template <int PAT, int R, int I>
-__device__ __forceinline__ int u1p_pair(const int8_t *s_lut, const uint32_t (&win)[5][2], uint32_t k0, uint32_t ta, int sum) {
+// The window of a thread's four pixels at a halo of H px: 2 H + 1 rows of 4 + 2 H bytes, held as whole dwords (5 x 2 at the
+// 2-px halo of s / d / y, 7 x 3 at the 3-px halo of e / h / o); the pixel I's own byte sits at column I + H of row H.
+constexpr int u1p_win_dwords(int H) { return (4 + 2 * H + 3) / 4; }
+template <int PAT, int R, int I, int H>
+__device__ __forceinline__ int u1p_pair(const int8_t *s_lut, const uint32_t (&win)[2 * H + 1][u1p_win_dwords(H)], uint32_t k0, uint32_t ta, int sum) {
+    constexpr int NR = 2 * H + 1, NW = u1p_win_dwords(H);
     constexpr int yb = rot_dy(R, kPatDi[PAT][0], kPatDj[PAT][0]), xb = rot_dx(R, kPatDi[PAT][0], kPatDj[PAT][0]);
     constexpr int yc = rot_dy(R, kPatDi[PAT][1], kPatDj[PAT][1]), xc = rot_dx(R, kPatDi[PAT][1], kPatDj[PAT][1]);
     constexpr int yd = rot_dy(R, kPatDi[PAT][2], kPatDj[PAT][2]), xd = rot_dx(R, kPatDi[PAT][2], kPatDj[PAT][2]);
-    FullPair1 fp;      // pixel I of the thread's four: its window is columns I .. I + 4 of the 8 the registers hold
-    simplex4_full_pair1(k0, win_byte_pair<2 + yb, I + 2 + xb, 2 - yb, I + 2 - xb>(win), win_byte_pair<2 + yc, I + 2 + xc, 2 - yc, I + 2 - xc>(win),
-                        win_byte_pair<2 + yd, I + 2 + xd, 2 - yd, I + 2 - xd>(win), fp);
+    FullPair1 fp;      // rotation R + 2 displaces by the negated offsets
+    simplex4_full_pair1(k0, win_byte_pair<H + yb, I + H + xb, H - yb, I + H - xb, NR, NW>(win), win_byte_pair<H + yc, I + H + xc, H - yc, I + H - xc, NR, NW>(win),
+                        win_byte_pair<H + yd, I + H + xd, H - yd, I + H - xd, NR, NW>(win), fp);
     uint32_t ra[4], rb[4];
     ra[0] = add_word<0>(ta, fp.base);
     rb[0] = add_word<1>(ta, fp.base);
@@ -70,35 +76,39 @@ __device__ __forceinline__ int u1p_pair(const int8_t *s_lut, const uint32_t (&wi
 }
 // acc[4 c + i]: pixel i of channel c.  The four pixels are unrolled with immediate window columns: no window shifting, no
 // accumulator rotation (the rolled pixel loop of u1w_mode spends 13 of its 49 instructions per pass on those).
-template <int PAT, int PW, int PH>
+template <int PAT, int PW, int PH, int H>
 __device__ __forceinline__ void u1p_mode(const int8_t *s_lut, const uint8_t *s_img, int ty, int x4, int C, int (&acc)[12]) {
     static_for<0, 3>([&](auto CC) {
         constexpr int c = CC;
         if (c < C) {          // workgroup-uniform
             const uint32_t *row = (const uint32_t *)(s_img + c * (PH * PW) + ty * PW + x4);
-            uint32_t win[5][2];
+            uint32_t win[2 * H + 1][u1p_win_dwords(H)];
 #pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                win[q][0] = row[q * (PW / 4)];
-                win[q][1] = row[q * (PW / 4) + 1];
-            }
+            for (int q = 0; q < 2 * H + 1; ++q)
+#pragma unroll
+                for (int k = 0; k < u1p_win_dwords(H); ++k) win[q][k] = row[q * (PW / 4) + k];
             static_for<0, 4>([&](auto II) {
                 constexpr int i = II;
-                const uint32_t va = (i + 2 < 4 ? (win[2][0] >> (8 * ((i + 2) & 3))) : (win[2][1] >> (8 * ((i + 2) & 3)))) & 0xFFu;
+                constexpr int J = i + H;      // the pixel's window column
+                const uint32_t va = (win[H][J >> 2] >> (8 * (J & 3))) & 0xFFu;
                 uint32_t k0 = full1_anchor_key(va);
                 const uint32_t ta = (va >> 4) * (uint32_t)kStrideA;
-                int sum = u1p_pair<PAT, 0, i>(s_lut, win, k0, ta, acc[4 * c + i]);
+                int sum = u1p_pair<PAT, 0, i, H>(s_lut, win, k0, ta, acc[4 * c + i]);
                 asm volatile("" : "+v"(sum), "+v"(k0));      // one pair at a time (register budget)
-                acc[4 * c + i] = u1p_pair<PAT, 1, i>(s_lut, win, k0, ta, sum);
+                acc[4 * c + i] = u1p_pair<PAT, 1, i, H>(s_lut, win, k0, ta, sum);
             });
         }
     });
 }
 
-template <int TW, int TH, int NT, bool LIST>
+// HALO = 3 (never LIST): the kernel of the mode lists that hold a 4 x 4 pattern, any mix of the six patterns.  Its tile rows are
+// 72 bytes (64 + 2 x 3 columns, padded to whole dwords) x 70: LDS 83,536 + C x 5,040 = 98,656 B for C = 3, one workgroup per CU as
+// at HALO = 2 (97,408 B).  64 x 64 keeps the halo overhead at 1.23x the tile's pixels (a 32 x 32 tile would pay 1.52x).
+template <int TW, int TH, int NT, bool LIST, int HALO = kHalo>
 __global__ void __launch_bounds__(NT) stage_u1w_kernel(StageArgs a) {
-    constexpr int PW = TW + 2 * kHalo, PH = TH + 2 * kHalo;
+    constexpr int PW = (TW + 2 * HALO + 3) & ~3, PH = TH + 2 * HALO;      // rows start on dwords: 68 B at HALO = 2, 72 at HALO = 3
     static_assert(TW * TH == 4 * NT && PW % 4 == 0, "four adjacent pixels per thread, dword-aligned tile rows");
+    static_assert(HALO == kHalo || !LIST, "the tile marks of the tube kernel belong to the s / d / y lists");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ int s_found;      // list mode: the next marked unit
     const int8_t *s_lut = (const int8_t *)smem;
@@ -156,7 +166,7 @@ __global__ void __launch_bounds__(NT) stage_u1w_kernel(StageArgs a) {
         n5 = src_[c5];                                                                                              \
     } while (0)
     MULUT_U1_FETCH(a.lut[0]);
-    load_tile_batched<TW, TH, NT>(a, n, y0, x0, s_img);
+    load_tile_batched<TW, TH, NT, HALO, PW>(a, n, y0, x0, s_img);
     const int x4 = (int)(threadIdx.x % (TW / 4)) * 4, ty = (int)(threadIdx.x / (TW / 4));
     int acc[12];   // [channel][pixel]
 #pragma unroll
@@ -172,12 +182,23 @@ __global__ void __launch_bounds__(NT) stage_u1w_kernel(StageArgs a) {
         }
         if (mv + 1 < a.M) MULUT_U1_FETCH(a.lut[__builtin_amdgcn_readfirstlane(mv + 1)]);
         __syncthreads();  // table and (m == 0) tile in place
-        // pattern of this mode from its first key offset: s (0,1), d (0,2), y (1,1) -- scalar
-        const int pat = a.dj[m][0] == 2 ? 1 : a.di[m][0] == 1 ? 2 : 0;
         const uint8_t *img_c = s_img + c_lo * (PH * PW);
-        if (pat == 0) u1p_mode<0, PW, PH>(s_lut, img_c, ty, x4, c_n, acc);
-        else if (pat == 1) u1p_mode<1, PW, PH>(s_lut, img_c, ty, x4, c_n, acc);
-        else u1p_mode<2, PW, PH>(s_lut, img_c, ty, x4, c_n, acc);
+        if constexpr (HALO == kHalo) {
+            // pattern of this mode from its first key offset: s (0,1), d (0,2), y (1,1) -- scalar
+            const int pat = a.dj[m][0] == 2 ? 1 : a.di[m][0] == 1 ? 2 : 0;
+            if (pat == 0) u1p_mode<0, PW, PH, HALO>(s_lut, img_c, ty, x4, c_n, acc);
+            else if (pat == 1) u1p_mode<1, PW, PH, HALO>(s_lut, img_c, ty, x4, c_n, acc);
+            else u1p_mode<2, PW, PH, HALO>(s_lut, img_c, ty, x4, c_n, acc);
+        } else {
+            switch (pattern_id_of(a.di[m][0], a.dj[m][0], a.di[m][1])) {      // scalar: any of the six patterns
+                case 0: u1p_mode<0, PW, PH, HALO>(s_lut, img_c, ty, x4, c_n, acc); break;
+                case 1: u1p_mode<1, PW, PH, HALO>(s_lut, img_c, ty, x4, c_n, acc); break;
+                case 2: u1p_mode<2, PW, PH, HALO>(s_lut, img_c, ty, x4, c_n, acc); break;
+                case 3: u1p_mode<3, PW, PH, HALO>(s_lut, img_c, ty, x4, c_n, acc); break;
+                case 4: u1p_mode<4, PW, PH, HALO>(s_lut, img_c, ty, x4, c_n, acc); break;
+                default: u1p_mode<5, PW, PH, HALO>(s_lut, img_c, ty, x4, c_n, acc); break;
+            }
+        }
     }
     const int y = y0 + ty;
     if (y < a.oy1) {
@@ -212,6 +233,28 @@ hipError_t launch_stage_u1(const StageArgs &a, hipStream_t st) {
     }
     const long long nb = (long long)a.N * a.tiles_x * a.tiles_y;
     if (nb <= 0 || nb > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(K1_NT), lds, st, a);
+    return hipGetLastError();
+}
+
+// a list with a 4 x 4 pattern (any mix and repeat of the six patterns): the same kernel with a 3-px halo
+constexpr int kWide1LdsMax = kU1TableBytes + 3 * K3_PH * K3_PW;      // 98,656
+static_assert(K1_TW == K3_TW && K1_TH == K3_TH && K1_NT == K3_NT && ((K1_TW + 2 * kHalo3 + 3) & ~3) == K3_PW, "the kernel's tile at HALO = 3 is the K3_* tile of mulut_dev.h");
+hipError_t launch_stage_wide1(const StageArgs &a, hipStream_t st) {
+    if (a.C < 1 || a.C > 3 || a.M < 1 || a.M > kMaxModes) return hipErrorInvalidValue;
+    for (int m = 0; m < a.M; ++m) {      // every mode's offsets are those of the pattern the kernel will take them for
+        const int pat = pattern_id_of(a.di[m][0], a.dj[m][0], a.di[m][1]);
+        for (int k = 0; k < 3; ++k)
+            if (a.di[m][k] != kPatDi[pat][k] || a.dj[m][k] != kPatDj[pat][k]) return hipErrorInvalidValue;
+    }
+    auto kern = stage_u1w_kernel<K1_TW, K1_TH, K1_NT, false, kHalo3>;
+    {
+        const hipError_t e = raise_lds_limit((const void *)kern, kWide1LdsMax);
+        if (e != hipSuccess) return e;
+    }
+    const long long nb = (long long)a.N * a.tiles_x * a.tiles_y;
+    if (nb <= 0 || nb > 0x7fffffffLL) return hipErrorInvalidValue;
+    const size_t lds = (size_t)kU1TableBytes + (size_t)a.C * K3_PH * K3_PW;
     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(K1_NT), lds, st, a);
     return hipGetLastError();
 }

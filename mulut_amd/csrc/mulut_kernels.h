@@ -158,16 +158,17 @@ void stage_u1_tile(int &tw, int &th);
 void stage_up_tile(int &tw, int &th);
 const char *stage_up_name(int u, int out_mode);
 
-// mode lists with a 4 x 4 pattern (e, h, o: reach 3 per stage), mulut_wide.hip.  Every stage of such a list runs here, any mix and
-// repeat of the six patterns, up to kMaxModes modes; no tube band, work list or tile mark is involved.
-//   launch_stage_wide1   1-byte rows (non-final stages, a final stage with u == 1): one mode's whole table in LDS, swapped per mode
-//   launch_stage_wide_up u in {2,3,4}: rows gathered from the full tables in global memory, generic output layout
-struct PatternArgs {
-    int pat[kMaxModes];   // pattern of mode m: 0..5 = s, d, y, e, h, o (from the mode letter: the kernel takes one instance of its pass body per pattern)
-};
-hipError_t launch_stage_wide1(const StageArgs &a, const PatternArgs &w, hipStream_t st);
+// mode lists with a 4 x 4 pattern (e, h, o: reach 3 per stage).  Every stage of such a list runs on the halo-3 instances of the two
+// full-table kernels, any mix and repeat of the six patterns, up to kMaxModes modes; no tube band, work list or tile mark is involved.
+// The tiles are those of the families (stage_u1_tile, stage_up_tile).  mulut_kernel_name keeps the names these routes have always had:
+//   launch_stage_wide1   "stage_wide1_kernel" = stage_u1w_kernel<64, 64, 1024, false, 3> (mulut_k1.hip): 1-byte rows (non-final stages,
+//                        a final stage with u == 1), one mode's whole table in LDS, swapped per mode; the pattern of a mode is read from
+//                        its offsets (pattern_id_of)
+//   launch_stage_wide_up "stage_wide_up_kernel<u>" = stage_up_kernel<u, kOutGeneric, 32, 8, false, WIDE, 3> (mulut_kernels.hip), u in
+//                        {2,3,4}: rows gathered from the full tables in global memory, generic output layout; WIDE (per-rotation
+//                        accumulators) only for u == 4 with more than four modes
+hipError_t launch_stage_wide1(const StageArgs &a, hipStream_t st);
 hipError_t launch_stage_wide_up(const StageArgs &a, int u, hipStream_t st);
-void stage_wide_tile(int u, int &tw, int &th);
 const char *stage_wide_name(int u);
 
 // sampling intervals 5 and 6 (q = 32 / 64, L = 9 / 5), mulut_interval.hip.  Every stage of a context configured at these intervals
@@ -175,6 +176,9 @@ const char *stage_wide_name(int u);
 //   launch_stage_interval  lds: every table of the stage staged into LDS once per persistent workgroup (kIvLdsBudget), else rows
 //                          gathered from the tables in global memory; 64 x 64 tiles with a 3-px halo, 32-bit sums
 constexpr int kIvLdsBudget = 96 * 1024;      // the stage's tables (M * iv_table_bytes) go to LDS when they fit this
+struct PatternArgs {
+    int pat[kMaxModes];   // pattern of mode m: 0..5 = s, d, y, e, h, o (from the mode letter: the kernel takes one instance of its pass body per pattern)
+};
 struct IvArgs : PatternArgs {
     int reach;            // rows beyond [oy0, oy1) the caller's band holds (2, or 3 for a list with e, h or o)
     DivMagic dm;          // epilogue divisor / 2^(interval - 1): 2 M (final stage) or 8 M (mulut_interval.h iv_div_modes)

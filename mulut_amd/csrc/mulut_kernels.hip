@@ -228,9 +228,10 @@ __global__ void __launch_bounds__(256) tile_stat_kernel(StageArgs a, uint32_t *v
 // HY = false: one block per TW x TH tile.
 // HY = true (hybrid launch): four blocks per 64x16 verdict tile (its 2x2 sub-tiles); a block exits at once
 // unless the statistic marked the tile for this kernel (an empty block costs ~0.3 us of one CU).
-template <int U, int OUT, int TW, int TH, bool HY, bool WIDE = false>
+// HALO = 3: the final stage of a mode list that holds a 4 x 4 pattern (e, h, o); such a list is never routed.
+template <int U, int OUT, int TW, int TH, bool HY, bool WIDE = false, int HALO = kHalo>
 __global__ void __launch_bounds__(TW *TH, 4) stage_up_kernel(StageArgs a) {
-    constexpr int PW = TW + 2 * kHalo, PH = TH + 2 * kHalo;
+    constexpr int PW = TW + 2 * HALO, PH = TH + 2 * HALO;
     constexpr int NT = TW * TH;
     static_assert(!HY || (TW == 32 && TH == 8), "hybrid sub-tiling assumes 2x2 sub-tiles of 32x8 in a 64x16 tile");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -243,7 +244,7 @@ __global__ void __launch_bounds__(TW *TH, 4) stage_up_kernel(StageArgs a) {
     // routed launch of a u == 2 / u == 3 final stage (a.tile_list set, not HY): one workgroup per 64 x 64 tile of the tube-band kernel
     // (stage_u1t_kernel: its tile grid starts at (oy0, 0) like this one); it leaves at once unless that kernel marked the tile as
     // detailed and left it out, else walks the tile's TW x TH sub-tiles
-    const bool routed = !HY && a.tile_list != nullptr;
+    const bool routed = HALO == kHalo && !HY && a.tile_list != nullptr;
     int n_sub = 1, ky0 = 0, kx0 = 0;
     if constexpr (HY) {
         if ((int)a.verdict[id] != a.verdict_take) return;              // block-uniform
@@ -274,13 +275,14 @@ __global__ void __launch_bounds__(TW *TH, 4) stage_up_kernel(StageArgs a) {
         if (y0 >= a.oy1 || x0 >= a.W) continue;                         // block-uniform
         if (q) __syncthreads();                                         // everyone is done with the previous sub-tile's pixels
     }
-    {   // this group's tile (load_tile, strided by the group's NT threads)
+    {   // this group's tile: load_tile<TW, TH, NT, HALO> written out (through the call the non-hybrid halo-2 instances come out with other
+        // register assignments, one of them an instruction longer: the timed kernels would no longer be the parent's, profiles/wide_templates_asm.txt)
         const int total = a.C * PH * PW;
-        const int ylo = imax(a.oy0 - kHalo, 0), yhi = imin(a.oy1 + kHalo, a.H) - 1;
+        const int ylo = imax(a.oy0 - HALO, 0), yhi = imin(a.oy1 + HALO, a.H) - 1;
         for (int i = lt; i < total; i += NT) {
             const int px = i % PW, py = (i / PW) % PH, c = i / (PW * PH);
-            const int gy = imin(imax(y0 + py - kHalo, ylo), yhi);
-            const int gx = imin(imax(x0 + px - kHalo, 0), a.W - 1);
+            const int gy = imin(imax(y0 + py - HALO, ylo), yhi);
+            const int gx = imin(imax(x0 + px - HALO, 0), a.W - 1);
             s_img[i] = *view_addr(a.in, n, c, gy, gx);
         }
     }
@@ -292,7 +294,7 @@ __global__ void __launch_bounds__(TW *TH, 4) stage_up_kernel(StageArgs a) {
 
     uint32_t oR[U], oG[U], oB[U];
     for (int c = 0; c < a.C; ++c) {
-        const uint8_t *ctr = s_img + c * (PH * PW) + (ty + kHalo) * PW + (tx + kHalo);
+        const uint8_t *ctr = s_img + c * (PH * PW) + (ty + HALO) * PW + (tx + HALO);
         const int va = ctr[0];
         RotAcc<U, (U == 4) && !WIDE> acc;
         acc.clear();
@@ -379,6 +381,41 @@ hipError_t launch_stage_up_wide4(const StageArgs &a, hipStream_t st) {
     if (nb <= 0 || nb > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL((stage_up_kernel<4, kOutGeneric, K2_TW, K2_TH, false, true>), dim3((unsigned)nb), dim3(K2_TW * K2_TH), tile_bytes, st, a);
     return hipGetLastError();
+}
+
+// a list with a 4 x 4 pattern (any mix and repeat of the six patterns), u in {2,3,4}: the gather kernel with a 3-px halo, generic
+// output layout; u == 4 keeps one accumulator set per rotation beyond four modes, as launch_stage_up_wide4
+template <int U, bool WIDE>
+static hipError_t launch_wide_up_t(const StageArgs &a, hipStream_t st) {
+    constexpr int tile_bytes = ((3 * (K2_TH + 2 * kHalo3) * (K2_TW + 2 * kHalo3) + 15) / 16) * 16;
+    auto kern = stage_up_kernel<U, kOutGeneric, K2_TW, K2_TH, false, WIDE, kHalo3>;
+    {
+        const hipError_t e = raise_lds_limit((const void *)kern, tile_bytes);
+        if (e != hipSuccess) return e;
+    }
+    const long long nb = (long long)a.N * a.tiles_x * a.tiles_y;
+    if (nb <= 0 || nb > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(K2_TW * K2_TH), (size_t)tile_bytes, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_stage_wide_up(const StageArgs &a, int u, hipStream_t st) {
+    if (a.C < 1 || a.C > 3 || a.M < 1 || a.M > kMaxModes) return hipErrorInvalidValue;
+    switch (u) {
+        case 2: return launch_wide_up_t<2, false>(a, st);
+        case 3: return launch_wide_up_t<3, false>(a, st);
+        case 4: return a.M > 4 ? launch_wide_up_t<4, true>(a, st) : launch_wide_up_t<4, false>(a, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+const char *stage_wide_name(int u) {
+    switch (u) {
+        case 1: return "stage_wide1_kernel";
+        case 2: return "stage_wide_up_kernel<2>";
+        case 3: return "stage_wide_up_kernel<3>";
+        default: return "stage_wide_up_kernel<4>";
+    }
 }
 
 void stage_band_tile(int &tw, int &th) { tw = KB_TW; th = KB_TH; }

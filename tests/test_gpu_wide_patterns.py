@@ -1,5 +1,5 @@
 """The 4 x 4 sampling patterns e, h, o on the GPU (-m gpu): mode lists that hold one of them ("wide" lists, reach 3 per stage) run
-every stage on the kernels of mulut_wide.hip.  Checked bit-exactly against the host emulator of mulut_core.h
+every stage on the 3-px-halo instances of stage_u1w_kernel (mulut_k1.hip) and stage_up_kernel (mulut_kernels.hip).  Checked bit-exactly against the host emulator of mulut_core.h
 (tests/host_emul) and against the NumPy port of the reference's loop with e, h, o added to its pattern table for the test."""
 import ctypes
 import os

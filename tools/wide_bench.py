@@ -2,7 +2,7 @@
 """The 4 x 4 patterns against the 3 x 3 ones on the same work: 8 natural 1080p frames, 2 stages, x4, in one process, legs alternated.
 
   (a) sdy, forced to the full-table kernels (first_stage_kernel 2: stage_u1w_kernel; final_stage_kernel 1: stage_up_kernel)
-  (b) eho on the wide kernels (stage_wide1_kernel, stage_wide_up_kernel<4>)
+  (b) eho on the same two kernel templates instantiated with a 3-px halo (mulut_kernel_name: stage_wide1_kernel, stage_wide_up_kernel<4>)
 
 Both legs make the same number of passes (3 modes x 4 rotations per site and stage), with seeded synthetic tables.  Per leg and
 round: ms per frame of the whole pipeline call (after a warm-up, timed over more than a second of calls) and the per-stage time of
