@@ -496,7 +496,11 @@ static StageArgs stage_args(const mulut_ctx *ctx, int stage, const View &in, con
     const bool last = stage == ctx->stages;
     a.in = in; a.out = out;
     a.dbg = ctx->dbg;
-    a.in_padded = (in.p == ctx->ws[0] || in.p == ctx->ws[1]) ? 1 : 0;
+    // in_padded: the input lies inside a workspace buffer, at its base or anywhere behind it.  A sub-launch of a large batch reads its
+    // images from the middle of one, and what follows them there is more of the buffer or its padding (ensure_workspace).
+    a.in_padded = 0;
+    for (int k = 0; k < 2; ++k)
+        if (ctx->ws[k] && in.p >= ctx->ws[k] && in.p < ctx->ws[k] + ctx->ws_cap[k]) a.in_padded = 1;
     a.N = N; a.C = C; a.H = H; a.W = W;
     a.oy0 = oy0; a.oy1 = oy1;
     a.M = ctx->n_modes;

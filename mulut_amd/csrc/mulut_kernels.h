@@ -28,7 +28,7 @@ struct View {
 __host__ __device__ constexpr int row_dwords(int u) { return (u * u + 3) / 4; }
 
 struct StageArgs {
-    int in_padded;   // the input buffer is followed by >= 8 readable bytes (the context's workspace)
+    int in_padded;   // the input is followed by >= 8 readable bytes: it lies inside one of the context's workspace buffers
     View in, out;
     int N, C, H, W;         // logical (full-image) size of the stage input
     int oy0, oy1;           // LR rows whose outputs this launch produces

@@ -133,14 +133,19 @@ class MuLUTEngine:
         out = torch.empty(shape, dtype=torch.uint8, device=self.device)
         return out, (out[0] if squeeze else out)
 
-    def stage(self, stage, x, layout=LAYOUT_HWC, out_layout=None):
-        """One stage (all modes x 4 rotations + combine): sr/4_test_lut.py:280-306."""
+    def stage(self, stage, x, layout=LAYOUT_HWC, out_layout=None, out=None):
+        """One stage (all modes x 4 rotations + combine): sr/4_test_lut.py:280-306.  `out`: write into this tensor (as pipeline does)."""
         self._need_config()
         out_layout = layout if out_layout is None else out_layout
         squeeze = x.dim() == 3
         x4, N, H, W, C = self._dims(self._dev_u8(x, "x"), layout)
         u = self.scale if stage == self.stages else 1
-        out, ret = self._out(N, H * u, W * u, C, out_layout, squeeze)
+        if out is None:
+            out, ret = self._out(N, H * u, W * u, C, out_layout, squeeze)
+        else:
+            ret = self._dev_u8(out, "out")
+            if out.numel() != N * H * W * C * u * u:
+                raise ValueError("out has the wrong size")
         self._check(self._lib.mulut_stage(self._h, int(stage), x4.data_ptr(), layout, out.data_ptr(), out_layout, N, H,
                                           W, C, self._stream()))
         return ret
@@ -160,13 +165,18 @@ class MuLUTEngine:
                                              self._stream()))
         return ret
 
-    def pipeline_rows(self, band, band_row0, y0, y1, H_full, layout=LAYOUT_HWC):
+    def pipeline_rows(self, band, band_row0, y0, y1, H_full, layout=LAYOUT_HWC, out=None):
         """Strip form: `band` holds rows [band_row0, band_row0+rows) of H_full-row images; returns the
-        output for LR rows [y0, y1)."""
+        output for LR rows [y0, y1).  `out`: write into this tensor (as pipeline does)."""
         self._need_config()
         squeeze = band.dim() == 3
         b4, N, rows, W, C = self._dims(self._dev_u8(band, "band"), layout)
-        out, ret = self._out(N, (y1 - y0) * self.scale, W * self.scale, C, layout, squeeze)
+        if out is None:
+            out, ret = self._out(N, (y1 - y0) * self.scale, W * self.scale, C, layout, squeeze)
+        else:
+            ret = self._dev_u8(out, "out")
+            if out.numel() != N * (y1 - y0) * W * C * self.scale ** 2:
+                raise ValueError("out has the wrong size")
         self._check(self._lib.mulut_pipeline_rows(self._h, b4.data_ptr(), int(band_row0), rows, out.data_ptr(), int(y0),
                                                   int(y1), N, int(H_full), W, C, layout, self._stream()))
         return ret
