@@ -7,6 +7,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mulut.h"
@@ -15,74 +16,10 @@
 
 using namespace mulut;
 
-struct DevTable {
-    void *dev = nullptr;    // full table image
-    void *tube = nullptr;   // "tube" band (keys spanning <= 2 MSB steps): v_num 16: expanded to 16-bit fields, two planes of kTubeSlots x 16 B;
-                            // v_num 1: one dword per slot (kTube1BandBytes)
-    size_t tube_bytes = 0;
-    uint8_t *slab = nullptr; // v_num 16: the table as 16 anchor slab pairs (mulut_core.h), kSlabTableBytes
-    size_t slab_bytes = 0;
-    int vnum = 0;
-    size_t bytes = 0;
-};
-
-// tuning keys that choose a stage's route (plan_stage); the defaults take the routes that use every buffer any route does
-struct Routing {
-    int final_kernel = 0;   // tuning "final_stage_kernel": 0 auto (= 6), 1 full-table kernel, 5 tube kernel (all bands resident), 6 hybrid (tube)
-    int first_kernel = 0;   // tuning "first_stage_kernel", 1-byte-row stages: 0 auto (tube kernel, detailed tiles to the window kernel), 2 window kernel (full table in
-                            // LDS) on every tile, 3 tube kernel on every tile
-    int tube2 = 1;          // tuning "tube_pipelined": 1 = stage_tube2_kernel (hand-scheduled LDS reads) where the mode list has one, 0 = stage_tube_kernel
-    int detail_kernel = 0;  // tuning "detail_kernel": 0 = anchor slabs in LDS (when the launch qualifies), 1 = full-table gather kernel
-};
-
-struct mulut_ctx {
-    int device = 0;
-    bool configured = false;
-    int stages = 0, n_modes = 0, scale = 0, interval = 0;
-    int tab_interval = kInterval;   // the interval the tables in tab[][] were set for (configuring another one clears them)
-    char modes[MULUT_MAX_MODES + 1] = {0};
-    signed char di[MULUT_MAX_MODES][3], dj[MULUT_MAX_MODES][3];
-    int reach = 2;  // LR rows one stage looks beyond its output rows
-    bool wide = false;  // the mode list holds a 4 x 4 pattern (e, h, o): reach 3, every stage on the halo-3 instances of the full-table kernels
-    DevTable tab[MULUT_MAX_STAGES][6];  // [stage-1][pattern id s,d,y,e,h,o]
-    uint8_t *ws[2] = {nullptr, nullptr};
-    size_t ws_cap[2] = {0, 0};
+// Where a failing HIP call leaves its text (mulut_last_hip_error): the part of the context that what it owns reports into
+struct HipErr {
     std::string hip_err;
-    int num_cus = 256;
-    Routing routing;
-    int f32_ok[2] = {0, 0}; // float epilogue proven exact for the [non-final, final] divisor
-    int fma_ok = 0;         // fused (biased-sum) float epilogue proven exact for the final stage
-    float epi_c = 0.0f;
-    uint32_t *verdict = nullptr;   // per-tile smooth/detailed verdicts of the hybrid final stage
-    size_t verdict_cap = 0;
-    uint32_t *fix = nullptr;       // [0] = count, [16...] = entries of the fix-up list (samples recomputed from the full tables)
-    size_t fix_cap = 0;            // capacities in elements (here: header + ids)
-    unsigned long long *dbg = nullptr;   // probe buffer (mulut_debug_read), MULUT_DEBUG_WORDS words, allocated on first use
-    uint32_t *det_ctl = nullptr;   // detailed-tile path of the final stage (launch_detail_slab): counters, items, sample ids, blocks
-    uint32_t *det_items = nullptr, *det_desc = nullptr, *det_tpos = nullptr, *det_dlist = nullptr;
-    uint16_t *det_thist = nullptr;
-    uint4 *det_blocks = nullptr;
-    size_t det_items_cap = 0, det_ids_cap = 0, det_blocks_cap = 0, det_thist_cap = 0, det_tpos_cap = 0, det_dlist_cap = 0;
-    bool k1_valid = false;         // ctx->tlist holds the marks of the first-stage launch that produced the next stage's input ...
-    int k1_N = 0, k1_W = 0, k1_H = 0, k1_tiles_x = 0, k1_tiles_y = 0, k1_oy0 = 0, k1_oy1 = 0;   // ... of this shape ...
-    const uint8_t *k1_out = nullptr;                                      // ... written to this buffer
-    int stat_from_k1 = 1;          // tuning "stat_from_first_stage": the final stage's statistic looks only at tiles the first stage marked
-    int up_detail_per_1024 = 8;    // the same threshold for the routed x2 / x3 final stages (their detailed tiles go to the gather kernel; profiles/r04y_scale_bench.jsonl)
-    int u1_detail_per_1024 = 24;   // a tile goes to the full-table kernel when more than this share of its (sampled) 4-pixel groups spans > 1 MSB step
-    uint32_t *tlist = nullptr;     // [16 + tile] = 1: the tube kernel left this tile to the full-table kernel
-    size_t tlist_cap = 0;
-    int fma1_ok = 0;               // fused float epilogue proven exact for non-final stages
-    int hybrid_oob_per_1024 = 128; // a tile is "detailed" when more than 1/8 of its (sampled) sites leave the band
-    bool timing = false;
-    hipEvent_t ev[MULUT_MAX_STAGES + 1] = {};
-    hipEvent_t evk[MULUT_MAX_STAGES][2] = {};   // around each stage's dominant kernel
-    bool evk_set[MULUT_MAX_STAGES] = {};
-    int timed_stages = 0;
 };
-
-static int pattern_id(char m) {
-    return m == 's' ? 0 : m == 'd' ? 1 : m == 'y' ? 2 : m == 'e' ? 3 : m == 'h' ? 4 : m == 'o' ? 5 : -1;
-}
 
 #define HIP_TRY(ctx, expr)                                                                  \
     do {                                                                                    \
@@ -95,33 +32,150 @@ static int pattern_id(char m) {
 
 // Set-up calls that overwrite or free device memory a kernel of an earlier call may still read (tables, bands, slabs, work lists,
 // the workspaces) wait for the device first: the caller's streams are unknown here, and a non-blocking stream is not ordered
-// against the null stream the copies run on.  Only mulut_set_lut, the releasing branch of mulut_configure, grow() when it
+// against the null stream the copies run on.  Only mulut_set_lut, the releasing branch of mulut_configure, DevBuf::grow when it
 // reallocates and mulut_destroy come through here -- never a compute call that allocates nothing
-static int wait_for_device(mulut_ctx *ctx) {
+static int wait_for_device(HipErr *ctx) {
     HIP_TRY(ctx, hipDeviceSynchronize());
     return MULUT_OK;
 }
 
-// Device copy of a host image: the buffer is reallocated only when the size changes
-template <class P, class V>
-static int upload(mulut_ctx *ctx, P *&dev, size_t &bytes, const std::vector<V> &img) {
-    const size_t n = img.size() * sizeof(V);
-    if (dev && bytes != n) {
-        HIP_TRY(ctx, hipFree(dev));
-        dev = nullptr;
-    }
-    if (!dev) HIP_TRY(ctx, hipMalloc((void **)&dev, n));
-    bytes = n;
-    HIP_TRY(ctx, hipMemcpy(dev, img.data(), n, hipMemcpyHostToDevice));
-    return MULUT_OK;
-}
+// One device allocation and its only owner: move-only, freed when the owner dies (unchecked: nothing could act on a failure there).
+// Its members are the three ways the context sizes its memory; a HIP failure in any of them is MULUT_EHIP with hip_err set.
+// A new buffer of the context is a new member and nothing else.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;     // elements
 
-template <class P>
-static int release(mulut_ctx *ctx, P *&dev, size_t &bytes) {
-    if (dev) HIP_TRY(ctx, hipFree(dev));
-    dev = nullptr;
-    bytes = 0;
-    return MULUT_OK;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { return std::swap(p, o.p), std::swap(cap, o.cap), *this; }
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    explicit operator bool() const { return p != nullptr; }
+
+    // at least n elements: reallocated (contents dropped, after a wait for the device) only when it is too small
+    int grow(HipErr *ctx, size_t n) {
+        if (n <= cap) return MULUT_OK;
+        if (p) {
+            const int rc = wait_for_device(ctx);
+            if (rc) return rc;
+            HIP_TRY(ctx, hipFree(p));
+        }
+        p = nullptr;
+        cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&p, n * sizeof(T)));
+        cap = n;
+        return MULUT_OK;
+    }
+    // the device copy of a host image: reallocated only when the size changes
+    template <class V>
+    int upload(HipErr *ctx, const std::vector<V> &img) {
+        const size_t n = img.size() * sizeof(V) / sizeof(T);
+        if (p && cap != n) {
+            HIP_TRY(ctx, hipFree(p));
+            p = nullptr;
+        }
+        if (!p) HIP_TRY(ctx, hipMalloc((void **)&p, n * sizeof(T)));
+        cap = n;
+        HIP_TRY(ctx, hipMemcpy(p, img.data(), n * sizeof(T), hipMemcpyHostToDevice));
+        return MULUT_OK;
+    }
+    int release(HipErr *ctx) {
+        if (p) HIP_TRY(ctx, hipFree(p));
+        p = nullptr;
+        cap = 0;
+        return MULUT_OK;
+    }
+};
+
+struct DevTable {
+    DevBuf<uint8_t> dev;    // full table image
+    DevBuf<uint8_t> tube;   // "tube" band (keys spanning <= 2 MSB steps): v_num 16: expanded to 16-bit fields, two planes of kTubeSlots x 16 B;
+                            // v_num 1: one dword per slot (kTube1BandBytes)
+    DevBuf<uint8_t> slab;   // v_num 16: the table as 16 anchor slab pairs (mulut_core.h), kSlabTableBytes
+    int vnum = 0;
+
+    int clear(HipErr *ctx) {
+        int rc = dev.release(ctx);
+        if (!rc) rc = tube.release(ctx);
+        if (!rc) rc = slab.release(ctx);
+        if (!rc) vnum = 0;
+        return rc;
+    }
+};
+
+// Buffers of the detailed-tile path of the final stage (launch_detail_slab): counters, items, sample ids, blocks
+struct DetailBufs {
+    DevBuf<uint32_t> ctl, items, desc, tpos, dlist;
+    DevBuf<uint16_t> thist;
+    DevBuf<uint4> blocks;
+
+    void fill(DetailArgs &d) const {
+        d.ctl = ctl.p; d.items = items.p; d.desc = desc.p; d.blocks = blocks.p;
+        d.thist = thist.p; d.tpos = tpos.p; d.dlist = dlist.p;
+    }
+};
+
+// An event of the stage timing: created on first use (mulut_set_stage_timing), destroyed with its owner
+struct DevEvent {
+    hipEvent_t e = nullptr;
+
+    DevEvent() = default;
+    DevEvent(DevEvent &&) = delete;
+    ~DevEvent() {
+        if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// tuning keys that choose a stage's route (plan_stage); the defaults take the routes that use every buffer any route does
+struct Routing {
+    int final_kernel = 0;   // tuning "final_stage_kernel": 0 auto (= 6), 1 full-table kernel, 5 tube kernel (all bands resident), 6 hybrid (tube)
+    int first_kernel = 0;   // tuning "first_stage_kernel", 1-byte-row stages: 0 auto (tube kernel, detailed tiles to the window kernel), 2 window kernel (full table in
+                            // LDS) on every tile, 3 tube kernel on every tile
+    int tube2 = 1;          // tuning "tube_pipelined": 1 = stage_tube2_kernel (hand-scheduled LDS reads) where the mode list has one, 0 = stage_tube_kernel
+    int detail_kernel = 0;  // tuning "detail_kernel": 0 = anchor slabs in LDS (when the launch qualifies), 1 = full-table gather kernel
+};
+
+struct mulut_ctx : HipErr {
+    int device = 0;
+    bool configured = false;
+    int stages = 0, n_modes = 0, scale = 0, interval = 0;
+    int tab_interval = kInterval;   // the interval the tables in tab[][] were set for (configuring another one clears them)
+    char modes[MULUT_MAX_MODES + 1] = {0};
+    signed char di[MULUT_MAX_MODES][3], dj[MULUT_MAX_MODES][3];
+    int reach = 2;  // LR rows one stage looks beyond its output rows
+    bool wide = false;  // the mode list holds a 4 x 4 pattern (e, h, o): reach 3, every stage on the halo-3 instances of the full-table kernels
+    DevTable tab[MULUT_MAX_STAGES][6];  // [stage-1][pattern id s,d,y,e,h,o]
+    DevBuf<uint8_t> ws[2];
+    int num_cus = 256;
+    Routing routing;
+    int f32_ok[2] = {0, 0}; // float epilogue proven exact for the [non-final, final] divisor
+    int fma_ok = 0;         // fused (biased-sum) float epilogue proven exact for the final stage
+    float epi_c = 0.0f;
+    DevBuf<uint32_t> verdict;      // per-tile smooth/detailed verdicts of the hybrid final stage
+    DevBuf<uint32_t> fix;          // [0] = count, [16...] = entries of the fix-up list (samples recomputed from the full tables)
+    DevBuf<unsigned long long> dbg;      // probe buffer (mulut_debug_read), MULUT_DEBUG_WORDS words, allocated on first use
+    DetailBufs det;
+    bool k1_valid = false;         // ctx->tlist holds the marks of the first-stage launch that produced the next stage's input ...
+    int k1_N = 0, k1_W = 0, k1_H = 0, k1_tiles_x = 0, k1_tiles_y = 0, k1_oy0 = 0, k1_oy1 = 0;   // ... of this shape ...
+    const uint8_t *k1_out = nullptr;                                      // ... written to this buffer
+    int stat_from_k1 = 1;          // tuning "stat_from_first_stage": the final stage's statistic looks only at tiles the first stage marked
+    int up_detail_per_1024 = 8;    // the same threshold for the routed x2 / x3 final stages (their detailed tiles go to the gather kernel; profiles/r04y_scale_bench.jsonl)
+    int u1_detail_per_1024 = 24;   // a tile goes to the full-table kernel when more than this share of its (sampled) 4-pixel groups spans > 1 MSB step
+    DevBuf<uint32_t> tlist;        // [16 + tile] = 1: the tube kernel left this tile to the full-table kernel
+    int fma1_ok = 0;               // fused float epilogue proven exact for non-final stages
+    int hybrid_oob_per_1024 = 128; // a tile is "detailed" when more than 1/8 of its (sampled) sites leave the band
+    bool timing = false;
+    DevEvent ev[MULUT_MAX_STAGES + 1];
+    DevEvent evk[MULUT_MAX_STAGES][2];          // around each stage's dominant kernel
+    bool evk_set[MULUT_MAX_STAGES] = {};
+    int timed_stages = 0;
+};
+
+static int pattern_id(char m) {
+    return m == 's' ? 0 : m == 'd' ? 1 : m == 'y' ? 2 : m == 'e' ? 3 : m == 'h' ? 4 : m == 'o' ? 5 : -1;
 }
 
 // Tube band of a table with u x u-value rows (img: its device image): the rows with max - min of the keys <= 2, at tube_slot().
@@ -170,22 +224,6 @@ static std::vector<uint8_t> slab_pairs(const std::vector<uint8_t> &img) {
     return sl;
 }
 
-// Device buffer of at least n elements: reallocated (contents dropped) only when it is too small; cap counts elements
-template <class T>
-static int grow(mulut_ctx *ctx, T *&p, size_t &cap, size_t n) {
-    if (n <= cap) return MULUT_OK;
-    if (p) {
-        const int rc = wait_for_device(ctx);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipFree(p));
-    }
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(ctx, hipMalloc((void **)&p, n * sizeof(T)));
-    cap = n;
-    return MULUT_OK;
-}
-
 extern "C" {
 
 int mulut_version(void) { return MULUT_VERSION; }
@@ -231,32 +269,7 @@ int mulut_create(int device_id, mulut_ctx **out_ctx) {
 int mulut_destroy(mulut_ctx *ctx) {
     if (!ctx) return MULUT_EINVAL;
     (void)hipSetDevice(ctx->device);
-    (void)wait_for_device(ctx);     // kernels still queued read what is freed below
-    for (auto &st : ctx->tab)
-        for (auto &t : st)
-        {
-            if (t.dev) (void)hipFree(t.dev);
-            if (t.tube) (void)hipFree(t.tube);
-            if (t.slab) (void)hipFree(t.slab);
-        }
-    for (auto &w : ctx->ws)
-        if (w) (void)hipFree(w);
-    if (ctx->verdict) (void)hipFree(ctx->verdict);
-    if (ctx->fix) (void)hipFree(ctx->fix);
-    if (ctx->tlist) (void)hipFree(ctx->tlist);
-    if (ctx->dbg) (void)hipFree(ctx->dbg);
-    if (ctx->det_ctl) (void)hipFree(ctx->det_ctl);
-    if (ctx->det_items) (void)hipFree(ctx->det_items);
-    if (ctx->det_desc) (void)hipFree(ctx->det_desc);
-    if (ctx->det_thist) (void)hipFree(ctx->det_thist);
-    if (ctx->det_tpos) (void)hipFree(ctx->det_tpos);
-    if (ctx->det_dlist) (void)hipFree(ctx->det_dlist);
-    if (ctx->det_blocks) (void)hipFree(ctx->det_blocks);
-    for (auto &e : ctx->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &p : ctx->evk)
-        for (auto &e : p)
-            if (e) (void)hipEventDestroy(e);
+    (void)wait_for_device(ctx);     // kernels still queued read what the context's members free as they die
     delete ctx;
     return MULUT_OK;
 }
@@ -287,11 +300,8 @@ int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, in
         if (wrc) return wrc;
         for (auto &st : ctx->tab)
             for (auto &t : st) {
-                int rc = release(ctx, t.dev, t.bytes);
-                if (!rc) rc = release(ctx, t.tube, t.tube_bytes);
-                if (!rc) rc = release(ctx, t.slab, t.slab_bytes);
+                const int rc = t.clear(ctx);
                 if (rc) return rc;
-                t.vnum = 0;
             }
         ctx->tab_interval = interval;
     }
@@ -348,9 +358,9 @@ int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows,
         const int rb = iv_row_bytes(u);
         std::vector<uint8_t> img((size_t)iv_table_bytes((int)rows, u), 0);
         for (int64_t i = 0; i < rows; ++i) memcpy(&img[(size_t)i * rb], host_rows + i * vnum, (size_t)vnum);
-        int rc = upload(ctx, t.dev, t.bytes, img);
-        if (!rc) rc = release(ctx, t.tube, t.tube_bytes);
-        if (!rc) rc = release(ctx, t.slab, t.slab_bytes);
+        int rc = t.dev.upload(ctx, img);
+        if (!rc) rc = t.tube.release(ctx);
+        if (!rc) rc = t.slab.release(ctx);
         if (rc) return rc;
         t.vnum = vnum;
         return MULUT_OK;
@@ -365,23 +375,23 @@ int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows,
         for (int64_t i = 0; i < kRows; ++i)
             for (int e = 0; e < vnum; ++e) img[(size_t)i * rb + e] = (uint8_t)((int)host_rows[i * vnum + e] + 128);
     }
-    int rc = upload(ctx, t.dev, t.bytes, img);
+    int rc = t.dev.upload(ctx, img);
     if (rc) return rc;
     t.vnum = vnum;
     // e / h / o tables: the wide kernels gather from the full table only (no tube band, no anchor slabs)
     const bool band = pattern_reach(mode) <= 2;
-    rc = band ? upload(ctx, t.tube, t.tube_bytes, tube_band(u, host_rows, img)) : release(ctx, t.tube, t.tube_bytes);
+    rc = band ? t.tube.upload(ctx, tube_band(u, host_rows, img)) : t.tube.release(ctx);
     if (rc) return rc;
-    return band && u == 4 ? upload(ctx, t.slab, t.slab_bytes, slab_pairs(img)) : release(ctx, t.slab, t.slab_bytes);
+    return band && u == 4 ? t.slab.upload(ctx, slab_pairs(img)) : t.slab.release(ctx);
 }
 
 // bracket the dominant kernel of a stage with events when timing is on (mulut_last_kernel_ms)
 #define MAIN_KERNEL(ctx, stage, st, launch)                                                   \
     do {                                                                                      \
-        if ((ctx)->timing) HIP_TRY(ctx, hipEventRecord((ctx)->evk[(stage) - 1][0], st));      \
+        if ((ctx)->timing) HIP_TRY(ctx, hipEventRecord((ctx)->evk[(stage) - 1][0].e, st));      \
         HIP_TRY(ctx, launch);                                                                 \
         if ((ctx)->timing) {                                                                  \
-            HIP_TRY(ctx, hipEventRecord((ctx)->evk[(stage) - 1][1], st));                      \
+            HIP_TRY(ctx, hipEventRecord((ctx)->evk[(stage) - 1][1].e, st));                      \
             (ctx)->evk_set[(stage) - 1] = true;                                               \
         }                                                                                     \
     } while (0)
@@ -395,7 +405,7 @@ static int stage_tables(const mulut_ctx *ctx, int stage, const void **lut) {
         const DevTable &t = ctx->tab[stage - 1][pattern_id(ctx->modes[m])];
         if (!t.dev) return MULUT_ENOLUT;
         if (t.vnum != vnum) return MULUT_ESHAPE;
-        lut[m] = t.dev;
+        lut[m] = t.dev.p;
     }
     return MULUT_OK;
 }
@@ -414,7 +424,7 @@ int mulut_pass(mulut_ctx *ctx, int stage, char mode, int r, const uint8_t *in_ch
     PassArgs a;
     a.in = in_chw;
     a.out = out_q;
-    a.lut = t.dev;
+    a.lut = t.dev.p;
     a.C = C; a.H = H; a.W = W; a.u = u; a.r = r;
     int di[3], dj[3];
     pattern_offsets(mode, di, dj);
@@ -495,12 +505,12 @@ static StageArgs stage_args(const mulut_ctx *ctx, int stage, const View &in, con
     memset(&a, 0, sizeof(a));
     const bool last = stage == ctx->stages;
     a.in = in; a.out = out;
-    a.dbg = ctx->dbg;
+    a.dbg = ctx->dbg.p;
     // in_padded: the input lies inside a workspace buffer, at its base or anywhere behind it.  A sub-launch of a large batch reads its
     // images from the middle of one, and what follows them there is more of the buffer or its padding (ensure_workspace).
     a.in_padded = 0;
     for (int k = 0; k < 2; ++k)
-        if (ctx->ws[k] && in.p >= ctx->ws[k] && in.p < ctx->ws[k] + ctx->ws_cap[k]) a.in_padded = 1;
+        if (ctx->ws[k] && in.p >= ctx->ws[k].p && in.p < ctx->ws[k].p + ctx->ws[k].cap) a.in_padded = 1;
     a.N = N; a.C = C; a.H = H; a.W = W;
     a.oy0 = oy0; a.oy1 = oy1;
     a.M = ctx->n_modes;
@@ -608,20 +618,22 @@ static StagePlan plan_stage(const mulut_ctx *ctx, const Routing &r, int u, const
 // Device buffers a plan needs (grown, never shrunk)
 static int ensure_plan(mulut_ctx *ctx, const StagePlan &p) {
     int rc = MULUT_OK;
-    if (p.fix_ids) rc = grow(ctx, ctx->fix, ctx->fix_cap, p.fix_ids + 16);
-    if (!rc && p.tlist_tiles) rc = grow(ctx, ctx->tlist, ctx->tlist_cap, p.tlist_tiles + 16);
-    if (!rc && p.verdict_tiles) rc = grow(ctx, ctx->verdict, ctx->verdict_cap, p.verdict_tiles);
+    if (p.fix_ids) rc = ctx->fix.grow(ctx, p.fix_ids + 16);      // (header + ids)
+    if (!rc && p.tlist_tiles) rc = ctx->tlist.grow(ctx, p.tlist_tiles + 16);
+    if (!rc && p.verdict_tiles) rc = ctx->verdict.grow(ctx, p.verdict_tiles);
     if (rc || !p.det_tiles) return rc;
-    if (!ctx->det_ctl) {
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->det_ctl, kDetCtlDwords * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMemset(ctx->det_ctl, 0, kDetCtlDwords * sizeof(uint32_t)));
+    DetailBufs &d = ctx->det;
+    if (!d.ctl) {
+        rc = d.ctl.grow(ctx, kDetCtlDwords);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemset(d.ctl.p, 0, kDetCtlDwords * sizeof(uint32_t)));
     }
-    rc = grow(ctx, ctx->det_thist, ctx->det_thist_cap, p.det_tiles * 16);
-    if (!rc) rc = grow(ctx, ctx->det_tpos, ctx->det_tpos_cap, p.det_tiles * 16);
-    if (!rc) rc = grow(ctx, ctx->det_dlist, ctx->det_dlist_cap, p.det_tiles);
-    if (!rc) rc = grow(ctx, ctx->det_items, ctx->det_items_cap, p.det_items * 2);
-    if (!rc) rc = grow(ctx, ctx->det_desc, ctx->det_ids_cap, p.det_ids);
-    if (!rc) rc = grow(ctx, ctx->det_blocks, ctx->det_blocks_cap, p.det_blocks);
+    rc = d.thist.grow(ctx, p.det_tiles * 16);
+    if (!rc) rc = d.tpos.grow(ctx, p.det_tiles * 16);
+    if (!rc) rc = d.dlist.grow(ctx, p.det_tiles);
+    if (!rc) rc = d.items.grow(ctx, p.det_items * 2);
+    if (!rc) rc = d.desc.grow(ctx, p.det_ids);
+    if (!rc) rc = d.blocks.grow(ctx, p.det_blocks);
     return rc;
 }
 
@@ -678,18 +690,18 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
     if ((unsigned long long)N * p.per_image >= p.width) return MULUT_EUNSUPPORTED;     // (one image beyond a width: run_stage splits batches)
     rc = ensure_plan(ctx, p);
     if (rc) return rc;
-    a.fix_count = ctx->fix;
-    a.fix_list = ctx->fix + 16;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->fix, 0, sizeof(uint32_t), st));
+    a.fix_count = ctx->fix.p;
+    a.fix_list = ctx->fix.p + 16;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->fix.p, 0, sizeof(uint32_t), st));
     BandArgs b;
-    for (int m = 0; m < ctx->n_modes; ++m) b.band[m] = ctx->tab[stage - 1][pattern_id(ctx->modes[m])].tube;
+    for (int m = 0; m < ctx->n_modes; ++m) b.band[m] = ctx->tab[stage - 1][pattern_id(ctx->modes[m])].tube.p;
     if (p.route == kRouteU1Tube || p.route == kRouteUpTube) {
         StageArgs g = a;            // the gather kernel's launch on the tiles the tube kernel leaves (its own tiling)
         tile_grid(g, stage_up_tile, g.tiles_x, g.tiles_y);
-        if (p.routed) HIP_TRY(ctx, hipMemsetAsync(ctx->tlist, 0, (16 + p.tlist_tiles) * sizeof(uint32_t), st));
+        if (p.routed) HIP_TRY(ctx, hipMemsetAsync(ctx->tlist.p, 0, (16 + p.tlist_tiles) * sizeof(uint32_t), st));
         if (p.route == kRouteU1Tube || p.routed) {
-            a.tile_count = ctx->tlist;
-            a.tile_list = ctx->tlist + 16;
+            a.tile_count = ctx->tlist.p;
+            a.tile_list = ctx->tlist.p + 16;
         }
         a.verdict_take = p.routed ? 0 : -1;
         if (p.route == kRouteUpTube) {
@@ -708,7 +720,7 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
         return MULUT_OK;
     }
     // (a launch without the slab path leaves none of an earlier launch's counters behind: mulut_last_detail_counters)
-    if (!p.slab && ctx->det_ctl) HIP_TRY(ctx, hipMemsetAsync(ctx->det_ctl, 0, kDetCtlDwords * sizeof(uint32_t), st));
+    if (!p.slab && ctx->det.ctl) HIP_TRY(ctx, hipMemsetAsync(ctx->det.ctl.p, 0, kDetCtlDwords * sizeof(uint32_t), st));
     auto tube = [&]() {
         return p.tube2 ? launch_stage_tube2(a, b, p.out_mode, ctx->num_cus, st) : launch_stage_tube(a, b, p.out_mode, ctx->num_cus, st);
     };
@@ -718,14 +730,14 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
         return MULUT_OK;
     }
     // the control words of the slab path are cleared before the statistic: it raises ctl[kDetAny] when it marks a tile
-    if (p.slab) HIP_TRY(ctx, hipMemsetAsync(ctx->det_ctl, 0, kDetCtlDwords * sizeof(uint32_t), st));
+    if (p.slab) HIP_TRY(ctx, hipMemsetAsync(ctx->det.ctl.p, 0, kDetCtlDwords * sizeof(uint32_t), st));
     if (ctx->stat_from_k1 && k1_marks) {
-        a.k1_hdr = ctx->tlist;
+        a.k1_hdr = ctx->tlist.p;
         a.k1_tiles_x = ctx->k1_tiles_x; a.k1_tiles_y = ctx->k1_tiles_y; a.k1_oy0 = ctx->k1_oy0; a.k1_n0 = k1_n0;
     }
-    HIP_TRY(ctx, launch_tile_stat(a, ctx->verdict, (uint32_t)ctx->hybrid_oob_per_1024, st, p.slab ? ctx->det_thist : nullptr, p.slab ? ctx->det_ctl + kDetAny : nullptr));
+    HIP_TRY(ctx, launch_tile_stat(a, ctx->verdict.p, (uint32_t)ctx->hybrid_oob_per_1024, st, p.slab ? ctx->det.thist.p : nullptr, p.slab ? ctx->det.ctl.p + kDetAny : nullptr));
     a.k1_hdr = nullptr;
-    a.verdict = ctx->verdict;
+    a.verdict = ctx->verdict.p;
     a.vt_x = a.tiles_x;
     a.vt_y = a.tiles_y;
     a.verdict_take = 0;
@@ -733,9 +745,8 @@ static int run_stage_one(mulut_ctx *ctx, int stage, const View &in, const View &
     if (p.slab) {
         DetailArgs d;
         memset(&d, 0, sizeof(d));
-        d.ctl = ctx->det_ctl; d.items = ctx->det_items; d.desc = ctx->det_desc; d.blocks = ctx->det_blocks;
-        d.thist = ctx->det_thist; d.tpos = ctx->det_tpos; d.dlist = ctx->det_dlist;
-        for (int m = 0; m < 3; ++m) d.slab[m] = m < ctx->n_modes ? ctx->tab[stage - 1][pattern_id(ctx->modes[m])].slab : nullptr;
+        ctx->det.fill(d);
+        for (int m = 0; m < 3; ++m) d.slab[m] = m < ctx->n_modes ? ctx->tab[stage - 1][pattern_id(ctx->modes[m])].slab.p : nullptr;
         HIP_TRY(ctx, launch_detail_slab(a, d, p.out_mode, ctx->num_cus, st));
     } else {
         StageArgs g = a;
@@ -782,7 +793,7 @@ int mulut_halo(const mulut_ctx *ctx) { return (ctx && ctx->configured) ? ctx->re
 
 static int ensure_workspace(mulut_ctx *ctx, size_t bytes) {
     int rc = MULUT_OK;
-    for (int k = 0; k < 2 && !rc; ++k) rc = grow(ctx, ctx->ws[k], ctx->ws_cap[k], bytes + 64);      // + padding: kernels may read whole dwords / 8 bytes at the very end (StageArgs::in_padded)
+    for (int k = 0; k < 2 && !rc; ++k) rc = ctx->ws[k].grow(ctx, bytes + 64);      // + padding: kernels may read whole dwords / 8 bytes at the very end (StageArgs::in_padded)
     return rc;
 }
 
@@ -868,7 +879,7 @@ int mulut_pipeline_rows(mulut_ctx *ctx, const uint8_t *in, int in_row0, int in_r
         const int Cg = imin(3, C - c0);
         View cur = make_view(in, layout, in_rows, W, C, in_row0);
         cur.p += (long long)c0 * cur.sC;
-        if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], (hipStream_t)stream));
+        if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0].e, (hipStream_t)stream));
         for (int s = 1; s <= S; ++s) {
             const int u = stage_u(ctx, s);
             View dst;
@@ -878,12 +889,12 @@ int mulut_pipeline_rows(mulut_ctx *ctx, const uint8_t *in, int in_row0, int in_r
                 dst.p += (long long)c0 * dst.sC;
                 dst_layout = layout;
             } else {
-                dst = make_view(ctx->ws[s & 1], MULUT_LAYOUT_CHW, hi[s] - lo[s], W, Cg, lo[s]);
+                dst = make_view(ctx->ws[s & 1].p, MULUT_LAYOUT_CHW, hi[s] - lo[s], W, Cg, lo[s]);
                 dst_layout = MULUT_LAYOUT_CHW;
             }
             int rc = run_stage(ctx, s, cur, dst, dst_layout, N, H, W, Cg, lo[s], hi[s], (hipStream_t)stream, C <= 3);
             if (rc) return rc;
-            if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[s], (hipStream_t)stream));
+            if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[s].e, (hipStream_t)stream));
             cur = dst;
         }
     }
@@ -904,10 +915,10 @@ int mulut_set_stage_timing(mulut_ctx *ctx, int enable) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (enable) {
         for (auto &e : ctx->ev)
-            if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+            if (!e.e) HIP_TRY(ctx, hipEventCreate(&e.e));
         for (auto &p : ctx->evk)
             for (auto &e : p)
-                if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+                if (!e.e) HIP_TRY(ctx, hipEventCreate(&e.e));
     }
     for (auto &f : ctx->evk_set) f = false;
     ctx->timing = enable != 0;
@@ -918,29 +929,29 @@ int mulut_set_stage_timing(mulut_ctx *ctx, int enable) {
 int mulut_last_stage_ms(mulut_ctx *ctx, float *ms, int cap) {
     if (!ctx || !ms || cap <= 0) return MULUT_EINVAL;
     const int n = ctx->timed_stages < cap ? ctx->timed_stages : cap;
-    if (n > 0) HIP_TRY(ctx, hipEventSynchronize(ctx->ev[ctx->timed_stages]));
-    for (int s = 0; s < n; ++s) HIP_TRY(ctx, hipEventElapsedTime(&ms[s], ctx->ev[s], ctx->ev[s + 1]));
+    if (n > 0) HIP_TRY(ctx, hipEventSynchronize(ctx->ev[ctx->timed_stages].e));
+    for (int s = 0; s < n; ++s) HIP_TRY(ctx, hipEventElapsedTime(&ms[s], ctx->ev[s].e, ctx->ev[s + 1].e));
     return n;
 }
 
 int mulut_last_kernel_ms(mulut_ctx *ctx, float *ms, int cap) {
     if (!ctx || !ms || cap <= 0) return MULUT_EINVAL;
     const int n = ctx->timed_stages < cap ? ctx->timed_stages : cap;
-    if (n > 0) HIP_TRY(ctx, hipEventSynchronize(ctx->ev[ctx->timed_stages]));
+    if (n > 0) HIP_TRY(ctx, hipEventSynchronize(ctx->ev[ctx->timed_stages].e));
     for (int s = 0; s < n; ++s) {
         ms[s] = 0.0f;
-        if (ctx->evk_set[s]) HIP_TRY(ctx, hipEventElapsedTime(&ms[s], ctx->evk[s][0], ctx->evk[s][1]));
+        if (ctx->evk_set[s]) HIP_TRY(ctx, hipEventElapsedTime(&ms[s], ctx->evk[s][0].e, ctx->evk[s][1].e));
     }
     return n;
 }
 
 int mulut_last_detail_counters(mulut_ctx *ctx, uint32_t *out, int cap, void *stream) {
     if (!ctx || !out || cap <= 0) return MULUT_EINVAL;
-    if (!ctx->det_ctl || !ctx->fix) return 0;
+    if (!ctx->det.ctl || !ctx->fix) return 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t ctl[kDetCtlDwords], fixn = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(ctl, ctx->det_ctl, sizeof(ctl), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&fixn, ctx->fix, sizeof(fixn), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctl, ctx->det.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&fixn, ctx->fix.p, sizeof(fixn), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(ctx, hipStreamSynchronize((hipStream_t)stream));
     int n = 0;
     for (int k = 0; k < 16 && n < cap; ++k) out[n++] = ctl[k];
@@ -954,12 +965,13 @@ int mulut_debug_read(mulut_ctx *ctx, unsigned long long *out, int cap, int reset
     if (!ctx || (cap > 0 && !out) || cap < 0) return MULUT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->dbg) {
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->dbg, MULUT_DEBUG_WORDS * sizeof(unsigned long long)));
-        HIP_TRY(ctx, hipMemset(ctx->dbg, 0, MULUT_DEBUG_WORDS * sizeof(unsigned long long)));
+        const int rc = ctx->dbg.grow(ctx, MULUT_DEBUG_WORDS);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemset(ctx->dbg.p, 0, MULUT_DEBUG_WORDS * sizeof(unsigned long long)));
     }
     const int n = cap < MULUT_DEBUG_WORDS ? cap : MULUT_DEBUG_WORDS;
-    if (n > 0) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->dbg, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    if (reset) HIP_TRY(ctx, hipMemsetAsync(ctx->dbg, 0, MULUT_DEBUG_WORDS * sizeof(unsigned long long), (hipStream_t)stream));
+    if (n > 0) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->dbg.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    if (reset) HIP_TRY(ctx, hipMemsetAsync(ctx->dbg.p, 0, MULUT_DEBUG_WORDS * sizeof(unsigned long long), (hipStream_t)stream));
     HIP_TRY(ctx, hipStreamSynchronize((hipStream_t)stream));
     return n;
 }

@@ -81,6 +81,20 @@ struct FtArgs {
     int di[kMaxFtModes][3], dj[kMaxFtModes][3];
 };
 
+// FtArgs with tiles_per_wg, and where it is: the arguments of the interval-5 / 6 kernels (mulut_ft_interval.hip).  Not FtArgs with the
+// field appended: behind di / dj the backward kernels fetch it with a scalar load of its own (next to is_last the two come as one),
+// and in the middle of FtArgs it would move the argument offsets of the interval-4 kernels.  `inside` is mandatory here.
+struct FtIvArgs {
+    const float *w[kMaxFtModes];
+    float *gw[kMaxFtModes];
+    const float *x, *gout;
+    float *out, *gx;
+    uint16_t *inside;
+    int B, C, H, W, u, M, is_last;
+    int tiles_per_wg;     // backward: consecutive tiles of sites a workgroup walks
+    int di[kMaxFtModes][3], dj[kMaxFtModes][3];
+};
+
 // float add into LDS as ds_add_f32: an atomicAdd on a pointer the compiler cannot prove to be LDS (here: one of two targets chosen
 // at run time) becomes flat_atomic_add_f32, which reaches the LDS through the texture path
 __device__ __forceinline__ void lds_add_f32(float *p, float v) {
@@ -111,7 +125,7 @@ __device__ __forceinline__ int eo_of_elem(int r, int e) {      // block position
 // bad call gets -- is part of the ABI (include/mulut.h).  need_mask: the entry point cannot do without `inside`; interval_ok: the
 // caller's own verdict on its interval argument (entry points without one pass true); max_reach: the largest pattern reach the entry
 // point accepts, i.e. the largest HALO its backward kernels are instantiated for (2: s, d, y; 3: e, h, o as well).
-// Args: FtArgs, or FtIvArgs of mulut_ft_interval.hip.
+// Args: FtArgs or FtIvArgs.
 template <class Args>
 static inline int ft_fill(Args &a, bool interval_ok, const float *const *weights, float *const *grad_wq, const char *modes, int is_last, int u,
                    const float *x, const uint16_t *inside, bool need_mask, int max_reach, int B, int C, int H, int W) {
@@ -147,13 +161,11 @@ static inline int ft_halo(const Args &a) {
     return r;
 }
 
-// Interval 4 of mulut_ft_wide_stage_forward / _backward (defined in mulut_ft.hip next to the kernels; the entry points themselves are
-// in mulut_ft_interval.hip).  The arguments have passed ft_fill there; these fill an FtArgs and launch HALO = 3, or HALO = 2 for a
-// list of s, d, y alone.
-int ft_wide4_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x, int B, int C, int H, int W,
-                     float *out, uint16_t *inside, void *stream);
-int ft_wide4_backward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x, const float *grad_out,
-                      const uint16_t *inside, int B, int C, int H, int W, float *const *grad_wq, float *grad_x, void *stream);
+// One stage, forward or backward, of a filled argument struct: the one launcher each kernel file exports.  halo: ft_halo() of the
+// arguments for a backward, 2 for a forward (the forward kernels have no halo).  The entry points and the one function that checks,
+// fills and launches for all of them are in mulut_ft.hip.
+hipError_t launch_ft_stage(const FtArgs &a, bool backward, int halo, hipStream_t st);                                              // mulut_ft.hip: interval 4
+hipError_t launch_ft_interval_stage(const FtIvArgs &a, int interval, bool backward, int halo, int num_cus, hipStream_t st);        // mulut_ft_interval.hip: 5 and 6
 #endif  // __HIPCC__
 
 }  // namespace mulut

@@ -569,6 +569,10 @@ static hipError_t launch_ft_u(const FtArgs &a, bool backward, hipStream_t st) {
          : a.u == 3 ? launch_ft<3, HALO>(a, backward, st) : launch_ft<4, HALO>(a, backward, st);
 }
 
+hipError_t launch_ft_stage(const FtArgs &a, bool backward, int halo, hipStream_t st) {
+    return halo > 2 ? launch_ft_u<3>(a, backward, st) : launch_ft_u<2>(a, backward, st);
+}
+
 // The module's quantisation step and its backward (sr/model.py:74-76: weight = clamp(round_func(weight * 127), -127, 127), round_func a
 // BPDA identity), for all tables of a stage in one launch: as torch operations they are six launches per table and direction.
 struct FtQuantArgs {
@@ -609,6 +613,71 @@ static int ft_quantize(int device, const float *const *w, float *const *o, int M
     return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }
 
+// The one host path of a stage call.  A request is what an entry point was given; a rule is what its family asks of it.  The order of
+// the checks -- and so which MULUT_E* code a bad call gets -- is part of the ABI: the family's early pointer, ft_fill (mulut_ft.h),
+// the call's own output pointers; all before the device is touched.
+struct FtRequest {
+    int device, interval;
+    const float *const *weights_q;
+    const char *modes;
+    int is_last, u;
+    const float *x;
+    int B, C, H, W;
+    float *out;                 // forward
+    const uint16_t *inside;
+    const float *grad_out;      // backward
+    float *const *grad_wq;
+    float *grad_x;
+    void *stream;
+};
+enum FtEarly { kFtEarlyNone, kFtEarlyInside, kFtEarlyGradWq };
+struct FtRule {
+    int iv_lo, iv_hi;   // intervals the family accepts (else MULUT_EUNSUPPORTED)
+    int max_reach;      // largest pattern reach: 2 = s, d, y; 3 = e, h, o as well
+    bool need_mask;     // `inside` is required
+    FtEarly early;      // the pointer tested ahead of everything else (kFtEarlyGradWq: of a backward call)
+};
+static const FtRule kFtPlain = {4, 4, 2, false, kFtEarlyNone};          // mulut_ft_stage_forward / _backward: the backward recomputes the mask
+static const FtRule kFtMask = {4, 4, 2, true, kFtEarlyInside};          // mulut_ft_stage_forward_mask / _backward_mask
+static const FtRule kFtInterval = {5, 6, 2, true, kFtEarlyGradWq};      // mulut_ft_interval_stage_*
+static const FtRule kFtWide = {4, 6, 3, true, kFtEarlyGradWq};          // mulut_ft_wide_stage_*
+
+static int ft_num_cus(int device) {
+    static int cus[64];
+    if (device < 0 || device >= 64) return 256;
+    if (!cus[device]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n < 1) n = 256;
+        cus[device] = n;
+    }
+    return cus[device];
+}
+
+// Args: FtArgs (interval 4) or FtIvArgs (5 and 6) -- exactly one is filled per call
+template <class Args>
+static int ft_stage_as(const FtRule &rule, const FtRequest &q, bool backward) {
+    Args a;
+    const int rc = ft_fill(a, q.interval >= rule.iv_lo && q.interval <= rule.iv_hi, q.weights_q, q.grad_wq, q.modes, q.is_last, q.u, q.x, q.inside,
+                           rule.need_mask, rule.max_reach, q.B, q.C, q.H, q.W);
+    if (rc) return rc;
+    if (backward ? !q.grad_out || !q.grad_wq || !q.grad_x : !q.out) return MULUT_EINVAL;
+    a.out = q.out;
+    a.gout = q.grad_out;
+    a.gx = q.grad_x;
+    if (hipSetDevice(q.device) != hipSuccess) return MULUT_ENODEVICE;
+    const int halo = backward ? ft_halo(a) : 2;      // (the forward kernels have no halo)
+    hipError_t e;
+    if constexpr (std::is_same<Args, FtArgs>::value) e = launch_ft_stage(a, backward, halo, (hipStream_t)q.stream);
+    else e = launch_ft_interval_stage(a, q.interval, backward, halo, ft_num_cus(q.device), (hipStream_t)q.stream);
+    return e == hipSuccess ? MULUT_OK : MULUT_EHIP;
+}
+
+static int ft_stage(const FtRule &rule, const FtRequest &q, bool backward) {
+    if (rule.early == kFtEarlyInside && !q.inside) return MULUT_EINVAL;
+    if (rule.early == kFtEarlyGradWq && backward && !q.grad_wq) return MULUT_EINVAL;
+    return q.interval == 4 ? ft_stage_as<FtArgs>(rule, q, backward) : ft_stage_as<FtIvArgs>(rule, q, backward);
+}
+
 extern "C" {
 
 int mulut_ft_quantize(int device, const float *const *weights, float *const *weights_q, int M, long long n, void *stream) {
@@ -619,65 +688,52 @@ int mulut_ft_quantize_backward(int device, const float *const *weights, float *c
     return ft_quantize(device, weights, grad, M, n, true, stream);
 }
 
-// max_reach: 2 for the entry points of this file (s, d, y), 3 for mulut_ft_wide_stage_* (mulut_ft_interval.hip)
-static int ft_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
-                      int B, int C, int H, int W, float *out, uint16_t *inside, int max_reach, void *stream) {
-    FtArgs a;
-    int rc = ft_fill(a, true, weights_q, nullptr, modes, is_last, u, x, inside, false, max_reach, B, C, H, W);
-    if (rc) return rc;
-    if (!out) return MULUT_EINVAL;
-    a.out = out;
-    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    const hipError_t e = launch_ft_u<2>(a, false, (hipStream_t)stream);      // (the forward kernels have no halo)
-    return e == hipSuccess ? MULUT_OK : MULUT_EHIP;
-}
-
 int mulut_ft_stage_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                            int B, int C, int H, int W, float *out, void *stream) {
-    return ft_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, nullptr, 2, stream);
-}
-
-int mulut_ft_stage_forward_mask(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
-                                int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
-    if (!inside) return MULUT_EINVAL;
-    return ft_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, 2, stream);
-}
-
-static int ft_backward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
-                       const float *grad_out, const uint16_t *inside, int B, int C, int H, int W, float *const *grad_wq, float *grad_x,
-                       int max_reach, void *stream) {
-    FtArgs a;
-    int rc = ft_fill(a, true, weights_q, grad_wq, modes, is_last, u, x, inside, false, max_reach, B, C, H, W);
-    if (rc) return rc;
-    if (!grad_out || !grad_wq || !grad_x) return MULUT_EINVAL;
-    a.gout = grad_out;
-    a.gx = grad_x;
-    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    const hipError_t e = ft_halo(a) > 2 ? launch_ft_u<3>(a, true, (hipStream_t)stream) : launch_ft_u<2>(a, true, (hipStream_t)stream);
-    return e == hipSuccess ? MULUT_OK : MULUT_EHIP;
+    return ft_stage(kFtPlain, {device, 4, weights_q, modes, is_last, u, x, B, C, H, W, out, nullptr, nullptr, nullptr, nullptr, stream}, false);
 }
 
 int mulut_ft_stage_backward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                             const float *grad_out, int B, int C, int H, int W, float *const *grad_wq, float *grad_x,
                             void *stream) {
-    return ft_backward(device, weights_q, modes, is_last, u, x, grad_out, nullptr, B, C, H, W, grad_wq, grad_x, 2, stream);
+    return ft_stage(kFtPlain, {device, 4, weights_q, modes, is_last, u, x, B, C, H, W, nullptr, nullptr, grad_out, grad_wq, grad_x, stream}, true);
+}
+
+int mulut_ft_stage_forward_mask(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
+                                int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
+    return ft_stage(kFtMask, {device, 4, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, nullptr, nullptr, nullptr, stream}, false);
 }
 
 int mulut_ft_stage_backward_mask(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                                  const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
                                  float *const *grad_wq, float *grad_x, void *stream) {
-    if (!inside) return MULUT_EINVAL;
-    return ft_backward(device, weights_q, modes, is_last, u, x, grad_out, inside, B, C, H, W, grad_wq, grad_x, 2, stream);
+    return ft_stage(kFtMask, {device, 4, weights_q, modes, is_last, u, x, B, C, H, W, nullptr, inside, grad_out, grad_wq, grad_x, stream}, true);
+}
+
+// MuLUT.forward's stage at interval 5 / 6 (sr/model.py:289-312 with :42-44, 78-80), and autograd's backward of it
+int mulut_ft_interval_stage_forward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                    const float *x, int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
+    return ft_stage(kFtInterval, {device, interval, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, nullptr, nullptr, nullptr, stream}, false);
+}
+
+int mulut_ft_interval_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                     const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
+                                     float *const *grad_wq, float *grad_x, void *stream) {
+    return ft_stage(kFtInterval, {device, interval, weights_q, modes, is_last, u, x, B, C, H, W, nullptr, inside, grad_out, grad_wq, grad_x, stream}, true);
+}
+
+// The same stage for any list over s, d, y, e, h, o at interval 4, 5 or 6 (sr/model.py:69-312; the reference's module stops at s, d, y
+// with "more sampling modes can be implemented similarly", :119-121 -- the 4 x 4 taps are common/network.py:173-215).  A list with one
+// of e, h, o runs the backward kernels' HALO = 3 instances; a list without runs what the families above run, launch for launch.
+int mulut_ft_wide_stage_forward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                const float *x, int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
+    return ft_stage(kFtWide, {device, interval, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, nullptr, nullptr, nullptr, stream}, false);
+}
+
+int mulut_ft_wide_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                 const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
+                                 float *const *grad_wq, float *grad_x, void *stream) {
+    return ft_stage(kFtWide, {device, interval, weights_q, modes, is_last, u, x, B, C, H, W, nullptr, inside, grad_out, grad_wq, grad_x, stream}, true);
 }
 
 }  // extern "C"
-
-// interval 4 of mulut_ft_wide_stage_* (mulut_ft.h)
-int mulut::ft_wide4_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x, int B, int C, int H,
-                            int W, float *out, uint16_t *inside, void *stream) {
-    return ft_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, 3, stream);
-}
-int mulut::ft_wide4_backward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x, const float *grad_out,
-                             const uint16_t *inside, int B, int C, int H, int W, float *const *grad_wq, float *grad_x, void *stream) {
-    return ft_backward(device, weights_q, modes, is_last, u, x, grad_out, inside, B, C, H, W, grad_wq, grad_x, 3, stream);
-}

@@ -48,20 +48,7 @@ namespace mulut {
 // 24 KB + the u = 4 backward's 77 KB, which only ever meets the 40 KB image of interval 6).
 constexpr int kFtIvLdsBudget = 120 * 1024;
 
-// FtArgs (mulut_ft.h) with tiles_per_wg, and where it is.  Not FtArgs with the field appended: behind di / dj the backward kernels fetch it
-// with a scalar load of its own (next to is_last the two come as one), and in the middle of FtArgs it would move the argument
-// offsets of the interval-4 kernels.  `inside` is mandatory here.
-struct FtIvArgs {
-    const float *w[kMaxFtModes];
-    float *gw[kMaxFtModes];
-    const float *x, *gout;
-    float *out, *gx;
-    uint16_t *inside;
-    int B, C, H, W, u, M, is_last;
-    int tiles_per_wg;     // backward: consecutive tiles of sites a workgroup walks
-    int di[kMaxFtModes][3], dj[kMaxFtModes][3];
-};
-
+// (the argument struct, FtIvArgs: mulut_ft.h)
 template <int IV>
 __device__ __forceinline__ void ftiv_pass_setup(const float *plane, int H, int W, int y, int x, int r, const int (&di)[3], const int (&dj)[3],
                                                 FtIvPass &p) {
@@ -481,17 +468,6 @@ __global__ void __launch_bounds__(kFtIvB4Sites) ft_interval_stage_bwd4(FtIvArgs 
     }
 }
 
-static int ftiv_num_cus(int device) {
-    static int cus[64];
-    if (device < 0 || device >= 64) return 256;
-    if (!cus[device]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n < 1) n = 256;
-        cus[device] = n;
-    }
-    return cus[device];
-}
-
 template <int IV, int U>
 static hipError_t launch_ftiv_fwd(const FtIvArgs &a, int num_cus, hipStream_t st) {
     const long long nsite = (long long)a.B * a.C * a.H * a.W;
@@ -563,75 +539,10 @@ static hipError_t launch_ftiv(const FtIvArgs &a, bool backward, int num_cus, hip
     }
 }
 
-// one stage, forward or backward, of a filled FtIvArgs at interval 5 or 6
-static int ftiv_run(FtIvArgs &a, int device, int interval, bool backward, void *stream) {
-    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    const int cus = ftiv_num_cus(device);
-    const hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
-    if (backward && ft_halo(a) > 2) e = interval == 5 ? launch_ftiv<5, 3>(a, true, cus, st) : launch_ftiv<6, 3>(a, true, cus, st);
-    else e = interval == 5 ? launch_ftiv<5, 2>(a, backward, cus, st) : launch_ftiv<6, 2>(a, backward, cus, st);
-    return e == hipSuccess ? MULUT_OK : MULUT_EHIP;
+// one stage, forward or backward, of a filled FtIvArgs at interval 5 or 6 (mulut_ft.h)
+hipError_t launch_ft_interval_stage(const FtIvArgs &a, int interval, bool backward, int halo, int num_cus, hipStream_t st) {
+    if (halo > 2) return interval == 5 ? launch_ftiv<5, 3>(a, backward, num_cus, st) : launch_ftiv<6, 3>(a, backward, num_cus, st);
+    return interval == 5 ? launch_ftiv<5, 2>(a, backward, num_cus, st) : launch_ftiv<6, 2>(a, backward, num_cus, st);
 }
 
 }  // namespace mulut
-
-using namespace mulut;
-
-extern "C" {
-
-// MuLUT.forward's stage at interval 5 / 6 (sr/model.py:289-312 with :42-44, 78-80)
-int mulut_ft_interval_stage_forward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
-                                    const float *x, int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
-    FtIvArgs a;
-    const int rc = ft_fill(a, interval == 5 || interval == 6, weights_q, nullptr, modes, is_last, u, x, inside, true, 2, B, C, H, W);      // (interval 4: mulut_ft_stage_*)
-    if (rc) return rc;
-    if (!out) return MULUT_EINVAL;
-    a.out = out;
-    return ftiv_run(a, device, interval, false, stream);
-}
-
-// autograd's backward of that stage: gradients of the quantised tables and of the input
-int mulut_ft_interval_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
-                                     const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
-                                     float *const *grad_wq, float *grad_x, void *stream) {
-    if (!grad_wq) return MULUT_EINVAL;
-    FtIvArgs a;
-    const int rc = ft_fill(a, interval == 5 || interval == 6, weights_q, grad_wq, modes, is_last, u, x, inside, true, 2, B, C, H, W);
-    if (rc) return rc;
-    if (!grad_out || !grad_x) return MULUT_EINVAL;
-    a.gout = grad_out;
-    a.gx = grad_x;
-    return ftiv_run(a, device, interval, true, stream);
-}
-
-// The same stage for any list over s, d, y, e, h, o at interval 4, 5 or 6 (sr/model.py:69-312; the reference's module stops at s, d, y
-// with "more sampling modes can be implemented similarly", :119-121 -- the 4 x 4 taps are common/network.py:173-215).  A list with one
-// of e, h, o runs the backward kernels' HALO = 3 instances; a list without runs what mulut_ft_stage_*_mask / mulut_ft_interval_stage_*
-// run, so the two families agree bit for bit there.
-int mulut_ft_wide_stage_forward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
-                                const float *x, int B, int C, int H, int W, float *out, unsigned short *inside, void *stream) {
-    FtIvArgs a;
-    const int rc = ft_fill(a, interval >= 4 && interval <= 6, weights_q, nullptr, modes, is_last, u, x, inside, true, 3, B, C, H, W);
-    if (rc) return rc;
-    if (!out) return MULUT_EINVAL;
-    if (interval == 4) return ft_wide4_forward(device, weights_q, modes, is_last, u, x, B, C, H, W, out, inside, stream);
-    a.out = out;
-    return ftiv_run(a, device, interval, false, stream);
-}
-
-int mulut_ft_wide_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
-                                 const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
-                                 float *const *grad_wq, float *grad_x, void *stream) {
-    if (!grad_wq) return MULUT_EINVAL;
-    FtIvArgs a;
-    const int rc = ft_fill(a, interval >= 4 && interval <= 6, weights_q, grad_wq, modes, is_last, u, x, inside, true, 3, B, C, H, W);
-    if (rc) return rc;
-    if (!grad_out || !grad_x) return MULUT_EINVAL;
-    if (interval == 4) return ft_wide4_backward(device, weights_q, modes, is_last, u, x, grad_out, inside, B, C, H, W, grad_wq, grad_x, stream);
-    a.gout = grad_out;
-    a.gx = grad_x;
-    return ftiv_run(a, device, interval, true, stream);
-}
-
-}  // extern "C"

@@ -4,7 +4,7 @@
 names (``weight_s{stage}_{mode}``, float32 [83521, u*u] = int8/127, sr/model.py:49-57) and forward contract
 (x float32 [B,C,H,W] in 0..1 -> [B,C,H*u,W*u] in 0..1, :289-312), so ``sr/3_finetune_lut.py`` can train it with
 the same Adam / cosine schedule and write ``LUT_ft_*.npy`` the same way (:162-169).  Each stage runs as one
-forward and one backward HIP kernel (mulut_amd/csrc/mulut_ft.hip) through the C ABI; torch provides autograd
+forward and one backward HIP kernel through the C ABI (mulut_ft_wide_stage_forward / _backward, for every class here); torch provides autograd
 plumbing, parameters and the optimiser only.  ``MuLUTInterval`` is the same module at intervals 5 and 6, ``MuLUTWide`` the one
 for mode lists with the 4 x 4 patterns e, h, o (intervals 4, 5 and 6).
 """
@@ -26,7 +26,7 @@ class _StageFn(torch.autograd.Function):
     """One stage: all modes x 4 rotations, per-pass BPDA rounding, clamp/round of the stage output."""
 
     @staticmethod
-    def forward(ctx, x, modes, is_last, u, interval, wide, *weights):
+    def forward(ctx, x, modes, is_last, u, interval, *weights):
         lib = _native.load()
         x = x.contiguous()
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
@@ -44,25 +44,19 @@ class _StageFn(torch.autograd.Function):
         out = torch.empty((B, C, H * u, W * u), dtype=torch.float32, device=x.device)
         # where the stage's clamp passes gradient, 16 bits per site: saves the backward a recomputation of the stage forward
         inside = torch.empty((B, C, H, W), dtype=torch.int16, device=x.device)
-        if wide:    # any list over s, d, y, e, h, o at interval 4, 5 or 6
-            rc = lib.mulut_ft_wide_stage_forward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
-                                                 x.data_ptr(), B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
-        elif interval == 4:
-            rc = lib.mulut_ft_stage_forward_mask(x.device.index, _ptr_array(wq), modes.encode(), int(is_last), int(u), x.data_ptr(),
-                                                 B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
-        else:       # intervals 5 and 6: mulut_ft_interval.hip
-            rc = lib.mulut_ft_interval_stage_forward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
-                                                     x.data_ptr(), B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
+        # any list over s, d, y, e, h, o at interval 4, 5 or 6: for a list of s, d, y the launches of the narrow entry points
+        rc = lib.mulut_ft_wide_stage_forward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                             x.data_ptr(), B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
         if rc:
             raise (ValueError if rc == -2 else RuntimeError)(lib.mulut_strerror(rc).decode())
         ctx.save_for_backward(x, wq_all, inside, *ws)
-        ctx.cfg = (modes, is_last, u, interval, wide)
+        ctx.cfg = (modes, is_last, u, interval)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         lib = _native.load()
-        modes, is_last, u, interval, wide = ctx.cfg
+        modes, is_last, u, interval = ctx.cfg
         x, wq_all, inside, *ws = ctx.saved_tensors
         wq = [wq_all[m].view(w.shape) for m, w in enumerate(ws)]
         gout = gout.contiguous()
@@ -71,24 +65,16 @@ class _StageFn(torch.autograd.Function):
         gwq = [g_all[m].view(w.shape) for m, w in enumerate(ws)]
         gx = torch.zeros_like(x)
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        if wide:
-            rc = lib.mulut_ft_wide_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
-                                                  x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
-                                                  gx.data_ptr(), stream)
-        elif interval == 4:
-            rc = lib.mulut_ft_stage_backward_mask(x.device.index, _ptr_array(wq), modes.encode(), int(is_last), int(u), x.data_ptr(),
-                                                  gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq), gx.data_ptr(), stream)
-        else:
-            rc = lib.mulut_ft_interval_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
-                                                      x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
-                                                      gx.data_ptr(), stream)
+        rc = lib.mulut_ft_wide_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                              x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
+                                              gx.data_ptr(), stream)
         if rc:
             raise RuntimeError(lib.mulut_strerror(rc).decode())
         # backward of clamp(round_func(w*127)): round is identity (BPDA), clamp passes inside [-127,127], x127 -- in place, one launch
         rc = lib.mulut_ft_quantize_backward(x.device.index, _ptr_array(ws), _ptr_array(gwq), len(ws), ws[0].numel(), stream)
         if rc:
             raise RuntimeError(lib.mulut_strerror(rc).decode())
-        return (gx, None, None, None, None, None) + tuple(gwq)
+        return (gx, None, None, None, None) + tuple(gwq)
 
 
 class MuLUT(nn.Module):
@@ -96,7 +82,6 @@ class MuLUT(nn.Module):
     Intervals 5 and 6 are ``MuLUTInterval``; mode lists with e, h or o are ``MuLUTWide``."""
 
     MODES = "sdy"       # the patterns the class takes
-    WIDE = False        # stages through mulut_ft_wide_stage_* (any of the six patterns) instead of the s, d, y entry points
 
     def __init__(self, lut_folder, stages, modes, upscale=4, interval=4):
         super().__init__()
@@ -125,7 +110,7 @@ class MuLUT(nn.Module):
             stage = s + 1
             last = stage == self.stages
             weights = [getattr(self, "weight_s{}_{}".format(stage, m)) for m in self.modes]
-            x = _StageFn.apply(x, self.modes, last, self.upscale if last else 1, self.interval, self.WIDE, *weights)
+            x = _StageFn.apply(x, self.modes, last, self.upscale if last else 1, self.interval, *weights)
         return x / 255.0
 
     @staticmethod
@@ -164,12 +149,10 @@ class MuLUTWide(MuLUT):
     """The same module for any list over the six sampling patterns s, d, y, e, h, o, at interval 4, 5 or 6.  The reference's
     module ends its pattern cascade at s, d, y with "more sampling modes can be implemented similarly" (sr/model.py:119-121) while
     its network and trainer define all six (common/network.py:173-215): this class fine-tunes the tables transfer_to_lut writes
-    for them, same file names, parameter names and forward contract.  The stages run through mulut_ft_wide_stage_forward /
-    _backward: the backward kernels with a 3-pixel halo of the input gradient when the list holds e, h or o, and exactly what
-    ``MuLUT`` / ``MuLUTInterval`` run when it does not."""
+    for them, same file names, parameter names and forward contract.  The backward kernels stage a 3-pixel halo of the input
+    gradient when the list holds e, h or o, and are exactly what ``MuLUT`` / ``MuLUTInterval`` run when it does not."""
 
     MODES = "sdyeho"
-    WIDE = True
 
     @staticmethod
     def _check_interval(interval):
