@@ -281,7 +281,9 @@ int mulut_eval_y(int device, const void *gt_hwc, const void *out_hwc, int H, int
  * serialised inside the library: contexts may be created and first used from several host threads. */
 int mulut_set_tuning(mulut_ctx *ctx, const char *key, int value);
 
-/* Name of the kernel variant used for the final / non-final stage (for profiles). */
+/* Name of the kernel variant used for the final / non-final stage (for profiles).  is_final 2: as 1, but where the final stage runs
+ * stage_tube2_kernel only that kernel is named, with its accumulator form: "stage_tube2_kernel<rgb,one-set>" (all four rotations in
+ * one accumulator set on the rotation-closed band: up to four modes) or "stage_tube2_kernel<rgb,two-set>". */
 const char *mulut_kernel_name(const mulut_ctx *ctx, int is_final);
 
 #ifdef __cplusplus

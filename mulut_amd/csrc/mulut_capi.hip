@@ -1027,7 +1027,11 @@ const char *mulut_kernel_name(const mulut_ctx *ctx, int is_final) {
     // written as packed RGB; the non-final stage has 1-byte rows
     const int stage = is_final ? ctx->stages : 1, u = is_final ? ctx->scale : 1;
     const View in = make_view(nullptr, MULUT_LAYOUT_CHW, 64, 64, 3, 0);
-    const StagePlan p = plan_stage(ctx, ctx->routing, u, stage_args(ctx, stage, in, in, 1, 64, 64, 3, 0, 64), MULUT_LAYOUT_HWC, true);
+    const StageArgs ra = stage_args(ctx, stage, in, in, 1, 64, 64, 3, 0, 64);
+    const StagePlan p = plan_stage(ctx, ctx->routing, u, ra, MULUT_LAYOUT_HWC, true);
+    // is_final 2: the final stage's tube2 kernel alone, with the accumulator form the launch takes
+    if (is_final == 2 && p.tube2 && (p.route == kRouteTube || p.route == kRouteHybrid))
+        return stage_tube2_one_set(ra, p.out_mode) ? "stage_tube2_kernel<rgb,one-set>" : "stage_tube2_kernel<rgb,two-set>";
     switch (p.route) {
         case kRouteIvLds:
         case kRouteIvGlobal: return stage_interval_name(ctx->interval, u, p.route == kRouteIvLds);

@@ -425,6 +425,90 @@ MULUT_HD constexpr bool tube_contains(int A, int B, int C, int D) {
 }
 MULUT_HD constexpr int tube_slot(int A, int B, int C, int D) { return A * kTubeSA + B * kTubeSB + C * kTubeSC + D * kTubeSD; }
 
+// ---- rotation-closed placement of a 16-value row in a tube slot (the "one-set" band of stage_tube2_kernel) ----
+// The plain band pairs the fields as (e 4k, e 4k+2) / (e 4k+1, e 4k+3): closed under the 180-degree rotation only, so rotations
+// (0,2) and (1,3) need an accumulator set each.  Here a block position shares its dword with its 180-degree partner instead.  rho =
+// the map rotation 1 applies to block positions (p -> row_elem(1, p)); it has four orbits of four on the 4 x 4 block.  With p_i the
+// smallest position of orbit i:
+//      LO plane dword i = e(p_i)     | e(rho^2 p_i) << 16,        HI plane dword i = e(rho p_i) | e(rho^3 p_i) << 16
+// i.e. position rho^k p_i sits in plane k & 1, dword i, half k >> 1.  An accumulator set laid out the same way by BLOCK position takes
+// every rotation dword by dword: rotation r adds row field rho^r(p) to position p, which moves a whole plane onto a whole plane with
+// the two halves of every dword either kept or swapped (tube4r_closed() proves it from row_elem; tube4r_acc_plane / tube4r_swap say
+// which).  Same slots, same 2 x 16 bytes per slot, same value + 128 fields as the plain band: the kernel reorders the fields of a slot
+// while it stages the band into LDS (tube4r_from_plain), so a table keeps one band image in device memory.
+MULUT_HD constexpr int rot4_step(int p) { return row_elem(1, p >> 2, p & 3, 4); }
+MULUT_HD constexpr int rot4_orbit_min(int p) {
+    int m = p;
+    for (int k = 0, q = p; k < 3; ++k) {
+        q = rot4_step(q);
+        if (q < m) m = q;
+    }
+    return m;
+}
+MULUT_HD constexpr int rot4_orbit(int p) {       // index of p's orbit, orbits ordered by their smallest position
+    int i = 0;
+    for (int q = 0; q < rot4_orbit_min(p); ++q)
+        if (rot4_orbit_min(q) == q) ++i;
+    return i;
+}
+MULUT_HD constexpr int rot4_phase(int p) {       // k with rho^k (orbit's smallest position) == p
+    int k = 0;
+    for (int q = rot4_orbit_min(p); q != p && k < 4; ++k) q = rot4_step(q);
+    return k;
+}
+// position -> place of its field in a slot (the same map places a block position in the accumulator set)
+MULUT_HD constexpr int tube4r_plane(int p) { return rot4_phase(p) & 1; }
+MULUT_HD constexpr int tube4r_dword(int p) { return rot4_orbit(p); }
+MULUT_HD constexpr int tube4r_half(int p) { return rot4_phase(p) >> 1; }
+// ... and its inverse
+MULUT_HD constexpr int tube4r_pos(int plane, int dword, int half) {
+    for (int p = 0; p < 16; ++p)
+        if (tube4r_plane(p) == plane && tube4r_dword(p) == dword && tube4r_half(p) == half) return p;
+    return -1;
+}
+// block position that rotation r gives row element e (the inverse of row_elem at u = 4)
+MULUT_HD constexpr int rot4_target(int r, int e) {
+    for (int p = 0; p < 16; ++p)
+        if (row_elem(r, p >> 2, p & 3, 4) == e) return p;
+    return -1;
+}
+// rotation r: the row dword (plane, i) is added into accumulator plane tube4r_acc_plane(r, plane), dword i, with its halves swapped iff
+// tube4r_swap(r, plane)
+MULUT_HD constexpr int tube4r_acc_plane(int r, int plane) { return tube4r_plane(rot4_target(r, tube4r_pos(plane, 0, 0))); }
+MULUT_HD constexpr int tube4r_swap(int r, int plane) { return tube4r_half(rot4_target(r, tube4r_pos(plane, 0, 0))); }
+MULUT_HD constexpr bool tube4r_closed() {
+    int seen = 0;
+    for (int p = 0; p < 16; ++p) {
+        if (tube4r_pos(tube4r_plane(p), tube4r_dword(p), tube4r_half(p)) != p || rot4_phase(p) > 3) return false;
+        seen |= 1 << (tube4r_plane(p) * 8 + tube4r_dword(p) * 2 + tube4r_half(p));
+    }
+    if (seen != 0xFFFF) return false;
+    for (int r = 0; r < 4; ++r)
+        for (int plane = 0; plane < 2; ++plane)
+            for (int i = 0; i < 4; ++i)
+                for (int half = 0; half < 2; ++half) {
+                    const int p = rot4_target(r, tube4r_pos(plane, i, half));       // where this row field lands
+                    if (p < 0 || tube4r_plane(p) != tube4r_acc_plane(r, plane) || tube4r_dword(p) != i || tube4r_half(p) != (half ^ tube4r_swap(r, plane)))
+                        return false;
+                }
+    return tube4r_acc_plane(1, 0) != tube4r_acc_plane(1, 1) && tube4r_acc_plane(3, 0) != tube4r_acc_plane(3, 1);
+}
+// the eight dwords of a slot of the plain band (lo_k = e(4k) | e(4k+2) << 16, hi_k = e(4k+1) | e(4k+3) << 16) in the rotation-closed order
+template <int E>
+MULUT_HD uint32_t tube4r_plain_field(const uint32_t (&lo)[4], const uint32_t (&hi)[4]) {
+    const uint32_t word = (E & 1) ? hi[E >> 2] : lo[E >> 2];
+    return (E & 2) ? (word >> 16) : (word & 0xFFFFu);
+}
+MULUT_HD void tube4r_from_plain(const uint32_t (&lo)[4], const uint32_t (&hi)[4], uint32_t (&rlo)[4], uint32_t (&rhi)[4]) {
+    static_for<0, 4>([&](auto I) {       // (every position a compile-time constant: two or three bit operations per dword)
+        constexpr int i = I;
+        constexpr int l0 = tube4r_pos(0, i, 0), l1 = tube4r_pos(0, i, 1), h0 = tube4r_pos(1, i, 0), h1 = tube4r_pos(1, i, 1);
+        rlo[i] = tube4r_plain_field<l0>(lo, hi) | (tube4r_plain_field<l1>(lo, hi) << 16);
+        rhi[i] = tube4r_plain_field<h0>(lo, hi) | (tube4r_plain_field<h1>(lo, hi) << 16);
+    });
+}
+static_assert(tube4r_closed(), "every rotation maps the dwords of the rotation-closed row onto the dwords of the accumulator set");
+
 // Two passes (low half = pass A, high half = pass B) of one site against a tube band, on pixel codes
 // (pixel_code below): ca = anchor code in the low half, pb/pc/pd = packed code pairs.  `bias` (a multiple of
 // 16, duplicated into both halves by the caller's constant) is added to every row offset so that the caller

@@ -448,6 +448,39 @@ __device__ __forceinline__ void tube_finish_rows_wide(const StageArgs &a, const 
     });
 }
 
+// One accumulator set for all four rotations (stage_tube2_kernel on the rotation-closed band, mulut_core.h tube4r_*): block position p
+// lives in plane tube4r_plane(p) (lo / hi), dword tube4r_dword(p), half tube4r_half(p).  The fields start at -unbias (mod 2^16) and
+// wrap freely; at the end a field IS the numerator K (mod 2^16, |K| <= 8192 M < 2^15 for M <= 4), so the epilogue reads every byte
+// straight from its half: sign-extending SDWA convert, multiply by fl(1/d), v_cvt_pk_u8_f32 -- no add, no second set.
+template <int HALF>
+__device__ __forceinline__ float f32_of_i16_half(uint32_t x) {
+    float f;
+    if constexpr (HALF == 0) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(f) : "v"(x));
+    else asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(f) : "v"(x));
+    return f;
+}
+struct TubeAcc1 {
+    uint32_t lo[4], hi[4];
+    __device__ __forceinline__ void start(uint32_t nb) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lo[k] = hi[k] = nb;
+    }
+    template <int P>
+    __device__ __forceinline__ float field() const {
+        const uint32_t word = tube4r_plane(P) ? hi[tube4r_dword(P)] : lo[tube4r_dword(P)];
+        return f32_of_i16_half<tube4r_half(P)>(word);
+    }
+    // the four bytes of block row SY (exact for the divisor: StageArgs::use_f32)
+    template <int SY>
+    __device__ __forceinline__ uint32_t finish_row(float inv_d) const {
+        uint32_t r = __builtin_amdgcn_cvt_pk_u8_f32(field<4 * SY + 0>() * inv_d, 0u, 0u);
+        r = __builtin_amdgcn_cvt_pk_u8_f32(field<4 * SY + 1>() * inv_d, 1u, r);
+        r = __builtin_amdgcn_cvt_pk_u8_f32(field<4 * SY + 2>() * inv_d, 2u, r);
+        r = __builtin_amdgcn_cvt_pk_u8_f32(field<4 * SY + 3>() * inv_d, 3u, r);
+        return r;
+    }
+};
+
 // where a tile's anchor-MSB histogram / list positions live (tile_stat_kernel writes, the detailed-tile path reads)
 __device__ __forceinline__ size_t detail_hist_index(uint32_t tile, uint32_t ntiles, int b) {
     return ((size_t)(b >> 3) * ntiles + tile) * 8 + (size_t)(b & 7);

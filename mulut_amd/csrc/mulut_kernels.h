@@ -138,6 +138,8 @@ const char *stage_tube_name(int out_mode);
 // the mode lists stage_tube2_supported() accepts
 constexpr int kMaxTube2Modes = 8;
 bool stage_tube2_supported(const StageArgs &a);
+// whether the launch takes the kernel's one-set form (same bands: the kernel stages them in the rotation-closed order of mulut_core.h)
+bool stage_tube2_one_set(const StageArgs &a, int out_mode);
 hipError_t launch_stage_tube2(const StageArgs &a, const BandArgs &b, int out_mode, int num_cus, hipStream_t st);
 // recompute the pixels listed in a.fix_list[0 .. *a.fix_count) from the full tables (u == 4)
 hipError_t launch_stage_up_fix(const StageArgs &a, int num_cus, hipStream_t st);

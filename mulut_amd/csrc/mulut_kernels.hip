@@ -836,28 +836,67 @@ __device__ __forceinline__ void t2_index(uint32_t k0, uint32_t ha, uint32_t base
     [n3] "i"(t2_nb(PAT, R, 1, -1) + (OFF)), [n4] "i"(t2_nb(PAT, R, 2, 1) + (OFF)), [n5] "i"(t2_nb(PAT, R, 2, -1) + (OFF)), [nan] "i"(2 * (2 * kT2PW + 2) + (OFF))
 
 #define T2_NBOUT_OPS [pb] "=&v"(pb), [pc] "=&v"(pc), [pd] "=&v"(pd), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2)
-// first pass of a pair (weights = low halves of cur): MACs, refill with the pair's second pass
-template <int PAT>
+// first pass of a pair (weights = low halves of cur): MACs, refill with the pair's second pass.
+// FORM: -1 = two accumulator sets on the plain band (lo / hi = the set of the pair's rotations); 0 / 1 = the one-set form on the rotation-closed
+// band, the pair's rotation class R (lo / hi = THE set; the blocks differ in which plane feeds which and in the half swaps)
+template <int PAT, int FORM>
 __device__ __forceinline__ void t2_block_a(uint32_t (&lo)[4], uint32_t (&hi)[4], const T2Pair &cur) {
     uint32_t a0, a1, a2, a3;
-    asm volatile(TUBE2_ASM_A : T2_ACC_OPS(lo, hi), T2_TMP_OPS : T2_W_OPS(cur), T2_ADDR_OPS(cur), T2_IMM_OPS(PAT) : TUBE2_CLOBBERS);
+#define T2_A_STMT(BLK) asm volatile(BLK : T2_ACC_OPS(lo, hi), T2_TMP_OPS : T2_W_OPS(cur), T2_ADDR_OPS(cur), T2_IMM_OPS(PAT) : TUBE2_CLOBBERS)
+    if constexpr (FORM < 0) T2_A_STMT(TUBE2_ASM_A);
+    else if constexpr (FORM == 0) T2_A_STMT(TUBE2_ASM1_A_R0);
+    else T2_A_STMT(TUBE2_ASM1_A_R1);
+#undef T2_A_STMT
 }
-// second pass (weights = high halves of cur, reversed element order): MACs, refill with the first pass of the next pair (pattern
+// second pass (weights = high halves of cur; two-set form: reversed element order): MACs, refill with the first pass of the next pair (pattern
 // NPAT, addresses from nxt).  NN: neighbour codes fetched under the MACs -- 0 none, 6 those of rotation pair TR of pattern TPAT in the
 // window at win + TOFF (out: pb, pc, pd), 7 the same + that window's anchor code (out: ca, in both halves).
 // LAST: no refill (the site's very last pass).
-template <int NPAT, int NN, int TPAT, int TR, int TOFF, bool LAST>
+template <int FORM, int NPAT, int NN, int TPAT, int TR, int TOFF, bool LAST>
 __device__ __forceinline__ void t2_block_b(uint32_t (&lo)[4], uint32_t (&hi)[4], const T2Pair &cur, const T2Pair &nxt, uint32_t win,
                                            uint32_t &pb, uint32_t &pc, uint32_t &pd, uint32_t &ca) {
     uint32_t a0, a1, a2, a3, t0, t1, t2;
-    if constexpr (LAST)
-        asm volatile(TUBE2_ASM_B_LAST : T2_ACC_OPS(lo, hi) : T2_W_OPS(cur) : TUBE2_CLOBBERS);
-    else if constexpr (NN == 0)
-        asm volatile(TUBE2_ASM_B_N0 : T2_ACC_OPS(lo, hi), T2_TMP_OPS : T2_W_OPS(cur), T2_ADDR_OPS(nxt), T2_IMM_OPS(NPAT) : TUBE2_CLOBBERS);
-    else if constexpr (NN == 6)
-        asm volatile(TUBE2_ASM_B_N6 : T2_ACC_OPS(lo, hi), T2_TMP_OPS, T2_NBOUT_OPS : T2_W_OPS(cur), T2_ADDR_OPS(nxt), T2_IMM_OPS(NPAT), [win] "v"(win), T2_NB_OPS(TPAT, TR, TOFF) : TUBE2_CLOBBERS);
-    else
-        asm volatile(TUBE2_ASM_B_N7 : T2_ACC_OPS(lo, hi), T2_TMP_OPS, T2_NBOUT_OPS, [ca] "=&v"(ca) : T2_W_OPS(cur), T2_ADDR_OPS(nxt), T2_IMM_OPS(NPAT), [win] "v"(win), T2_NB_OPS(TPAT, TR, TOFF) : TUBE2_CLOBBERS);
+#define T2_B_STMTS(BLK)                                                                                                                                       \
+    do {                                                                                                                                                      \
+        if constexpr (LAST)                                                                                                                                   \
+            asm volatile(BLK##_LAST : T2_ACC_OPS(lo, hi) : T2_W_OPS(cur) : TUBE2_CLOBBERS);                                                                  \
+        else if constexpr (NN == 0)                                                                                                                           \
+            asm volatile(BLK##_N0 : T2_ACC_OPS(lo, hi), T2_TMP_OPS : T2_W_OPS(cur), T2_ADDR_OPS(nxt), T2_IMM_OPS(NPAT) : TUBE2_CLOBBERS);                    \
+        else if constexpr (NN == 6)                                                                                                                           \
+            asm volatile(BLK##_N6 : T2_ACC_OPS(lo, hi), T2_TMP_OPS, T2_NBOUT_OPS : T2_W_OPS(cur), T2_ADDR_OPS(nxt), T2_IMM_OPS(NPAT), [win] "v"(win), T2_NB_OPS(TPAT, TR, TOFF) : TUBE2_CLOBBERS); \
+        else                                                                                                                                                  \
+            asm volatile(BLK##_N7 : T2_ACC_OPS(lo, hi), T2_TMP_OPS, T2_NBOUT_OPS, [ca] "=&v"(ca) : T2_W_OPS(cur), T2_ADDR_OPS(nxt), T2_IMM_OPS(NPAT), [win] "v"(win), T2_NB_OPS(TPAT, TR, TOFF) : TUBE2_CLOBBERS); \
+    } while (0)
+    if constexpr (FORM < 0) T2_B_STMTS(TUBE2_ASM_B);
+    else if constexpr (FORM == 0) T2_B_STMTS(TUBE2_ASM1_B_R0);
+    else T2_B_STMTS(TUBE2_ASM1_B_R1);
+#undef T2_B_STMTS
+}
+
+// One-set form, the last two pairs of a channel: block B in its form for "another channel follows" (NN = 6 / 7, as above) and in its form for
+// the site's last channel (no neighbour fetch; LAST: no refill either), both in one statement behind a scalar branch on `more` (wave-uniform).
+// pb, pc, pd, ca are written only where more != 0.
+template <int FORM, int NPAT, int NN, int TPAT, int TR, int TOFF, bool LAST>
+__device__ __forceinline__ void t2_block_b_either(uint32_t (&lo)[4], uint32_t (&hi)[4], const T2Pair &cur, const T2Pair &nxt, uint32_t win, uint32_t more,
+                                                  uint32_t &pb, uint32_t &pc, uint32_t &pd, uint32_t &ca) {
+    static_assert((FORM == 0 || FORM == 1) && (NN == 6 || NN == 7), "one-set blocks");
+    uint32_t a0, a1, a2, a3, t0, t1, t2;
+#define T2_E6_STMT(BLK)                                                                                  \
+    asm volatile(BLK : T2_ACC_OPS(lo, hi), T2_TMP_OPS, T2_NBOUT_OPS                                      \
+                 : T2_W_OPS(cur), T2_ADDR_OPS(nxt), T2_IMM_OPS(NPAT), [win] "v"(win), T2_NB_OPS(TPAT, TR, TOFF), [more] "s"(more) : TUBE2_CLOBBERS, "scc")
+#define T2_E7_STMT(BLK)                                                                                  \
+    asm volatile(BLK : T2_ACC_OPS(lo, hi), T2_TMP_OPS, T2_NBOUT_OPS, [ca] "=&v"(ca)                      \
+                 : T2_W_OPS(cur), T2_ADDR_OPS(nxt), T2_IMM_OPS(NPAT), [win] "v"(win), T2_NB_OPS(TPAT, TR, TOFF), [more] "s"(more) : TUBE2_CLOBBERS, "scc")
+    if constexpr (FORM == 0 && NN == 6 && !LAST) T2_E6_STMT(TUBE2_ASM1_B_R0_N6_OR_N0);
+    else if constexpr (FORM == 0 && NN == 6) T2_E6_STMT(TUBE2_ASM1_B_R0_N6_OR_LAST);
+    else if constexpr (FORM == 0 && !LAST) T2_E7_STMT(TUBE2_ASM1_B_R0_N7_OR_N0);
+    else if constexpr (FORM == 0) T2_E7_STMT(TUBE2_ASM1_B_R0_N7_OR_LAST);
+    else if constexpr (NN == 6 && !LAST) T2_E6_STMT(TUBE2_ASM1_B_R1_N6_OR_N0);
+    else if constexpr (NN == 6) T2_E6_STMT(TUBE2_ASM1_B_R1_N6_OR_LAST);
+    else if constexpr (!LAST) T2_E7_STMT(TUBE2_ASM1_B_R1_N7_OR_N0);
+    else T2_E7_STMT(TUBE2_ASM1_B_R1_N7_OR_LAST);
+#undef T2_E6_STMT
+#undef T2_E7_STMT
 }
 
 // Work decomposition: NO workgroup barrier after the bands are staged.  The phase stamps of the first version (one 64 x 16 tile per
@@ -866,8 +905,12 @@ __device__ __forceinline__ void t2_block_b(uint32_t (&lo)[4], uint32_t (&hi)[4],
 // a 16 x 4 pixel tile (one site per lane) with a private 24 x 8 x C image of pixel codes in LDS; it draws its next tile from a
 // workgroup counter in LDS (a workgroup still owns an XCD-contiguous run of 64 x 16 verdict tiles = 16 wave tiles each), fetches it
 // while it computes the current one, and never waits for another wave.
-template <int OUT, int PATS>
-__global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_eu(TUBE2_WAVES_PER_EU, TUBE2_WAVES_PER_EU))) stage_tube2_kernel(StageArgs a, BandArgs b) {
+// ONE: the one-set form -- the bands are staged in the rotation-closed order (mulut_core.h tube4r_*), all twelve passes of a channel add into
+// one set of 8 accumulators (TubeAcc1) and the epilogue converts every byte straight from its field.  For the packed / planar outputs of lists
+// of up to four modes (the signed numerator fits its 16-bit field); the kernel below picks the form per launch.
+template <int OUT, int PATS, bool ONE>
+__device__ __forceinline__ void stage_tube2_body(const StageArgs a, const BandArgs b) {
+    static_assert(!ONE || OUT != kOutGeneric, "the one-set form has the float epilogue of the packed / planar outputs only");
     constexpr int TW = KB_TW, TH = KB_TH, PW = kT2PW, PH = kT2PH, NT = TW * TH;
     constexpr int M = t2_modes(PATS), NP = 2 * M;
     constexpr int DW = PW / 4, PER4 = 3;         // aligned dwords per image row / per lane: channel k in register k of lanes 0 .. PH * DW - 1
@@ -995,7 +1038,17 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
         const uint4 *src = (const uint4 *)b.band[MI];
         uint4 *dst = (uint4 *)(smem + pat * kTubeBandBytes);
         const uint32_t k = b.scale[MI];
-        if (k == 0x00010001u) {
+        if constexpr (ONE) {
+            // slot by slot: both planes of a slot in, its 16 fields out in the rotation-closed order (a handful of moves per slot and workgroup)
+            for (int i = threadIdx.x; i < kTubeSlots; i += NT) {
+                const uint4 l = src[i], h = src[kTubeSlots + i];
+                const uint32_t lo[4] = {l.x, l.y, l.z, l.w}, hi[4] = {h.x, h.y, h.z, h.w};
+                uint32_t rlo[4], rhi[4];
+                tube4r_from_plain(lo, hi, rlo, rhi);
+                dst[i] = make_uint4(pk_mad(rlo[0], k, 0u), pk_mad(rlo[1], k, 0u), pk_mad(rlo[2], k, 0u), pk_mad(rlo[3], k, 0u));
+                dst[kTubeSlots + i] = make_uint4(pk_mad(rhi[0], k, 0u), pk_mad(rhi[1], k, 0u), pk_mad(rhi[2], k, 0u), pk_mad(rhi[3], k, 0u));
+            }
+        } else if (k == 0x00010001u) {
             for (int i = threadIdx.x; i < kTubeBandBytes / 16; i += NT) dst[i] = src[i];
         } else {
             for (int i = threadIdx.x; i < kTubeBandBytes / 16; i += NT) {
@@ -1079,11 +1132,14 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
                 t2_index<p0>(k0, ha, ba0, pb, pc, pd, nxt, dirty, (flat & 1u) == 0u);
             }
             RotAcc<4> acc;
+            TubeAcc1 acc1;      // (ONE: started inside the channel loop -- a set carried round the loop is copied at its edges)
             // the (0,2) fields start at -unbias (the rows are value + 128: unbias = 128 * 16 * 4 M <= 24576) where the epilogue works on K
             // more than four modes: the numerator does not fit a signed 16-bit field any more (|K| <= 8192 x modes); the pair sums still fit
             // their unsigned fields (8160 x modes <= 65280 for 8 modes), so such lists start from zero and take the biased-sum epilogue
-            const bool wide = a.M > 4;      // wave-uniform
+            // (the two-set body of a packed / planar instance only ever sees such lists: shorter ones take the one-set body)
+            const bool wide = !ONE && (OUT != kOutGeneric || a.M > 4);      // wave-uniform
             auto acc_start = [&]() {
+                if constexpr (ONE) return;
                 acc.clear();
                 if (OUT != kOutGeneric && !wide) {
                     const uint32_t nb = pk_dup((uint32_t)(65536 - 128 * kQ * 4 * a.M));      // (a.M: the modes of the list, not the patterns)
@@ -1098,6 +1154,7 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
                 const bool more = c + 1 < a.C;       // wave-uniform
                 // pairs 2 .. of this channel are tested here, pairs 0 and 1 of the next (indexed inside this channel's last two pairs) with ITS bit
                 const bool test = ((flat >> c) & 1u) == 0u, test_n = ((flat >> (c + 1)) & 1u) == 0u;
+                if constexpr (ONE) acc1.start(pk_dup((uint32_t)(65536 - 128 * kQ * 4 * a.M)));      // every field at -unbias (a.M: the modes of the list, not the patterns)
                 asm volatile("; MULUT_T2_STREAM_BEGIN (tools/ubench/gen_stream_ubench.py cuts the ISA here)");
                 static_for<0, NP>([&](auto PI) {
                     constexpr int p = PI;
@@ -1109,23 +1166,47 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
                     constexpr bool n_here = p + 1 < NP;
                     constexpr int npat = t2_pat(PATS, n_here ? (p + 1) >> 1 : 0);
                     T2Pair nn;
-                    auto &lo = R == 0 ? acc.lo02 : acc.lo13;
-                    auto &hi = R == 0 ? acc.hi02 : acc.hi13;
-                    t2_block_a<pat>(lo, hi, cur);
-                    if (t_here || more) {      // (then the next pair exists too: t_here implies n_here)
-                        t2_block_b<npat, (tp == 0 ? 7 : 6), tpat, tr, toff, false>(lo, hi, cur, nxt, win, pb, pc, pd, ca);
+                    constexpr int form = ONE ? R : -1;
+                    auto &lo = ONE ? acc1.lo : R == 0 ? acc.lo02 : acc.lo13;
+                    auto &hi = ONE ? acc1.hi : R == 0 ? acc.hi02 : acc.hi13;
+                    t2_block_a<pat, form>(lo, hi, cur);
+                    if constexpr (ONE && !t_here) {
+                        // both forms of block B in one statement (t2_block_b_either): as two statements in the arms of `if (more)` the set
+                        // was copied on entry to either arm
+                        t2_block_b_either<form, npat, (tp == 0 ? 7 : 6), tpat, tr, toff, !n_here>(lo, hi, cur, nxt, win, (uint32_t)__builtin_amdgcn_readfirstlane((int)more), pb, pc, pd, ca);
+                        if (more) {
+                            if constexpr (tp == 0) anchor(ca);
+                            t2_index<tpat>(k0, ha, ba0, pb, pc, pd, nn, dirty_n, test_n);
+                        } else {
+                            nn = nxt;
+                        }
+                    } else if (t_here || more) {      // (then the next pair exists too: t_here implies n_here)
+                        t2_block_b<form, npat, (tp == 0 ? 7 : 6), tpat, tr, toff, false>(lo, hi, cur, nxt, win, pb, pc, pd, ca);
                         if constexpr (tp == 0) anchor(ca);
                         if constexpr (t_here) t2_index<tpat>(k0, ha, ba0, pb, pc, pd, nn, dirty, test);
                         else t2_index<tpat>(k0, ha, ba0, pb, pc, pd, nn, dirty_n, test_n);
                     } else {
-                        if constexpr (n_here) t2_block_b<npat, 0, 0, 0, 0, false>(lo, hi, cur, nxt, win, pb, pc, pd, ca);
-                        else t2_block_b<npat, 0, 0, 0, 0, true>(lo, hi, cur, nxt, win, pb, pc, pd, ca);
+                        if constexpr (n_here) t2_block_b<form, npat, 0, 0, 0, 0, false>(lo, hi, cur, nxt, win, pb, pc, pd, ca);
+                        else t2_block_b<form, npat, 0, 0, 0, 0, true>(lo, hi, cur, nxt, win, pb, pc, pd, ca);
                         nn = nxt;
                     }
                     cur = nxt;
                     nxt = nn;
                 });
-                if (wide) {
+                if constexpr (ONE) {
+                    // Epilogue straight from the set: a field IS K = 16 M pred (mod 2^16, |K| < 2^15).  Per byte: one sign-extending convert of
+                    // its half, one multiply by fl(1/d), one v_cvt_pk_u8_f32 (exact for this divisor: StageArgs::use_f32)
+                    o[0] = acc1.finish_row<0>(a.inv_d); o[1] = acc1.finish_row<1>(a.inv_d);
+                    o[2] = acc1.finish_row<2>(a.inv_d); o[3] = acc1.finish_row<3>(a.inv_d);
+                    if constexpr (OUT == kOutPackedRGBU4) {
+                        if (c < 2) park()[c * NT] = make_uint4(o[0], o[1], o[2], o[3]);
+                    } else {
+                        int n2, y2, x2, lx2, ly2;
+                        site(n2, y2, x2, lx2, ly2);
+#pragma unroll
+                        for (int sy = 0; sy < 4; ++sy) *(uint32_t *)const_cast<uint8_t *>(view_addr(a.out, n2, c, y2 * 4 + sy, x2 * 4)) = o[sy];
+                    }
+                } else if (wide) {
                     tube_finish_rows_wide(a, acc, o);
                     if constexpr (OUT == kOutPackedRGBU4) {
                         if (c < 2) park()[c * NT] = make_uint4(o[0], o[1], o[2], o[3]);
@@ -1223,6 +1304,18 @@ __global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_
 #undef T2_STAMP
 }
 
+// The form is chosen per launch (kernel-argument uniform: one scalar branch ahead of everything): one set where stage_tube2_one_set()
+// says so, else two.  Both bodies are instances of the one template above.
+template <int OUT, int PATS>
+__global__ void __launch_bounds__(KB_TW *KB_TH) __attribute__((amdgpu_waves_per_eu(TUBE2_WAVES_PER_EU, TUBE2_WAVES_PER_EU))) stage_tube2_kernel(StageArgs a, BandArgs b) {
+    if constexpr (OUT == kOutGeneric) {
+        stage_tube2_body<OUT, PATS, false>(a, b);
+    } else {
+        if (a.M <= 4) stage_tube2_body<OUT, PATS, true>(a, b);
+        else stage_tube2_body<OUT, PATS, false>(a, b);
+    }
+}
+
 constexpr int kT2PatsSDY = 3 | (0 << 2) | (1 << 4) | (2 << 6);
 
 // how many modes of the launch have pattern s, d, y; false if a mode has none of them
@@ -1249,6 +1342,14 @@ bool stage_tube2_supported(const StageArgs &a) {
     // or integer epilogue)
     return a.C <= 3 && a.M <= kMaxTube2Modes && tube2_counts(a, cnt) && cnt[0] && cnt[1] && cnt[2] && (a.M > 4 || a.use_f32) &&
            a.bias_num == 0;
+}
+
+// The one-set form (all four rotations in one accumulator set, on the band staged in the rotation-closed order) applies where the
+// signed-numerator epilogue does: packed / planar output and at most four modes (what stage_tube2_kernel itself branches on).  Longer lists
+// and the generic output keep two sets on the plain order.
+bool stage_tube2_one_set(const StageArgs &a, int out_mode) {
+    const bool fast_out = out_mode == kOutPlanarU4 || (out_mode == kOutPackedRGBU4 && a.C == 3);
+    return stage_tube2_supported(a) && fast_out && a.M <= 4;
 }
 
 template <int OUT>

@@ -60,6 +60,66 @@ def mac8(j, rev):
     return o
 
 
+def row_elem(r, sy, sx):
+    """mulut_core.h row_elem at u = 4: the row element that lands on block position (sy, sx) under rotation r"""
+    return [sy * 4 + sx, (3 - sx) * 4 + sy, (3 - sy) * 4 + (3 - sx), sx * 4 + (3 - sy)][r]
+
+
+def oneset_maps():
+    """The rotation-closed placement (mulut_core.h tube4r_*): position rho^k p_i -> (plane k & 1, dword i, half k >> 1), rho = rotation
+    1's map on block positions, p_i the smallest position of orbit i.  Returns [r][row plane] -> (accumulator plane, halves swapped);
+    the emitted file static_asserts the table against the header's constexpr map."""
+    rho = lambda p: row_elem(1, p >> 2, p & 3)
+    place, reps = {}, []
+    for p in range(16):
+        if p in place:
+            continue
+        reps.append(p)
+        q = p
+        for k in range(4):
+            place[q] = (k & 1, len(reps) - 1, k >> 1)
+            q = rho(q)
+        assert q == p
+    at = {v: k for k, v in place.items()}
+    maps = []
+    for r in range(4):
+        m = []
+        for plane in range(2):
+            seen = set()
+            for i in range(4):
+                for half in range(2):
+                    e = at[(plane, i, half)]
+                    p = [q for q in range(16) if row_elem(r, q >> 2, q & 3) == e][0]       # the block position this row field lands on
+                    ap, ai, ah = place[p]
+                    assert ai == i
+                    seen.add((ap, ah ^ half))
+            assert len(seen) == 1, (r, plane, seen)
+            m.append(seen.pop())
+        assert m[0][0] != m[1][0]
+        maps.append(m)
+    return maps
+
+
+ONESET = oneset_maps()
+
+
+def mac8_one(j, rot):
+    """one-set form: acc += row j * weight j for rotation rot on the rotation-closed band.  Row plane P dword k goes to accumulator
+    plane ONESET[rot][P][0] dword k, halves swapped (op_sel on src0) iff ONESET[rot][P][1]; rotations 2 and 3 are the second pass
+    of their pair (weights in the high halves)."""
+    wh = rot >> 1
+    src = {}
+    for plane in range(2):
+        ap, sw = ONESET[rot][plane]
+        src[ap] = (plane, sw)
+    o = []
+    for k in range(4):
+        for ap, nm in ((0, "l"), (1, "h")):
+            plane, sw = src[ap]
+            o.append("v_pk_mad_u16 %%[%s%d], %s, %%[w%d], %%[%s%d] op_sel:[%d,%d,0] op_sel_hi:[%d,%d,1]" % (nm, k, row(j, 4 * plane + k), j, nm, k, sw, wh, 1 - sw, wh))
+    return o
+
+
 def row_loads(j):
     a = "a%d" % (j if j < 4 else 0)
     lo, hi = ("ilo", "ihi") if j < 4 else ("ilo4", "ihi4")
@@ -121,9 +181,9 @@ def rows_tags(p):
     return ["%s%d%s" % (p, j, h) for j in range(5) for h in ("l", "h")]
 
 
-def block(q, rev, nn, loads, addr_half, cur, nxt):
+def block(q, rev, nn, loads, addr_half, cur, nxt, rot=None):
     """One pass on the queue q (which holds the reads of this pass's rows, tags cur + row + plane).  rev: reversed (second) pass of
-    the pair.  nn: neighbour codes fetched in this block (0, 6, or 7 with the anchor): issued after the first wait, merged at the
+    the pair.  rot: one-set form, the pass's rotation (its MACs from mac8_one; everything else is the same block).  nn: neighbour codes fetched in this block (0, 6, or 7 with the anchor): issued after the first wait, merged at the
     end -- they land in the block's own output operands, so nothing of theirs is in flight when the block ends.  loads: refill a
     row's registers with the next pass's row (tags nxt...) right after its MACs (addresses from half addr_half of base / s0..s2)."""
     o = q.out
@@ -139,7 +199,7 @@ def block(q, rev, nn, loads, addr_half, cur, nxt):
             q.issue(["n%d" % i for i in range(nn)])
             o += nb_loads(nn == 7)
         if DEBUG != 5:
-            o += mac8(j, rev)
+            o += mac8(j, rev) if rot is None else mac8_one(j, rot)
         if loads:
             q.issue(["%s%dl" % (nxt, j), "%s%dh" % (nxt, j)])
             if DEBUG != 4:
@@ -147,6 +207,14 @@ def block(q, rev, nn, loads, addr_half, cur, nxt):
     if nn:
         q.need(["n%d" % i for i in range(7)])
         o += unpack(nn == 7)
+
+
+def either(more_lines, last_lines):
+    """Two forms of a block in ONE asm statement, chosen by the wave-uniform operand %[more] (an SGPR): to the compiler it is straight-line
+    code.  As two statements in the arms of a branch the accumulators, tied operands of both, stay live across each other's arm and the
+    whole set is copied on entry to either (8 v_mov_b32 per arm)."""
+    return (["s_cmp_eq_u32 %[more], 0", "s_cbranch_scc1 .Lt2_last_%="] + list(more_lines) + ["s_branch .Lt2_done_%=", ".Lt2_last_%=:"] + list(last_lines) +
+            [".Lt2_done_%=:"])
 
 
 def cstr(name, lines):
@@ -185,6 +253,33 @@ def main():
     block(ql, True, 0, False, 0, "B", "A")
     assert ql.q == [], ql.q
     out.append(cstr("TUBE2_ASM_B_LAST", ql.out))
+    # The one-set form (rotation-closed band, one accumulator set for all four rotations): the same blocks per rotation class R = 0, 1
+    # of the pair -- A is rotation R, B rotation R + 2 -- with the MACs of mac8_one; refills, waits and neighbour fetches are unchanged.
+    out.append("// one-set blocks: [rotation][row plane] -> accumulator plane / halves swapped, checked against mulut_core.h")
+    out.append("static_assert(" + " && ".join("tube4r_acc_plane(%d, %d) == %d && tube4r_swap(%d, %d) == %d" % (r, pl, ONESET[r][pl][0], r, pl, ONESET[r][pl][1])
+                                                for r in range(4) for pl in range(2)) + ', "tools/gen_tube2_asm.py and mulut_core.h disagree on the rotation-closed placement");')
+    out.append("")
+    # The last two pairs of a channel have a form for "another channel follows" (the next channel's neighbour codes are fetched: N6 / N7)
+    # and one for the site's last channel (N0, and LAST for the very last pass): _N<k>_OR_<form> holds both behind a scalar branch.
+    for R in (0, 1):
+        qa = Queue(rows_tags("A"), [])
+        block(qa, False, 0, True, 1, "A", "B", rot=R)
+        out.append(cstr("TUBE2_ASM1_A_R%d" % R, qa.out))
+        forms = {}
+        for nn in (0, 6, 7):
+            qb = Queue(qa.q, [])
+            block(qb, True, nn, True, 0, "B", "A", rot=R + 2)
+            assert qb.q == rows_tags("A"), qb.q
+            forms["N%d" % nn] = qb.out
+            out.append(cstr("TUBE2_ASM1_B_R%d_N%d" % (R, nn), qb.out))
+        ql = Queue(qa.q, [])
+        block(ql, True, 0, False, 0, "B", "A", rot=R + 2)
+        assert ql.q == [], ql.q
+        forms["LAST"] = ql.out
+        out.append(cstr("TUBE2_ASM1_B_R%d_LAST" % R, ql.out))
+        for nn in (6, 7):
+            for last in ("N0", "LAST"):
+                out.append(cstr("TUBE2_ASM1_B_R%d_N%d_OR_%s" % (R, nn, last), either(forms["N%d" % nn], forms[last])))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     if DEBUG or os.environ.get("TUBE2_TAG"):     # timing-only generations: built with -DMULUT_TUBE2_ASM_INC='"<path>"'
         path = os.path.join(root, "tools", "experiments", "tube2_timing", "mulut_tube2_asm_dbg%s.inc" % os.environ.get("TUBE2_TAG", DEBUG))
