@@ -898,5 +898,83 @@ MULUT_HD bool rhe_f32_valid(int kmin, int kmax, DivMagic m, float inv_d) {
     return true;
 }
 
+// ---- fix-up of the tube kernels' work list, lists of up to four modes (stage_up_fix2_kernel) ---------------
+// A lane holds one pass (mode, rotation) of a listed sample.  Its five weighted rows are summed per row dword in two packed
+// accumulators, as the slab kernel does: F += dword * w on the RAW dword (a 16-bit field then holds 256 * odd byte + even byte,
+// sums wrap mod 2^16) and H += odd bytes * w.  H is exact (<= 16 * 255 = 4080) and the even fields come back as F - 256 H
+// mod 2^16 (slab_even_sums): twelve instructions per row.  The results are the plain band order lo_k = e(4k) | e(4k+2) << 16
+// (even) and hi_k = e(4k+1) | e(4k+3) << 16 (odd) of one pass.
+MULUT_HD uint32_t fix2_odd_bytes(uint32_t d) {      // e(4k+1) | e(4k+3) << 16 of row dword k
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(0u, d, 0x0C030C01u);
+#else
+    return (d >> 8) & 0x00FF00FFu;
+#endif
+}
+MULUT_HD void fix2_mac_row(uint32_t (&F)[4], uint32_t (&H)[4], const uint32_t (&row)[4], uint32_t w) {
+    for (int k = 0; k < 4; ++k) {
+        F[k] = pk_mad_w<0>(row[k], w, F[k]);
+        H[k] = pk_mad_w<0>(fix2_odd_bytes(row[k]), w, H[k]);
+    }
+}
+// X[0..3] = lo_k, X[4..7] = hi_k of the pass
+MULUT_HD void fix2_pass_sums(const uint32_t (&F)[4], const uint32_t (&H)[4], uint32_t (&X)[8]) {
+    for (int k = 0; k < 4; ++k) {
+        X[k] = slab_even_sums(F[k], H[k]);
+        X[4 + k] = H[k];
+    }
+}
+// A group's sixteen LDS dwords are the two accumulator sets of RotAcc<4> in the plain order: dwords 0-3 lo02, 4-7 hi02, 8-11 lo13,
+// 12-15 hi13.  Rotation r adds dword j of X to dword fix2_slot(r, j) after rotating it right by fix2_swap(r) bits: rotations 0 and 1
+// in place into their set, rotations 2 and 3 in reversed element order (lo_k -> hi_(3-k), hi_k -> lo_(3-k), halves swapped), as
+// RotAcc<4>::mac_x does in registers.  A field holds at most 4 M x 4080 <= 65,280 for M <= 4: the dword adds never carry
+// between the halves.
+MULUT_HD constexpr int fix2_slot(int r, int j) { return (r & 1) * 8 + (j ^ ((r & 2) ? 7 : 0)); }
+MULUT_HD constexpr uint32_t fix2_swap(int r) { return (r & 2) ? 16u : 0u; }
+MULUT_HD uint32_t fix2_rotr(uint32_t x, uint32_t s) {      // s in {0, 16}
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(x, x, s);
+#else
+    return s ? (x >> 16) | (x << 16) : x;
+#endif
+}
+// Block position p = 4 sy + sx is field p of set (0,2) plus field 12 + sy - 4 sx of set (1,3) (tube_finish_rows); field E of a set
+// lies in 16-bit half fix2_field_half(set, E) of the group's 32 halves (little-endian dwords).
+MULUT_HD constexpr int fix2_partner(int p) { return 12 + (p >> 2) - 4 * (p & 3); }
+MULUT_HD constexpr int fix2_field_half(int set, int E) { return set * 16 + ((E & 1) * 4 + (E >> 2)) * 2 + ((E >> 1) & 1); }
+
+// Entry decode: id = (n H + y) W + x < 2^30 without the division sequence.  For a divisor d >= 2 with 2^f <= d < 2^(f+1) take
+// s = f - 1 and magic = ceil(2^(32+s) / d) <= 2^31; the error e = magic d - 2^(32+s) is below d, and floor(id / d) ==
+// (id * magic) >> (32 + s) for every id with e * id < 2^(32+s) (Granlund-Montgomery), which `exact` states for id < 2^30.
+struct Recip30 {
+    uint32_t d, magic, shift, exact;
+};
+MULUT_HD Recip30 make_recip30(uint32_t d) {
+    Recip30 r;
+    r.d = d;
+    r.magic = r.shift = r.exact = 0;
+    if (d < 2) return r;
+    r.shift = (uint32_t)(30 - __builtin_clz(d));
+    const uint64_t p = 1ull << (32 + r.shift), m = (p + d - 1) / d, e = m * d - p;
+    r.magic = (uint32_t)m;
+    r.exact = ((m >> 32) == 0 && e * ((1ull << 30) - 1) < p) ? 1u : 0u;
+    return r;
+}
+MULUT_HD uint32_t recip30_div(uint32_t id, const Recip30 &r) { return (uint32_t)(((uint64_t)id * r.magic) >> 32) >> r.shift; }
+// x, y, n of an id; `fast` = both reciprocals exact (the caller tests it once), else the plain divisions
+MULUT_HD void fix2_decode(uint32_t id, uint32_t W, uint32_t H, const Recip30 &rw, const Recip30 &rwh, bool fast, int &x, int &y, int &n) {
+    uint32_t row, img;
+    if (fast) {
+        row = recip30_div(id, rw);
+        img = recip30_div(id, rwh);
+    } else {
+        row = id / W;
+        img = id / (W * H);
+    }
+    x = (int)(id - row * W);
+    y = (int)(row - img * H);
+    n = (int)img;
+}
+
 }  // namespace mulut
 #endif  // MULUT_CORE_H_

@@ -660,8 +660,22 @@ __global__ void __launch_bounds__(TW *TH) stage_tube_kernel(StageArgs a, BandArg
 // -- two dependent trips for the whole sample -- multiplied out per row element and added into the group's 16 LDS sums at the block
 // positions that rotation maps the elements to; lane e then finishes block position e (divide, round half to even, clip) and
 // stores its byte.
-__global__ void __launch_bounds__(256) stage_up_fix2_kernel(StageArgs a) {
-    __shared__ int s_sum[16][16];
+// dst = a + (byte K of b): one SDWA add
+template <int K>
+__device__ __forceinline__ uint32_t add_byte_k(uint32_t a, uint32_t b) {
+    static_assert(K >= 0 && K < 3, "byte 0, 1 or 2");
+    uint32_t r;
+    if constexpr (K == 0) asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "v"(a), "v"(b));
+    if constexpr (K == 1) asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "v"(a), "v"(b));
+    if constexpr (K == 2) asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// LDS add at an integer byte address (no return value)
+__device__ __forceinline__ void lds_add_u32(uint32_t addr, uint32_t v) {
+    __hip_atomic_fetch_add((__attribute__((address_space(3))) uint32_t *)(uintptr_t)addr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ __forceinline__ void fix2_any_modes(const StageArgs &a, int (&s_sum)[16][16]) {
     const uint32_t count = *a.fix_count;
     const int grp = (int)(threadIdx.x >> 4), ln = (int)(threadIdx.x & 15);
     const int ylo = imax(a.oy0 - kHalo, 0), yhi = imin(a.oy1 + kHalo, a.H) - 1;
@@ -715,6 +729,97 @@ __global__ void __launch_bounds__(256) stage_up_fix2_kernel(StageArgs a) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // sums read before the next round clears them
         }
     }
+}
+
+
+// Lists of up to four modes: 4 M <= 16, so lane ln holds pass (mode ln >> 2, rotation ln & 3) for the whole kernel and everything
+// that depends on the pass alone -- rotated sampling offsets, table, destination set, reversal -- is made before the list walk.
+// Rows are summed as packed 16-bit pairs and the group's LDS sums are the two sets of RotAcc<4> (mulut_core.h fix2_*): eight
+// ds_add_u32 per pass at lane-constant addresses, no selection by rotation.  The entry is decoded with reciprocals made once, its
+// clamps are taken once per entry, and pixel offsets inside a plane are 32-bit (the caller has checked that they fit).
+__device__ __forceinline__ void fix2_four_modes(const StageArgs &a, int (&s_sum)[16][16]) {
+    const uint32_t count = *a.fix_count;
+    const int grp = (int)(threadIdx.x >> 4), ln = (int)(threadIdx.x & 15);
+    const int ylo = imax(a.oy0 - kHalo, 0), yhi = imin(a.oy1 + kHalo, a.H) - 1;
+    const int unbias = 128 * kQ * 4 * a.M - a.bias_num;
+    const bool act = ln < 4 * a.M;
+    const int m = act ? ln >> 2 : 0, r = ln & 3;
+    // the pass's three rotated offsets, + 4 each (1 .. 7), one per byte: an SDWA add extracts and adds
+    uint32_t dy4 = 0u, dx4 = 0u;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        int dy, dx;
+        sample_offset(r, a.di[m][k], a.dj[m][k], dy, dx);
+        dy4 |= (uint32_t)(dy + 4) << (8 * k);
+        dx4 |= (uint32_t)(dx + 4) << (8 * k);
+    }
+    const char *tab = (const char *)a.lut[m];
+    uint32_t *sum = (uint32_t *)s_sum[grp];
+    // dword j of a pass goes to dword fix2_slot(r, j) = 8 (r & 1) + (j ^ flip) of the group's sums: one address register, the
+    // flip is an exclusive or with the constant 4 j on the byte address (a group's sums are 64-byte aligned)
+    const uint32_t dst0 = lds_addr_of(sum + fix2_slot(r, 0));
+    const uint32_t swap = fix2_swap(r);
+    const uint16_t *f02 = (const uint16_t *)sum + fix2_field_half(0, ln), *f13 = (const uint16_t *)sum + fix2_field_half(1, fix2_partner(ln));
+    const uint32_t W = (uint32_t)a.W, H = (uint32_t)a.H;
+    const Recip30 rw = make_recip30(W), rwh = make_recip30(W * H);
+    const bool fast = rw.exact != 0 && rwh.exact != 0;      // wave-uniform
+    const uint32_t sY = (uint32_t)a.in.sY, sX = (uint32_t)a.in.sX;
+    for (uint32_t i = blockIdx.x * 16u + (uint32_t)grp; i < count; i += gridDim.x * 16u) {
+        const uint32_t ent = a.fix_list[i], id = ent & 0x3FFFFFFFu, only = ent >> 30;
+        int x, y, n;
+        fix2_decode(id, W, H, rw, rwh, fast, x, y, n);
+        if (n >= a.N || y < a.oy0 || y >= a.oy1) continue;      // never follow an entry outside the launch (a list bug must show as a wrong pixel, not as a memory fault)
+        // channels [c_lo, c_hi): only < 3 names one, only == 3 every one
+        const int c_lo = (int)only - 3 * (int)((only + 1u) >> 2), c_hi = imin(imin(a.C, 3), (int)only + 1);
+        const uint8_t *src = a.in.p + (long long)n * a.in.sN + (long long)c_lo * a.in.sC;
+        const uint8_t *pa = src + ((uint32_t)(y - a.in.row0) * sY + (uint32_t)x * sX), *pk[3];
+        const uint32_t y4 = (uint32_t)(y - 4), x4 = (uint32_t)(x - 4);
+        static_for<0, 3>([&](auto K) {
+            const int gy = imin(imax((int)add_byte_k<K>(y4, dy4), ylo), yhi), gx = imin(imax((int)add_byte_k<K>(x4, dx4), 0), a.W - 1);
+            pk[K] = src + ((uint32_t)(gy - a.in.row0) * sY + (uint32_t)gx * sX);
+        });
+        uint8_t *out = const_cast<uint8_t *>(view_addr(a.out, n, c_lo, y * 4 + (ln >> 2), x * 4 + (ln & 3)));
+        for (int c = c_lo; c < c_hi; ++c, pa += a.in.sC, pk[0] += a.in.sC, pk[1] += a.in.sC, pk[2] += a.in.sC, out += a.out.sC) {
+            sum[ln] = 0;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            const int va = (int)*pa;
+            if (act) {
+                const int v0 = (int)*pk[0], v1 = (int)*pk[1], v2 = (int)*pk[2];
+                int idx[5], w[5];
+                simplex4(va, v0, v1, v2, idx, w);
+                uint32_t row[5][4];
+#pragma unroll
+                for (int j = 0; j < 5; ++j) {
+                    const uint4 t = *(const uint4 *)(tab + ((uint32_t)idx[j] << 4));
+                    row[j][0] = t.x; row[j][1] = t.y; row[j][2] = t.z; row[j][3] = t.w;
+                }
+                uint32_t F[4] = {0u, 0u, 0u, 0u}, Hs[4] = {0u, 0u, 0u, 0u}, X[8];
+#pragma unroll
+                for (int j = 0; j < 5; ++j) fix2_mac_row(F, Hs, row[j], (uint32_t)w[j]);
+                fix2_pass_sums(F, Hs, X);
+                uint32_t d0 = dst0;
+                asm volatile("" : "+v"(d0));      // keeps the eight addresses out of registers that live across the list walk
+                static_for<0, 8>([&](auto J) { lds_add_u32(d0 ^ (uint32_t)(4 * J), fix2_rotr(X[J], swap)); });
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            const uint32_t b = rhe_clip_u8((int)((uint32_t)*f02 + (uint32_t)*f13) - unbias, a.div);
+            *out = (uint8_t)b;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // sums read before the next round clears them
+        }
+    }
+}
+
+// whether every pixel of the rows this launch reads lies at a non-negative 32-bit offset inside its plane (wave-uniform)
+__device__ __forceinline__ bool fix2_offsets_fit(const StageArgs &a) {
+    const int ylo = imax(a.oy0 - kHalo, 0), yhi = imin(a.oy1 + kHalo, a.H) - 1;
+    if (a.in.sY < 0 || a.in.sX < 0 || ylo < a.in.row0 || yhi < ylo || a.W < 1) return false;
+    return (unsigned long long)(yhi - a.in.row0) * (unsigned long long)a.in.sY + (unsigned long long)(a.W - 1) * (unsigned long long)a.in.sX < (1ull << 32);
+}
+
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) stage_up_fix2_kernel(StageArgs a) {
+    __shared__ __attribute__((aligned(64))) int s_sum[16][16];      // a group's sums: 64 bytes on a 64-byte boundary
+    if (a.M <= 4 && fix2_offsets_fit(a)) fix2_four_modes(a, s_sum);      // wave-uniform
+    else fix2_any_modes(a, s_sum);
 }
 
 hipError_t launch_stage_up_fix(const StageArgs &a, int num_cus, hipStream_t st) {
