@@ -230,6 +230,26 @@ int mulut_ft_wide_stage_forward(int device, int interval, const float *const *we
 int mulut_ft_wide_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
                                  const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
                                  float *const *grad_wq, float *grad_x, void *stream);
+/* A fine-tune batch cut on the device from a device-resident training set: DIV2K.__getitem__ (sr/data.py:91-121, restated by
+ * CropProvider.next() of mulut_amd/finetune_lut.py) for B samples in one launch.  The reference draws and cuts in DataLoader
+ * workers (sr/data.py:27-49); here the host draws six integers per sample and the device does the rest.
+ *   pool   : device bytes holding every image as the PNG decodes, HWC uint8 with `ch` channels (grey: ch = 1)
+ *   pairs  : device table, one entry per (LR, HR) pair: byte offsets of the two images in `pool` and their sizes
+ *            (hr_w need not be lr_w * scale: the HR window is read at the HR image's own width)
+ *   draws  : device int32 [B][6] = pair, i, j, c, flips (bit 0 np.fliplr, bit 1 np.flipud), k (np.rot90's k, taken mod 4)
+ *   im, lb : device float32 [B][1][sz][sz] and [B][1][sz*scale][sz*scale]; 16-byte aligned bases with sz (sz*scale) a
+ *            multiple of 4 take 16-byte stores, anything else float stores -- the same result
+ * Sample b: LR rows i..i+sz, columns j..j+sz, channel c and the same window times `scale` of the HR image; fliplr if bit 0, then
+ * flipud if bit 1, then rot90 by k; value = float32(byte) / 255.0f, IEEE division (NumPy's result for all 256 bytes).
+ * Refusals, before the device is touched: NULL pool, pairs, draws, im or lb, or a non-positive B, sz, n_pairs or pool_bytes
+ * MULUT_EINVAL; then scale outside 1..4 MULUT_EUNSUPPORTED; then B * (sz*scale)^2 >= 2^31 MULUT_EUNSUPPORTED.
+ * The draws are device memory, so each sample is checked by the kernel: pair in 0..n_pairs-1, 0 <= c < ch, i, j >= 0,
+ * i + sz <= lr_h, j + sz <= lr_w, the scaled window inside hr_h x hr_w, and both images inside [0, pool_bytes).  A sample that fails
+ * is written as zeros and adds one to *bad (device int the CALLER zeroes; NULL: not counted); no address is formed from it, so
+ * nothing outside the pool is ever read.  Stateless and stream-ordered, like the calls above. */
+typedef struct { long long lr_off, hr_off; int lr_h, lr_w, hr_h, hr_w, ch, pad; } mulut_ft_pair;   /* 40 bytes, offsets into pool */
+int mulut_ft_crop_batch(int device, const unsigned char *pool, long long pool_bytes, const mulut_ft_pair *pairs, int n_pairs,
+                        const int *draws, int B, int sz, int scale, float *im, float *lb, int *bad, void *stream);
 
 /* ---- device-side evaluation (not on the inference path) ---------------------------------------------------
  * Y-channel PSNR and SSIM of a super-resolved frame against its ground truth, exactly as the test script scores

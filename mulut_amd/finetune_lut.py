@@ -12,8 +12,16 @@ Training pairs: ``{trainDir}/HR/<stem>.png`` with ``{trainDir}/LR/X{scale}/<stem
 (:23-65): every ``--valStep`` iterations (and at iteration 1) each benchmark image goes through the module, the result is
 saved as ``{valoutDir}/{dataset}/{last '_'-token of the stem}_lutft.png`` (the reference's naming) and Y-PSNR / SSIM are averaged per dataset -- computed on the device
 (``mulut_eval_y``), logged with the reference's line.
+
+Training batches come from ``DeviceCropProvider``: the pairs lie on the device as the uint8 bytes the PNGs hold and one HIP launch
+(``mulut_ft_crop_batch``) cuts, flips, turns and converts a batch from six host-drawn integers per sample -- the same batches, bit for
+bit, as ``CropProvider`` (the reference's host path, kept as ``--hostData`` and as the fallback when the set does not fit the device)
+gives for the same ``--seed``.  The loop does not wait for the device per step: losses go into a device vector that is read every
+``--displayStep`` iterations, so the logged ``rT`` is WALL time per iteration between two display points (data, step and the read-back
+included), not the reference's host-side time of the step alone.
 """
 import argparse
+import ctypes
 import math
 import os
 import random
@@ -68,6 +76,92 @@ class CropProvider:
             lbs.append(np.rot90(lb, k).astype(np.float32)[None] / 255.0)
             ims.append(np.rot90(im, k).astype(np.float32)[None] / 255.0)
         return torch.from_numpy(np.stack(ims)).cuda(), torch.from_numpy(np.stack(lbs)).cuda()
+
+
+class TrainingSetTooLarge(Exception):
+    """The packed training set is larger than the caller allows on the device; ``host`` is the loaded CropProvider (same seed, no
+    draw taken yet) to go on with."""
+
+    def __init__(self, nbytes, limit, host):
+        super().__init__("training set of %d bytes exceeds the %d allowed on the device" % (nbytes, limit))
+        self.nbytes, self.limit, self.host = nbytes, limit, host
+
+
+class DeviceCropProvider:
+    """CropProvider's batches, bit for bit for the same seed, cut on the device (mulut_ft_crop_batch): the pairs CropProvider accepts,
+    in its order, lie in one uint8 device tensor as the PNGs decode; next() draws pair, i, j, c, the two flips and k per sample from
+    random.Random(seed) in CropProvider's order, sends those B x 6 integers through a ring of pinned buffers and launches once on
+    the current stream.  next() never waits for the device unless the host is RING batches ahead of it: a slot's event, recorded
+    behind its copy, is waited for before the slot is rewritten."""
+    RING = 32
+
+    def __init__(self, path, scale, patch, batch, seed=None, max_bytes=None):
+        host = CropProvider(path, scale, patch, batch, seed)      # the same scan: the same pairs in the same order
+        self.scale, self.sz, self.batch = scale, patch, batch
+        self.rng = host.rng
+        table, off = np.zeros((len(host.pairs), 10), np.int32), 0
+        t64 = table.view(np.int64)                                 # mulut_ft_pair: two 64-bit offsets, then lr_h, lr_w, hr_h, hr_w, ch, pad
+        for n, (lr_im, hr_im) in enumerate(host.pairs):
+            if lr_im.dtype != np.uint8 or hr_im.dtype != np.uint8 or lr_im.shape[2] != hr_im.shape[2]:
+                raise ValueError("pair %d is not a pair of 8-bit images with the same channels (--hostData takes it)" % n)
+            t64[n, 0], t64[n, 1] = off, off + lr_im.size
+            table[n, 4:9] = lr_im.shape[0], lr_im.shape[1], hr_im.shape[0], hr_im.shape[1], lr_im.shape[2]
+            off += lr_im.size + hr_im.size
+        self.pool_bytes = off
+        if max_bytes is not None and off > max_bytes:
+            raise TrainingSetTooLarge(off, max_bytes, host)
+        self.shapes = [im.shape for im, _ in host.pairs]           # (lr_h, lr_w, ch) per pair: all the draws need
+        self.device = torch.empty(0).cuda().device
+        self.pool = torch.empty(off, dtype=torch.uint8, device=self.device)
+        for n, (lr_im, hr_im) in enumerate(host.pairs):            # image by image: no second copy of the set on the host
+            a = int(t64[n, 0])
+            self.pool[a:a + lr_im.size].copy_(torch.from_numpy(np.ascontiguousarray(lr_im).reshape(-1)))
+            self.pool[a + lr_im.size:a + lr_im.size + hr_im.size].copy_(torch.from_numpy(np.ascontiguousarray(hr_im).reshape(-1)))
+        self.table = torch.from_numpy(table).cuda()
+        self.bad = torch.zeros(1, dtype=torch.int32).cuda()         # samples the kernel refused: stays 0 (the draws are legal by construction)
+        if self.pool.is_cuda:
+            torch.cuda.synchronize(self.device)                    # the set is in place whatever stream next() is called on
+        self._ring, self._events, self._slot, self._lib = None, None, 0, None
+
+    def draw(self, out=None):
+        """The host half of next(): the batch's draws as int32 [B][6] = pair, i, j, c, flips (bit 0 lr, bit 1 ud), k."""
+        out = np.empty((self.batch, 6), np.int32) if out is None else out
+        rng, sz, shapes, pairs, ks, rows = self.rng, self.sz, self.shapes, range(len(self.shapes)), [0, 1, 2, 3], []
+        for _ in range(self.batch):
+            n = rng.choice(pairs)
+            h, w, ch = shapes[n]
+            i = rng.randint(0, h - sz)
+            j = rng.randint(0, w - sz)
+            c = rng.randrange(ch)
+            lr = rng.uniform(0, 1) < 0.5
+            ud = rng.uniform(0, 1) < 0.5
+            rows.append((n, i, j, c, lr + 2 * ud, rng.choice(ks)))
+        out[:] = rows
+        return out
+
+    def next(self):
+        if self._ring is None:
+            from . import _native
+            self._lib = _native.load()
+            self._ring = [torch.empty((self.batch, 6), dtype=torch.int32).pin_memory() for _ in range(self.RING)]
+            self._events = [None] * self.RING
+        slot, self._slot = self._slot, (self._slot + 1) % self.RING
+        if self._events[slot] is not None:
+            self._events[slot].synchronize()                       # (returns at once unless the host is RING batches ahead)
+        else:
+            self._events[slot] = torch.cuda.Event()
+        self.draw(self._ring[slot].numpy())
+        stream = torch.cuda.current_stream(self.device)
+        draws = self._ring[slot].to(self.device, non_blocking=True)
+        self._events[slot].record(stream)
+        im = torch.empty((self.batch, 1, self.sz, self.sz), dtype=torch.float32, device=self.device)
+        lb = torch.empty((self.batch, 1, self.sz * self.scale, self.sz * self.scale), dtype=torch.float32, device=self.device)
+        rc = self._lib.mulut_ft_crop_batch(self.device.index, self.pool.data_ptr(), self.pool_bytes, self.table.data_ptr(), len(self.shapes),
+                                           draws.data_ptr(), self.batch, self.sz, self.scale, im.data_ptr(), lb.data_ptr(),
+                                           self.bad.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+        if rc:
+            raise RuntimeError(self._lib.mulut_strerror(rc).decode())
+        return im, lb
 
 
 def valid_steps(net, opt, it, log=print):
@@ -139,6 +233,8 @@ def build_parser():
     p.add_argument('--lr1', type=float, default=1e-4)
     p.add_argument('--weightDecay', type=float, default=0)
     p.add_argument('--seed', type=int, default=None)
+    p.add_argument('--hostData', default=False, action='store_true',
+                   help='cut the batches on the host (CropProvider, the reference\'s path) instead of on the device')
     return p
 
 
@@ -155,27 +251,41 @@ def finetune(opt, log=print):
         lr_a = 1 - lr_b
         lf = lambda x: (((1 + math.cos(x * math.pi / opt.totalIter)) / 2) ** 1.0) * lr_a + lr_b   # noqa: E731
     sched = torch.optim.lr_scheduler.LambdaLR(optim, lr_lambda=lf)
-    data = CropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed)
-    accum, t_run, losses = 0.0, 0.0, []
+    if getattr(opt, "hostData", False):
+        data = CropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed)
+    else:
+        try:      # the set stays on the device for the whole run: at most half of what is free now
+            data = DeviceCropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, max_bytes=torch.cuda.mem_get_info()[0] // 2)
+        except TrainingSetTooLarge as e:
+            log("{} | training set of {} bytes exceeds half the free device memory ({}): batches are cut on the host".format(opt.expDir, e.nbytes, e.limit))
+            data = e.host
     if getattr(opt, "valoutDir", None) is None:
         opt.valoutDir = os.path.join(opt.expDir, "val")
+    # the loop never waits for the device per step: every loss goes into this vector, read at the display points and at the end
+    loss_buf = torch.zeros(opt.totalIter, dtype=torch.float32, device="cuda")
+    losses, t_mark = [], time.time()
     for i in range(1, opt.totalIter + 1):
         im, lb = data.next()
-        st = time.time()
         optim.zero_grad()
         loss = F.mse_loss(net(im), lb)
         loss.backward()
         optim.step()
         sched.step()
-        accum += loss.item()
-        t_run += time.time() - st
-        losses.append(loss.item())
+        loss_buf[i - 1] = loss.detach()
         if i % opt.displayStep == 0:
+            losses.extend(loss_buf[len(losses):i].tolist())        # (waits for the device)
+            # rT: wall time per iteration since the last display point (or the start), validation left out
             log("{} | Iter:{:6d}, Sample:{:6d}, GPixel:{:.2e}, rT:{:.4f}".format(opt.expDir, i, i * opt.batchSize,
-                                                                               accum / opt.displayStep, t_run / opt.displayStep))
-            accum, t_run = 0.0, 0.0
+                                                                               sum(losses[i - opt.displayStep:i]) / opt.displayStep,
+                                                                               (time.time() - t_mark) / opt.displayStep))
+            t_mark = time.time()
         if getattr(opt, "valStep", 0) and (i % opt.valStep == 0 or i == 1) and os.path.isdir(getattr(opt, "valDir", "")):   # :152-158
+            t_val = time.time()
             valid_steps(net, opt, i, log)
+            t_mark += time.time() - t_val
+    losses.extend(loss_buf[len(losses):opt.totalIter].tolist())
+    if isinstance(data, DeviceCropProvider) and int(data.bad.item()):
+        raise RuntimeError("mulut_ft_crop_batch refused %d samples" % int(data.bad.item()))
     for key, table in net.export_int8().items():                          # :162-169
         np.save(os.path.join(opt.expDir, "LUT_ft_x{}_{}bit_int8_{}.npy".format(opt.scale, opt.interval, key)), table)
     log("Finetuned LUT saved to {}".format(opt.expDir))
