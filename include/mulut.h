@@ -98,6 +98,13 @@ int mulut_configure(mulut_ctx *ctx, int stages, const char *modes, int scale, in
  * are uploaded (no tube bands, slabs or 16-bit images are built). */
 int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows, int64_t rows, int vnum);
 
+/* One of the device images a table is kept as (for tests and tools, in the spirit of mulut_last_detail_counters; the reference has
+ * no counterpart -- its tables are the arrays of :322-333 and nothing else): which = 0 the full-table image, 1 the tube band, 2 the
+ * anchor slab pairs.  Synchronises `stream`, copies min(cap, size) bytes to host_out and returns the image's size in bytes -- 0
+ * where the slot holds no such image (no table set; no band for e / h / o tables and at intervals 5 / 6; slab pairs only for
+ * vnum 16) -- or a negative MULUT_E* code.  Not on any hot path. */
+long long mulut_read_table_image(mulut_ctx *ctx, int stage, char mode, int which, void *host_out, long long cap, void *stream);
+
 /* One (table, mode, rotation) pass: replaces FourSimplexInterpFaster(weight, img_in, h, w,
  * interval, rot=4-r, upscale, mode) (sr/4_test_lut.py:14-237) TOGETHER WITH the caller's
  * np.rot90(img, r) + edge pad (:294-296).  in_chw: device uint8 planar [C][H][W], un-rotated,

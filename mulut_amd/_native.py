@@ -17,7 +17,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 # every symbol include/mulut.h declares
 EXPORTS = [
     "mulut_version", "mulut_strerror", "mulut_last_hip_error", "mulut_create", "mulut_destroy",
-    "mulut_configure", "mulut_set_lut", "mulut_pass", "mulut_stage", "mulut_pipeline",
+    "mulut_configure", "mulut_set_lut", "mulut_read_table_image", "mulut_pass", "mulut_stage", "mulut_pipeline",
     "mulut_pipeline_rows", "mulut_halo", "mulut_reserve", "mulut_set_stage_timing", "mulut_last_stage_ms", "mulut_last_kernel_ms",
     "mulut_set_tuning", "mulut_kernel_name", "mulut_ft_stage_forward", "mulut_ft_stage_backward", "mulut_ft_quantize", "mulut_ft_quantize_backward",
     "mulut_ft_stage_forward_mask", "mulut_ft_stage_backward_mask", "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward",
@@ -153,6 +153,8 @@ def load(path=None):
     L.mulut_destroy.argtypes = [p]
     L.mulut_configure.argtypes = [p, i, c_char_p, i, i]
     L.mulut_set_lut.argtypes = [p, i, ctypes.c_char, p, i64, i]
+    L.mulut_read_table_image.argtypes = [p, i, ctypes.c_char, i, p, ctypes.c_longlong, p]
+    L.mulut_read_table_image.restype = ctypes.c_longlong
     L.mulut_pass.argtypes = [p, i, ctypes.c_char, i, p, i, i, i, p, p]
     L.mulut_stage.argtypes = [p, i, p, i, p, i, i, i, i, i, p]
     L.mulut_pipeline.argtypes = [p, p, p, i, i, i, i, i, p]

@@ -385,6 +385,20 @@ int mulut_set_lut(mulut_ctx *ctx, int stage, char mode, const int8_t *host_rows,
     return band && u == 4 ? t.slab.upload(ctx, slab_pairs(img)) : t.slab.release(ctx);
 }
 
+long long mulut_read_table_image(mulut_ctx *ctx, int stage, char mode, int which, void *host_out, long long cap, void *stream) {
+    if (!ctx || cap < 0 || (cap > 0 && !host_out) || which < 0 || which > 2) return MULUT_EINVAL;
+    if (stage < 1 || stage > MULUT_MAX_STAGES) return MULUT_EINVAL;
+    const int pid = pattern_id(mode);
+    if (pid < 0) return MULUT_EMODE;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const DevTable &t = ctx->tab[stage - 1][pid];
+    const DevBuf<uint8_t> &img = which == 0 ? t.dev : which == 1 ? t.tube : t.slab;
+    HIP_TRY(ctx, hipStreamSynchronize((hipStream_t)stream));
+    const long long size = img ? (long long)img.cap : 0, n = size < cap ? size : cap;
+    if (n > 0) HIP_TRY(ctx, hipMemcpy(host_out, img.p, (size_t)n, hipMemcpyDeviceToHost));
+    return size;
+}
+
 // bracket the dominant kernel of a stage with events when timing is on (mulut_last_kernel_ms)
 #define MAIN_KERNEL(ctx, stage, st, launch)                                                   \
     do {                                                                                      \

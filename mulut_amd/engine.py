@@ -93,6 +93,18 @@ class MuLUTEngine:
             self.set_lut(int(stage), mode, table)
         return self
 
+    def read_table_image(self, stage, mode, which):
+        """The bytes of one device image of a table (mulut_read_table_image; tests and tools): which = 0 the full-table image, 1 the
+        tube band, 2 the anchor slab pairs; b"" where the slot has no such image.  Waits for torch's current stream."""
+        size = self._lib.mulut_read_table_image(self._h, int(stage), mode.encode()[:1], int(which), None, 0, self._stream())
+        if size < 0:
+            self._check(int(size))
+        buf = ctypes.create_string_buffer(int(size))
+        got = self._lib.mulut_read_table_image(self._h, int(stage), mode.encode()[:1], int(which), buf, int(size), self._stream())
+        if got < 0:
+            self._check(int(got))
+        return buf.raw[:int(got)]
+
     def load_luts(self, exp_dir, lut_name="LUT_ft"):
         """The LUT-loading block of sr/4_test_lut.py:322-333."""
         return self.set_lut_dict(load_lut_dict(exp_dir, self.stages, self.modes, self.scale, self.interval, lut_name))

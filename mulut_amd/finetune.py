@@ -120,6 +120,15 @@ class MuLUT(nn.Module):
             raise NotImplementedError("mulut_amd.finetune.MuLUT: fine-tuning is interval-4 only (got interval {}); "
                                       "intervals 5 and 6 are mulut_amd.finetune.MuLUTInterval".format(interval))
 
+    def install_into(self, engine):
+        """The current parameters into a MuLUTEngine of the same configuration, as the tables export_int8() writes into the
+        LUT_ft files (sr/3_finetune_lut.py:162-169): the engine then runs the cascade users deploy on what the module holds now."""
+        mine = (self.stages, self.modes, self.upscale, self.interval)
+        theirs = (engine.stages, engine.modes, engine.scale, engine.interval)
+        if mine != theirs:
+            raise ValueError("engine configured as (stages, modes, scale, interval) = {}, module is {}".format(theirs, mine))
+        return engine.set_lut_dict(self.export_int8())
+
     def export_int8(self):
         """{ 's{stage}_{mode}': int8 table } as sr/3_finetune_lut.py:162-169 writes LUT_ft_*.npy."""
         out = {}

@@ -19,6 +19,11 @@ bit, as ``CropProvider`` (the reference's host path, kept as ``--hostData`` and 
 gives for the same ``--seed``.  The loop does not wait for the device per step: losses go into a device vector that is read every
 ``--displayStep`` iterations, so the logged ``rT`` is WALL time per iteration between two display points (data, step and the read-back
 included), not the reference's host-side time of the step alone.
+
+``--valEngine`` also scores the tables on the path users deploy: at every validation point, and once after the last iteration, the
+current parameters are installed into one ``MuLUTEngine`` (``MuLUT.install_into``: quantised as they will be exported) and every validation image runs through ``engine.pipeline``, scored by ``mulut_eval_y`` and logged with the
+test script's line behind the iteration.  ``valid_steps`` rounds after every pass (the module's forward); the deployed cascade does not,
+which is the reference's own 30.60 against 30.61 dB on Set5 -- with the flag the deployed number is in the log while the run goes on.
 """
 import argparse
 import ctypes
@@ -170,7 +175,7 @@ def valid_steps(net, opt, it, log=print):
     import ctypes
     from . import _native
     lib = _native.load()
-    datasets = ['Set5', 'Set14'] if opt.debug else ['Set5', 'Set14', 'B100', 'Urban100', 'Manga109']
+    datasets = _val_datasets(opt)
     was_training = net.training
     net.eval()
     results = {}
@@ -212,6 +217,37 @@ def valid_steps(net, opt, it, log=print):
     return results
 
 
+def _val_datasets(opt):
+    return ['Set5', 'Set14'] if opt.debug else ['Set5', 'Set14', 'B100', 'Urban100', 'Manga109']
+
+
+def engine_valid_steps(net, engine, opt, it, log=print):
+    """The validation sets on the deployed path: the module's current parameters installed into `engine` (install_into), then sr/4_test_lut.py's loop per dataset (:257-317: LR through the cascade, ground truth
+    modcropped, grey replicated, Y-PSNR / SSIM) with the test script's summary line behind the iteration.  Returns
+    {dataset: float64 array [images, 2]} -- what ``mulut_amd.test_lut`` with device metrics returns for the tables exported now."""
+    from .metrics import modcrop
+    net.install_into(engine)
+    results = {}
+    for ds in _val_datasets(opt):
+        hr_dir = os.path.join(opt.valDir, ds, "HR")
+        if not os.path.isdir(hr_dir):
+            continue
+        scores = []
+        for fn in sorted(os.listdir(hr_dir)):
+            im = np.array(Image.open(os.path.join(opt.valDir, ds, "LR_bicubic", "X%d" % opt.scale, fn)))
+            gt = modcrop(np.array(Image.open(os.path.join(hr_dir, fn))), opt.scale)
+            if im.ndim == 2:
+                im = np.stack([im] * 3, axis=2)
+            if gt.ndim == 2:
+                gt = np.stack([gt] * 3, axis=2)
+            out = engine.pipeline(torch.from_numpy(np.ascontiguousarray(im)).to(engine.device))
+            scores.append(engine.eval_y(torch.from_numpy(np.ascontiguousarray(gt)).to(engine.device), out, opt.scale))
+        if scores:
+            results[ds] = np.asarray(scores)
+            log('Iter {} | Dataset {} | AVG LUT PSNR: {:.2f} SSIM: {:.4f}'.format(it, ds, np.mean(results[ds][:, 0]), np.mean(results[ds][:, 1])))
+    return results
+
+
 def build_parser():
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     # the flags sr/3_finetune_lut.py reads from TrainOptions (common/option.py:15-29,160-187)
@@ -235,6 +271,9 @@ def build_parser():
     p.add_argument('--seed', type=int, default=None)
     p.add_argument('--hostData', default=False, action='store_true',
                    help='cut the batches on the host (CropProvider, the reference\'s path) instead of on the device')
+    p.add_argument('--valEngine', default=False, action='store_true',
+                   help='also score the current tables on the inference engine (the deployed path) at every validation point and '
+                        'after the last iteration')
     return p
 
 
@@ -261,6 +300,11 @@ def finetune(opt, log=print):
             data = e.host
     if getattr(opt, "valoutDir", None) is None:
         opt.valoutDir = os.path.join(opt.expDir, "val")
+    engine, engine_at = None, 0
+    if getattr(opt, "valEngine", False):      # one engine for the run: later installs rewrite its tables in place
+        from .engine import MuLUTEngine
+        engine = MuLUTEngine(next(net.parameters()).device.index).configure(opt.stages, opt.modes, opt.scale, opt.interval)
+        opt.valEngineResults = {}              # {dataset: [images, 2]} of the last engine validation, for callers
     # the loop never waits for the device per step: every loss goes into this vector, read at the display points and at the end
     loss_buf = torch.zeros(opt.totalIter, dtype=torch.float32, device="cuda")
     losses, t_mark = [], time.time()
@@ -282,8 +326,14 @@ def finetune(opt, log=print):
         if getattr(opt, "valStep", 0) and (i % opt.valStep == 0 or i == 1) and os.path.isdir(getattr(opt, "valDir", "")):   # :152-158
             t_val = time.time()
             valid_steps(net, opt, i, log)
+            if engine is not None:
+                opt.valEngineResults, engine_at = engine_valid_steps(net, engine, opt, i, log), i
             t_mark += time.time() - t_val
     losses.extend(loss_buf[len(losses):opt.totalIter].tolist())
+    if engine is not None:
+        if engine_at != opt.totalIter and os.path.isdir(getattr(opt, "valDir", "")):      # the tables as they are exported below
+            opt.valEngineResults = engine_valid_steps(net, engine, opt, opt.totalIter, log)
+        engine.close()
     if isinstance(data, DeviceCropProvider) and int(data.bad.item()):
         raise RuntimeError("mulut_ft_crop_batch refused %d samples" % int(data.bad.item()))
     for key, table in net.export_int8().items():                          # :162-169

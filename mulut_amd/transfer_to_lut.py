@@ -66,13 +66,17 @@ def transfer_one(model_G, opt, stage, mode, device=None, chunks=100):
     return np.concatenate(outputs, 0)
 
 
-def transfer(model_G, opt, device=None, save=True):
-    """All stages x modes (:80-116); returns {'s{stage}_{mode}': table} and writes the .npy files into opt.expDir."""
+def transfer(model_G, opt, device=None, save=True, engine=None):
+    """All stages x modes (:80-116); returns {'s{stage}_{mode}': table} and writes the .npy files into opt.expDir.
+    engine: a MuLUTEngine (configured for the interval) that is left holding the same tables -- ready to run without the files
+    being read back."""
     out = {}
     for s in range(opt.stages):
         for mode in opt.modes:
             results = transfer_one(model_G, opt, s + 1, mode, device)
             out["s{}_{}".format(s + 1, mode)] = results
+            if engine is not None:
+                engine.set_lut(s + 1, mode, results)
             if save:
                 lut_path = os.path.join(opt.expDir, lut_file_name(opt, s + 1, mode))
                 np.save(lut_path, results)

@@ -8,6 +8,8 @@
                                                   its include/mulut.h is found beside it)
   tools/host_abi.py trace OUTDIR [--csrc DIR]     build, run, print the trace (tests/golden/host_abi_trace.txt is this output for
                                                   the parent of the commit that last touched it)
+  --driver abi_tables_host                        the same build around tests/host_emul/abi_tables_host.cpp, the driver of
+                                                  mulut_read_table_image (its trace: tests/golden/host_tables_trace.txt)
 
 The program is stand-alone (its own main, no LD_PRELOAD, nothing loaded into python): AddressSanitizer and
 UndefinedBehaviorSanitizer watch the host code while it runs, LeakSanitizer reports at exit what was never freed.
@@ -23,7 +25,7 @@ EMUL = os.path.join(ROOT, "tests", "host_emul")
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
 
 
-def build(outdir, csrc):
+def build(outdir, csrc, driver="abi_host"):
     from mulut_amd import _native
     hipcc = _native._hipcc()
     outdir = os.path.abspath(outdir)
@@ -34,12 +36,12 @@ def build(outdir, csrc):
     jobs = [(s, subprocess.Popen(host + ["-c", "-o", os.path.join(outdir, s[:-4] + ".o"), s], cwd=csrc)) for s in _native.SOURCES]
     # (the two files of the harness always compile against THIS tree's include/mulut.h, whatever --csrc names: comparing two trees
     # this way presumes that the ABI header did not change between them)
-    for s in ("fake_hip.cpp", "abi_host.cpp"):
+    for s in ("fake_hip.cpp", driver + ".cpp"):
         jobs.append((s, subprocess.Popen(host + ["-x", "hip", "-c", "-o", os.path.join(outdir, s[:-4] + ".o"), os.path.join(EMUL, s)])))
     bad = [s for s, p in jobs if p.wait() != 0]
     if bad:
         sys.exit("failed to compile: %s" % " ".join(bad))
-    exe = os.path.join(outdir, "abi_host")
+    exe = os.path.join(outdir, driver)
     objs = [os.path.join(outdir, s.rsplit(".", 1)[0] + ".o") for s, _ in jobs]
     clang = os.path.join(subprocess.check_output([os.path.join(os.path.dirname(hipcc), "hipconfig"), "-l"], text=True).strip(), "clang++")
     # (the per-file __hip_fatbin_* symbols of a host-only compile stay undefined: nothing reads them here)
@@ -57,8 +59,9 @@ if __name__ == "__main__":
     ap.add_argument("cmd", choices=["build", "trace"])
     ap.add_argument("outdir")
     ap.add_argument("--csrc", default=os.path.join(ROOT, "mulut_amd", "csrc"))
+    ap.add_argument("--driver", default="abi_host", choices=["abi_host", "abi_tables_host"])
     args = ap.parse_args()
-    exe = build(args.outdir, args.csrc)
+    exe = build(args.outdir, args.csrc, args.driver)
     if args.cmd == "trace":
         r = run(exe)
         sys.stderr.write(r.stderr)
