@@ -586,7 +586,68 @@ constexpr int kTube3SlotBytes = 24;
 constexpr int kTube3BandBytes = ((kTubeSlots * kTube3SlotBytes + 15) / 16) * 16;      // 24992
 MULUT_HD constexpr int tube3_field(int q) { return q <= 4 ? q : q + 1; }               // field of block element q (the centre's second copy is field 5)
 MULUT_HD uint32_t pixel_code1(uint32_t v) { return ((v & 15u) << 12) | (v >> 4); }
-MULUT_HD uint32_t tube1_key(uint32_t code_pk, uint32_t stride4) { return (code_pk & 0xF000F000u) | pk_dup(stride4); }
+// sort key pair = f << 12 | stride per half.  The C expression costs the device two instructions per key (a gfx9 VOP3 instruction reads one
+// scalar or literal operand, and mask and stride are two): there it is ONE full-rate v_bitop3_b32, (code & mask) | stride = truth table 0xEA,
+// with the mask in a VGPR the compiler is free to hoist (no volatile: pinned per call it is re-made per call) and the stride as the scalar operand.
+MULUT_HD uint32_t tube1_key(uint32_t code_pk, uint32_t stride4) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xea" : "=v"(r) : "v"(code_pk), "v"(0xF000F000u), "s"(pk_dup(stride4)));
+    return r;
+#else
+    return (code_pk & 0xF000F000u) | pk_dup(stride4);
+#endif
+}
+
+// ---- the 5 x 5 neighbourhood test of the 1-byte-row kernels, on one-hot MSB masks ---------------------------------------------
+// A neighbourhood spans more than one MSB step  <=>  the OR of its pixels' one-hot masks 1 << h has a set bit above (lowest set bit) << 1.
+// One-hot masks of a code pair (code1 = f << 12 | h per half): a 16-bit shift uses bits 3:0 of its count only, so on the device the code
+// pair itself is the count of one v_pk_lshlrev_b16 of 0x00010001 -- f is not masked off (asm: from C the compiler inserts the and).
+MULUT_HD uint32_t tube1_onehot(uint32_t code_pk) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_pk_lshlrev_b16 %0, %1, %2" : "=v"(r) : "v"(code_pk), "s"(0x00010001u));
+    return r;
+#else
+    return (1u << (code_pk & 15u)) | (0x10000u << ((code_pk >> 16) & 15u));
+#endif
+}
+// (hi : lo) >> 16: the high half of `lo` beside the low half of `hi` (v_alignbit_b32)
+MULUT_HD uint32_t pk_cross(uint32_t hi, uint32_t lo) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, 16);
+#else
+    return (lo >> 16) | (hi << 16);
+#endif
+}
+// per half of a pair of union masks T (non-zero): 1 if the set bits span more than one step, else 0.  low = T & -T; low * 3 = the lowest
+// bit and the one above it (truncated to the half: for h = 15 it is the lowest bit alone, and nothing lies above it); what T holds
+// beyond those is the verdict, brought to 0 / 1 by a packed min (asm: from C the compiler makes compare + select of it, v_cndmask_b32
+// issues at a quarter of the rate)
+MULUT_HD uint32_t tube1_span_gt1(uint32_t T) {
+    const uint32_t low = T & pk_sub(0u, T);
+    const uint32_t rest = T & ~pk_mad(low, pk_dup(3u), 0u);
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(rest), "s"(0x00010001u));
+    return r;
+#else
+    return pk_min(rest, 0x00010001u);
+#endif
+}
+// win = the 5 x 8 window of a thread's four pixels (rows x four dwords of two code1 columns each; pixel i sits at column i + 2).
+// Bit i of the result is set <=> the 5 x 5 neighbourhood of pixel i spans more than one MSB step.  Five rows ORed per column dword
+// first; pixels 0 / 1 (columns 0-4 / 1-5) in the low / high half of one dword, pixels 2 / 3 (columns 2-6 / 3-7) of another.
+MULUT_HD uint32_t tube1_dirty4(const uint32_t (&win)[5][4]) {
+    uint32_t c[4];
+    for (int d = 0; d < 4; ++d)
+        c[d] = (tube1_onehot(win[0][d]) | tube1_onehot(win[1][d]) | tube1_onehot(win[2][d])) | tube1_onehot(win[3][d]) | tube1_onehot(win[4][d]);
+    // low half: both columns of dwords 0, 1 and the even column of dword 2; high half: the odd column of dword 0 and both of 1, 2
+    const uint32_t t01 = (c[1] | pk_cross(c[1], c[1]) | c[0]) | c[2] | pk_cross(c[2], c[0]);
+    const uint32_t t23 = (c[2] | pk_cross(c[2], c[2]) | c[1]) | c[3] | pk_cross(c[3], c[1]);
+    const uint32_t v = tube1_span_gt1(t01) | (tube1_span_gt1(t23) << 2);      // bits 0, 16 | 2, 18
+    return (v | (v >> 15)) & 0xFu;
+}
 // SLOT = bytes per slot: 4 for 1-byte rows (one dword per slot), 8 for u == 2 rows (four 16-bit fields per slot) -- a stride then fits
 // the low BYTE of a key -- and 24 for u == 3 rows, whose strides (<= 24 * 27) take the twelve bits under f
 template <int SLOT>

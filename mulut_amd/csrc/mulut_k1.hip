@@ -476,31 +476,10 @@ __device__ __forceinline__ uint32_t u1t_pixel(const StageArgs &a, uint32_t pats_
 }
 
 // bit i set <=> the 5 x 5 neighbourhood of the thread's pixel i spans more than one MSB step (then some pass of the
-// site may leave the tube).  Column maxima / minima over the five rows first, then five adjacent columns per pixel,
-// two pixels at a time in packed halves.
-__device__ __forceinline__ uint32_t u1t_dirty(const uint32_t (&win)[5][4]) {
-    uint32_t cx[4], cn[4], mx[4], mn[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        uint32_t hi = win[0][d] & 0x000F000Fu, lo = hi;
-#pragma unroll
-        for (int q = 1; q < 5; ++q) {
-            const uint32_t h = win[q][d] & 0x000F000Fu;
-            hi = pk_max(hi, h);
-            lo = pk_min(lo, h);
-        }
-        cx[d] = hi; cn[d] = lo;
-        mx[d] = pk_max(hi, __builtin_amdgcn_alignbit(hi, hi, 16));    // both halves: max of the dword's two columns
-        mn[d] = pk_min(lo, __builtin_amdgcn_alignbit(lo, lo, 16));
-    }
-    // pixel 0: columns 0-4, pixel 1: columns 1-5 (low / high half); pixels 2, 3: columns 2-6, 3-7
-    const uint32_t x01 = pk_max(pk_max((mx[0] & 0xFFFFu) | (cx[0] & 0xFFFF0000u), mx[1]), (cx[2] & 0xFFFFu) | (mx[2] & 0xFFFF0000u));
-    const uint32_t n01 = pk_min(pk_min((mn[0] & 0xFFFFu) | (cn[0] & 0xFFFF0000u), mn[1]), (cn[2] & 0xFFFFu) | (mn[2] & 0xFFFF0000u));
-    const uint32_t x23 = pk_max(pk_max((mx[1] & 0xFFFFu) | (cx[1] & 0xFFFF0000u), mx[2]), (cx[3] & 0xFFFFu) | (mx[3] & 0xFFFF0000u));
-    const uint32_t n23 = pk_min(pk_min((mn[1] & 0xFFFFu) | (cn[1] & 0xFFFF0000u), mn[2]), (cn[3] & 0xFFFFu) | (mn[3] & 0xFFFF0000u));
-    const uint32_t d01 = (x01 - n01) & 0xFFFEFFFEu, d23 = (x23 - n23) & 0xFFFEFFFEu;     // spread of the MSBs > 1
-    return ((d01 & 0xFFFFu) ? 1u : 0u) | ((d01 >> 16) ? 2u : 0u) | ((d23 & 0xFFFFu) ? 4u : 0u) | ((d23 >> 16) ? 8u : 0u);
-}
+// site may leave the tube).  On one-hot MSB masks (mulut_core.h: tube1_dirty4, which tests/host_emul runs on the CPU): one packed shift
+// per window dword, the five rows ORed per column dword, the verdict from the union's lowest set bit -- no masking of the LSB nibbles,
+// no packed min / max over the window, no select.
+__device__ __forceinline__ uint32_t u1t_dirty(const uint32_t (&win)[5][4]) { return tube1_dirty4(win); }
 
 // (b, 0) pairs of bytes -> code1 pairs: b * 0x1001 = f << 12 | b per 16-bit lane; >> 4 moves the MSB nibble to bits 0-3
 // and the LSB nibble to bits 8-11, where the mask drops it:  f << 12 | h
