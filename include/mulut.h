@@ -269,6 +269,37 @@ long long mulut_eval_ws_doubles(int H, int W);
 int mulut_eval_y(int device, const void *gt_hwc, const void *out_hwc, int H, int W, int shave, double *ws, long long ws_doubles,
                  double *psnr, double *ssim, void *stream);
 
+/* ---- LR images made on the device (not on the inference path) ------------------------------------------------
+ * Pillow's bicubic resampling of 8-bit images, byte for byte: what sr/Test_dataset.py:24-25 does with
+ *   img.resize((img.width // scale, img.height // scale), resample=Image.BICUBIC)
+ * to make LR/X{scale}/ from HR/, and the same filter run the other way (bicubic upscaling, the baseline column of an SR table).
+ * Pillow works in fixed point: per output position normalised double coefficients rounded to integers at 22 fractional bits,
+ * an integer accumulator that starts at 1 << 21, clip(acc >> 22) to 0..255; a horizontal pass into uint8, then a vertical pass
+ * over those bytes; an axis whose size does not change is skipped.  int32 accumulators are exact here.
+ *
+ * mulut_resample_coeffs (sr/Test_dataset.py:24-25; host only, needs no device): the tables of ONE axis, in -> out samples.
+ *   kk [out][taps] int32 (zero beyond a row's n), xmin [out], n [out]: output xx = sum over t < n[xx] of kk[xx][t] * in[xmin[xx] + t];
+ *   every tap lies in [0, in).  Returns taps = 2 * ceil(2 * max(in / out, 1)) + 1, or a negative code: a NULL pointer or in, out < 1
+ *   MULUT_EINVAL; a ratio whose taps do not fit (support above 2^20) MULUT_EUNSUPPORTED; cap < out * taps int32s at kk MULUT_EWORKSPACE.
+ * mulut_resample_plan_create (sr/Test_dataset.py:24-25): builds both axes' tables for in_h x in_w -> out_h x out_w and uploads them
+ *   to `device` (one allocation, one blocking copy: not capturable).  A NULL `plan` or a size below 1 MULUT_EINVAL; a plane of 2^31
+ *   bytes or more, tables of 2^28 entries or more, or a tile whose coefficient rows and input rows do not fit 64 KiB of LDS
+ *   (1 KiB per horizontal tap + 256 bytes per input row under a tile of 16 output rows, 64 where the image grows downwards:
+ *   shrinking an axis by more than about 12)
+ *   MULUT_EUNSUPPORTED -- all before the device is touched.  *plan is NULL after any failure.
+ * mulut_resample_plan_destroy: frees the tables (hipFree waits for work in flight on the device) and the plan.
+ * mulut_resample_run (sr/Test_dataset.py:24-25): N images of C independent channels, `in` and `out` caller-owned device uint8 in
+ *   MULUT_LAYOUT_HWC or MULUT_LAYOUT_CHW, each its own; no alignment needed; nothing outside out[0, N * out_h * out_w * C) is written.
+ *   One kernel launch on `stream`; allocates nothing and waits for nothing, so it can be captured into a hipGraph.  NULL plan, in or
+ *   out, N < 1, C < 1 or an unknown layout MULUT_EINVAL; a packed image of 2^31 bytes or more, or 2^31 workgroups or more in the
+ *   call, MULUT_EUNSUPPORTED -- before the device is touched. */
+typedef struct mulut_resample_plan mulut_resample_plan;
+int mulut_resample_coeffs(int in, int out, int32_t *kk, int32_t *xmin, int32_t *n, long long cap);
+int mulut_resample_plan_create(int device, int in_h, int in_w, int out_h, int out_w, mulut_resample_plan **plan);
+int mulut_resample_plan_destroy(mulut_resample_plan *plan);
+int mulut_resample_run(const mulut_resample_plan *plan, const uint8_t *in, int in_layout, uint8_t *out, int out_layout, int N, int C,
+                       void *stream);
+
 /* Tuning knobs (never change results).
  * "final_stage_kernel" (scale 4, <= 3 modes): 0 = auto (= 6), 1 = full-table gather kernel, 5 = tube kernel on every tile (the tube
  *   bands of all modes resident in LDS; samples with a pass outside the tube are recomputed from the full table through a device

@@ -20,6 +20,10 @@ gives for the same ``--seed``.  The loop does not wait for the device per step: 
 ``--displayStep`` iterations, so the logged ``rT`` is WALL time per iteration between two display points (data, step and the read-back
 included), not the reference's host-side time of the step alone.
 
+``--makeLR``: an HR file without an LR twin on disk gets one made on the GPU at load time -- Pillow's bicubic resize to
+``(w // scale, h // scale)``, byte for byte what sr/Test_dataset.py:24-25 writes (``mulut_amd.resample``).  ``DeviceCropProvider`` has the
+kernel write it from the pair's HR slot of the pool straight into its LR slot; ``CropProvider`` copies it back to the host.
+
 ``--valEngine`` also scores the tables on the path users deploy: at every validation point, and once after the last iteration, the
 current parameters are installed into one ``MuLUTEngine`` (``MuLUT.install_into``: quantised as they will be exported) and every validation image runs through ``engine.pipeline``, scored by ``mulut_eval_y`` and logged with the
 test script's line behind the iteration.  ``valid_steps`` rounds after every pass (the module's forward); the deployed cascade does not,
@@ -40,10 +44,18 @@ from PIL import Image
 from .finetune import MuLUT, MuLUTInterval, MuLUTWide
 
 
+class _PendingLR:
+    """An LR image that DeviceCropProvider will have the resample kernel write straight into its pool slot: only its shape."""
+    dtype = np.dtype(np.uint8)
+
+    def __init__(self, shape):
+        self.shape, self.size = tuple(shape), int(np.prod(shape))
+
+
 class CropProvider:
     """Random (LR crop, HR crop) batches, one colour channel each, flips + rot90 as sr/data.py:96-124."""
 
-    def __init__(self, path, scale, patch, batch, seed=None):
+    def __init__(self, path, scale, patch, batch, seed=None, make_lr=False, log=print, _defer=False):
         self.scale, self.sz, self.batch = scale, patch, batch
         self.rng = random.Random(seed)
         hr_dir = os.path.join(path, "HR")
@@ -60,8 +72,33 @@ class CropProvider:
                     if min(lr_im.shape[:2]) >= patch:
                         self.pairs.append((lr_im, hr_im))
                     break
+            else:
+                if make_lr:      # no LR twin on disk: the (w // s, h // s) bicubic image of sr/Test_dataset.py:24-25, no modcrop
+                    self._make_pair(Image.open(os.path.join(hr_dir, fn)), fn, patch, log, _defer)
         if not self.pairs:
             raise FileNotFoundError("no HR/LR training pairs with LR >= %d px under %s" % (patch, path))
+
+    def _make_pair(self, img, fn, patch, log, defer):
+        from .resample import bicubic, resize_image
+        s = self.scale
+        h, w = img.height // s, img.width // s
+        if min(h, w) < max(patch, 1):
+            return
+        hr_im = np.array(img)
+        if img.mode in ("L", "RGB"):
+            if hr_im.ndim == 2:
+                hr_im = hr_im[:, :, None]
+            lr_im = _PendingLR((h, w, hr_im.shape[2])) if defer else bicubic(hr_im, (h, w))
+        else:                                  # Pillow on the host, one log line
+            lr_im = np.array(resize_image(img, (w, h), log, fn))
+            if hr_im.ndim == 2:
+                hr_im, lr_im = hr_im[:, :, None], lr_im[:, :, None]
+        self.pairs.append((lr_im, hr_im))
+
+    def materialise(self):
+        """Make the LR images a deferring scan left pending (on the device, copied back)."""
+        from .resample import bicubic
+        self.pairs = [(bicubic(hr_im, lr_im.shape[:2]) if isinstance(lr_im, _PendingLR) else lr_im, hr_im) for lr_im, hr_im in self.pairs]
 
     def next(self):
         ims, lbs = [], []
@@ -100,8 +137,8 @@ class DeviceCropProvider:
     behind its copy, is waited for before the slot is rewritten."""
     RING = 32
 
-    def __init__(self, path, scale, patch, batch, seed=None, max_bytes=None):
-        host = CropProvider(path, scale, patch, batch, seed)      # the same scan: the same pairs in the same order
+    def __init__(self, path, scale, patch, batch, seed=None, max_bytes=None, make_lr=False, log=print):
+        host = CropProvider(path, scale, patch, batch, seed, make_lr, log, _defer=True)      # the same scan: the same pairs in the same order
         self.scale, self.sz, self.batch = scale, patch, batch
         self.rng = host.rng
         table, off = np.zeros((len(host.pairs), 10), np.int32), 0
@@ -114,14 +151,20 @@ class DeviceCropProvider:
             off += lr_im.size + hr_im.size
         self.pool_bytes = off
         if max_bytes is not None and off > max_bytes:
+            host.materialise()
             raise TrainingSetTooLarge(off, max_bytes, host)
         self.shapes = [im.shape for im, _ in host.pairs]           # (lr_h, lr_w, ch) per pair: all the draws need
         self.device = torch.empty(0).cuda().device
         self.pool = torch.empty(off, dtype=torch.uint8, device=self.device)
         for n, (lr_im, hr_im) in enumerate(host.pairs):            # image by image: no second copy of the set on the host
             a = int(t64[n, 0])
-            self.pool[a:a + lr_im.size].copy_(torch.from_numpy(np.ascontiguousarray(lr_im).reshape(-1)))
-            self.pool[a + lr_im.size:a + lr_im.size + hr_im.size].copy_(torch.from_numpy(np.ascontiguousarray(hr_im).reshape(-1)))
+            hr_slot = self.pool[a + lr_im.size:a + lr_im.size + hr_im.size]
+            hr_slot.copy_(torch.from_numpy(np.ascontiguousarray(hr_im).reshape(-1)))
+            if isinstance(lr_im, _PendingLR):                      # --makeLR: the kernel writes the pair's LR slot from its HR slot
+                from .resample import bicubic
+                bicubic(hr_slot.view(hr_im.shape), lr_im.shape[:2], out=self.pool[a:a + lr_im.size])
+            else:
+                self.pool[a:a + lr_im.size].copy_(torch.from_numpy(np.ascontiguousarray(lr_im).reshape(-1)))
         self.table = torch.from_numpy(table).cuda()
         self.bad = torch.zeros(1, dtype=torch.int32).cuda()         # samples the kernel refused: stays 0 (the draws are legal by construction)
         if self.pool.is_cuda:
@@ -271,6 +314,9 @@ def build_parser():
     p.add_argument('--seed', type=int, default=None)
     p.add_argument('--hostData', default=False, action='store_true',
                    help='cut the batches on the host (CropProvider, the reference\'s path) instead of on the device')
+    p.add_argument('--makeLR', default=False, action='store_true',
+                   help='an HR image without an LR twin on disk gets one made on the GPU at load time: Pillow\'s bicubic resize to '
+                        '(w // scale, h // scale), the bytes sr/Test_dataset.py writes')
     p.add_argument('--valEngine', default=False, action='store_true',
                    help='also score the current tables on the inference engine (the deployed path) at every validation point and '
                         'after the last iteration')
@@ -290,11 +336,13 @@ def finetune(opt, log=print):
         lr_a = 1 - lr_b
         lf = lambda x: (((1 + math.cos(x * math.pi / opt.totalIter)) / 2) ** 1.0) * lr_a + lr_b   # noqa: E731
     sched = torch.optim.lr_scheduler.LambdaLR(optim, lr_lambda=lf)
+    make_lr = getattr(opt, "makeLR", False)
     if getattr(opt, "hostData", False):
-        data = CropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed)
+        data = CropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, make_lr, log)
     else:
         try:      # the set stays on the device for the whole run: at most half of what is free now
-            data = DeviceCropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, max_bytes=torch.cuda.mem_get_info()[0] // 2)
+            data = DeviceCropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, max_bytes=torch.cuda.mem_get_info()[0] // 2,
+                                      make_lr=make_lr, log=log)
         except TrainingSetTooLarge as e:
             log("{} | training set of {} bytes exceeds half the free device memory ({}): batches are cut on the host".format(opt.expDir, e.nbytes, e.limit))
             data = e.host

@@ -3,7 +3,9 @@
 Deviations, both documented in DESIGN.md:
   * ``parse()`` does not copy every ``*.py`` under cwd into ``<expDir>/code`` (common/option.py:104-110,155-156);
     pass ``--saveCode`` to get that side effect back.  ``--debug`` is accepted and means what it meant.
-  * new optional flags (``--device``, ``--datasets``, ``--batch``, ``--ioWorkers``, ``--timing``) default to the reference's behaviour.
+  * new optional flags (``--device``, ``--datasets``, ``--batch``, ``--ioWorkers``, ``--timing``, ``--bicubicBaseline``) default to the reference's behaviour.
+    ``--bicubicBaseline`` takes effect here: ``parse()`` has ``mulut_amd.resample.add_baseline_line`` wrap the test script's
+    ``eltr.run``, which then prints one more line per dataset behind the summary; ``mulut_amd/test_lut.py`` itself is as it was.
 """
 import argparse
 import os
@@ -42,6 +44,9 @@ class TestOptions:
         parser.add_argument('--ioWorkers', type=int, default=4,
                             help='PNG decode threads ahead of the GPU and encode / score threads behind it (1 = strictly serial)')
         parser.add_argument('--timing', action='store_true', default=False, help='also print end-to-end images/s per dataset')
+        parser.add_argument('--bicubicBaseline', action='store_true', default=False,
+                            help="after each dataset's summary, also print the PSNR / SSIM of the LR images upscaled by Pillow's "
+                                 "bicubic filter on the GPU (the baseline column of an SR table)")
         parser.add_argument('--saveCode', action='store_true', default=False,
                             help="copy *.py under cwd into <expDir>/code like the reference's parse()")
         return parser
@@ -70,5 +75,15 @@ class TestOptions:
                 trg = os.path.join(opt.expDir, "code", f)
                 os.makedirs(os.path.dirname(trg), exist_ok=True)
                 shutil.copy(f, trg, follow_symlinks=False)
+        if opt.bicubicBaseline:
+            # the test script's evaluator, under the name it was started by (python -m mulut_amd.test_lut runs it as __main__)
+            import sys
+            from .resample import add_baseline_line
+            main_mod = sys.modules.get("__main__")
+            if getattr(getattr(main_mod, "__spec__", None), "name", None) == "mulut_amd.test_lut":
+                add_baseline_line(main_mod.eltr)
+            else:
+                from . import test_lut
+                add_baseline_line(test_lut.eltr)
         self.opt = opt
         return opt
