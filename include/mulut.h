@@ -192,7 +192,29 @@ int mulut_debug_read(mulut_ctx *ctx, unsigned long long *out, int cap, int reset
  *   x         : device float32 [B][C][H][W] in 0..255 (the module multiplies its input by 255, :290)
  *   out       : device float32 [B][C][H*u][W*u] in 0..255
  * backward: grad_out = dL/d out; accumulates dL/d weights_q into grad_wq[m] (atomic adds; zero them first) and
- * dL/dx into grad_x (zero it first).  u = upscale for the last stage, else 1. */
+ * dL/dx into grad_x (zero it first).  u = upscale for the last stage, else 1.
+ * Contracts of every call of this section (the quantiser pair, the four families of stage calls; tests/test_gpu_ft_abi.py):
+ *   - stateless and stream-ordered: a call is one kernel launch on `stream`; it allocates nothing, waits for nothing and keeps no
+ *     state that affects a result (what it keeps is set-up done once: see the capture note), so it reads what work queued earlier on
+ *     that stream wrote and may be queued behind its producer.
+ *   - "accumulates" means ADDS: after the call every element of grad_wq[m] and grad_x holds what it held before plus this call's
+ *     gradient -- elements the batch does not touch are not written at all -- so gradients of several micro-batches may be summed
+ *     by calling again without zeroing ("zero them first" is for the caller who wants one call's gradient).  The adds are float32
+ *     atomics in no fixed order: bit-reproducible only where the sums are exact.
+ *   - alignment: float alignment (4 bytes) suffices for x, out, grad_out, grad_x and every table and gradient pointer, 2 bytes for
+ *     `inside`; tables of one stage may lie back to back (rows * u*u floats apart).  Nothing outside x, weights_q[m], grad_out and
+ *     `inside` is read, nothing outside out, `inside` (forward), grad_wq[m] and grad_x is written.
+ *   - x outside 0..255 (below 0, above 255, infinite, NaN of either sign, denormal): defined, and inside the tables, forward and
+ *     backward.  The MSB of every key is clamped into 0 .. L-2.  At interval 4 the keys are ranked on |LSB|, which makes the five rows
+ *     of a pass the anchor row plus each key's stride once for any four floats: rows stay in [0, 83521), tube slots in [0, 1041).  At
+ *     intervals 5 and 6 every row is clamped into [0, L^4) as well.  The LSB stays x - q*floor(x/q), so such a pixel gives the sites
+ *     that read it a meaningless (for an infinity or NaN: NaN) output and gradient -- a NaN weight is added to the in-table rows of
+ *     that pass -- and no other site anything else than it would get otherwise.  The reference raises an index error there.
+ *   - hipGraph capture: run the call once outside capture first.  The first launch of a kernel that takes dynamic LDS raises that
+ *     kernel's limit (hipFuncSetAttribute): the u = 4 backward at interval 4 (the other interval-4 kernels use static LDS), every
+ *     backward and the LDS-resident forward at intervals 5 and 6; and the first interval-5 / 6 call asks for the device's CU count.
+ *     Neither is capturable; both are remembered per device.  After that warm-up a call is a kernel launch and nothing else: it can
+ *     be captured, and a replay reads x, grad_out, the tables and `inside` as they are in memory then (rewrite them in place). */
 /* The module's quantisation of its float parameters and that step's backward (sr/model.py:74-76), for the M tables of a stage
  * (n floats each) in one launch:
  *   mulut_ft_quantize          : weights_q[m][i] = clamp(round(weights[m][i] * 127), -127, 127), round = half to even (torch.round)

@@ -1,9 +1,10 @@
 // mulut_ft.h -- what the fine-tuning kernels of every sampling interval share (mulut_ft.hip: interval 4, mulut_ft_interval.hip: 5 and 6).
 //
-// First part, pure arithmetic compiled by hipcc into both files and by g++ into tests/host_emul/emul_ft_interval.cpp (a CPU unit
-// test, not a product path): the order of the four keys of a pass, their sorted LSBs and the five weights (the reference's
+// First part, pure arithmetic compiled by hipcc into both files and by g++ into tests/host_emul/emul_ft_interval.cpp and emul_ft_clamp.cpp (CPU unit
+// tests, not a product path): the order of the four keys of a pass, their sorted LSBs and the five weights (the reference's
 // differentiable module, MuLUT.InterpTorchBatch, sr/model.py:78-121, 191-282).  The MSB / row-index part of the set-up stays per
-// family: ft_pass_setup() of mulut_ft.hip also derives tube slots and does not clamp, ft_iv_pass<IV>() of mulut_ft_interval.h clamps.
+// family: ft_pass_setup() below (interval 4) also derives tube slots, ft_iv_pass<IV>() of mulut_ft_interval.h (5 and 6) corner codes;
+// both clamp the MSB of every key into 0 .. L - 2, so no key value -- out of 0..255, infinite or NaN -- takes a pass out of its table.
 // Both files include it under `#pragma clang fp contract(off)` (the reference's float expressions are not contracted); g++ gets
 // -ffp-contract=off from the test.
 // Second part (hipcc only): the kernel argument struct with its argument checks, and the LDS float add and DPP row helpers of the
@@ -61,6 +62,73 @@ MULUT_HD void ft_weights(float q, const float (&fs)[4], float (&wt)[5]) {
     wt[2] = fs[1] - fs[2];
     wt[3] = fs[2] - fs[3];
     wt[4] = fs[3];
+}
+
+// One pass at interval 4 (q = 16, L = 17): the four keys of site (y, x) of `plane` under rotation r, their table rows, weights, tube
+// slots and rank order.  For x in 0..255 this is the reference's set-up.  For ANY float it stays inside the table and the tube band:
+//   - the MSB of every key is clamped into 0 .. L - 2 = 15 (255 has MSB 15), in float before the conversion, so a value the int
+//     cannot hold, an infinity or a NaN converts defined and alike on host and device (NaN -> 0, +inf -> 15);
+//   - the keys are ranked on |LSB|.  The LSB, v - q floor(v / q) (the reference's img % q), is >= +0 for every v in range; out of range
+//     it can carry a sign bit (a NaN of either sign, a negative denormal whose quotient underflows to -0), and ft_order_code() orders
+//     int32 patterns, which is a total order on non-negative patterns only -- with a sign bit its six comparisons can form a cycle and
+//     the code is no permutation: one key's stride added twice, a row past 83520 or a slot past 1040.  On non-negative patterns the
+//     code is always a permutation, so row 4 = row 0 + 5220 <= 83520 and slot 4 = slot 0 + 65 <= 1040.
+// Such a pixel gets a defined, meaningless weight (NaN for a NaN or an infinity), never an address.
+struct FtPass {
+    int idx[5];      // table rows of the five vertices
+    float wt[5];     // q-f1, f1-f2, f2-f3, f3-f4, f4
+    int tslot[5];    // tube-band slots of the five vertices (mulut_core.h), valid when in_tube
+    bool in_tube;    // the four MSBs span at most one step: every vertex lies in the 1041-slot tube band
+    int ord;         // key (0 = a ... 3 = d) of rank j in bits 2j, 2j + 1
+};
+
+MULUT_HD void ft_pass_setup(const float *plane, int H, int W, int y, int x, int r, const int (&di)[3], const int (&dj)[3], FtPass &p) {
+    int pix[4];
+    float v[4];
+    pix[0] = y * W + x;
+    for (int k = 0; k < 3; ++k) {
+        int dy, dx;
+        sample_offset(r, di[k], dj[k], dy, dx);
+        pix[k + 1] = imin(imax(y + dy, 0), H - 1) * W + imin(imax(x + dx, 0), W - 1);
+    }
+    int h[4];
+    float f[4];
+    for (int k = 0; k < 4; ++k) {
+        v[k] = plane[pix[k]];
+        const float hf = floorf(v[k] / (float)kQ);       // torch.floor_divide(img, q)
+        f[k] = v[k] - (float)kQ * hf;                    // img % q
+        h[k] = (int)fminf(fmaxf(hf, 0.0f), (float)(kL - 2));      // (a value outside 0..255 must not leave the table; fmaxf drops a NaN)
+    }
+    const int ord = ft_order_code(fabsf(f[0]), fabsf(f[1]), fabsf(f[2]), fabsf(f[3]));      // (a permutation for any four floats: see above)
+    p.ord = ord;
+    float fs[4];
+    ft_sort_lsb(f, fs);
+    // strides of the key of rank j: a shift of a packed constant by that key's id
+    constexpr unsigned long long kRowStrides = (unsigned long long)kStrideA | ((unsigned long long)kStrideB << 16) | ((unsigned long long)kStrideC << 32) |
+                                               ((unsigned long long)kStrideD << 48);
+    constexpr uint32_t kTubeStrides = (uint32_t)kTubeSA | ((uint32_t)kTubeSB << 8) | ((uint32_t)kTubeSC << 16) | ((uint32_t)kTubeSD << 24);
+    static_assert(kStrideA < 65536 && kTubeSA < 256 && kStrideD == 1, "packed stride constants");
+    int ss[4], ts[4];
+    for (int j = 0; j < 4; ++j) {
+        const int d = (ord >> (2 * j)) & 3;
+        ss[j] = (int)((uint32_t)(kRowStrides >> (16 * d)) & 0xFFFFu);
+        ts[j] = (int)((kTubeStrides >> (8 * d)) & 0xFFu);
+    }
+    {
+        p.tslot[0] = tube_slot(h[0], h[1], h[2], h[3]);
+        p.tslot[1] = p.tslot[0] + ts[0];
+        p.tslot[2] = p.tslot[1] + ts[1];
+        p.tslot[3] = p.tslot[2] + ts[2];
+        p.tslot[4] = p.tslot[3] + ts[3];
+        const int hx = imax(imax(h[0], h[1]), imax(h[2], h[3])), hn = imin(imin(h[0], h[1]), imin(h[2], h[3]));
+        p.in_tube = hx - hn <= 1;
+    }
+    p.idx[0] = h[0] * kStrideA + h[1] * kStrideB + h[2] * kStrideC + h[3];
+    p.idx[1] = p.idx[0] + ss[0];
+    p.idx[2] = p.idx[1] + ss[1];
+    p.idx[3] = p.idx[2] + ss[2];
+    p.idx[4] = p.idx[3] + ss[3];
+    ft_weights((float)kQ, fs, p.wt);
 }
 
 #if defined(__HIPCC__)

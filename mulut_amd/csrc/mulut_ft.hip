@@ -47,66 +47,7 @@ constexpr FtTubeRows ft_make_tube_rows() {
 }
 __device__ const FtTubeRows kFtTubeRows = ft_make_tube_rows();
 
-struct FtPass {
-    int idx[5];      // table rows of the five vertices
-    float wt[5];     // q-f1, f1-f2, f2-f3, f3-f4, f4
-    int tslot[5];    // tube-band slots of the five vertices (mulut_core.h), valid when in_tube
-    bool in_tube;    // the four MSBs span at most one step: every vertex lies in the 1041-slot tube band
-    int ord;         // key (0 = a ... 3 = d) of rank j in bits 2j, 2j + 1
-};
-
-__device__ __forceinline__ void ft_pass_setup(const float *plane, int H, int W, int y, int x, int r, const int (&di)[3],
-                                              const int (&dj)[3], FtPass &p) {
-    int pix[4];
-    float v[4];
-    pix[0] = y * W + x;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        int dy, dx;
-        sample_offset(r, di[k], dj[k], dy, dx);
-        pix[k + 1] = imin(imax(y + dy, 0), H - 1) * W + imin(imax(x + dx, 0), W - 1);
-    }
-    int h[4];
-    float f[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = plane[pix[k]];
-        const float hf = floorf(v[k] / (float)kQ);       // torch.floor_divide(img, q)
-        h[k] = (int)hf;
-        f[k] = v[k] - (float)kQ * hf;                    // img % q
-    }
-    const int ord = ft_order_code(f[0], f[1], f[2], f[3]);      // (mulut_ft.h, as the LSB sort and the weights)
-    p.ord = ord;
-    float fs[4];
-    ft_sort_lsb(f, fs);
-    // strides of the key of rank j: a shift of a packed constant by that key's id
-    constexpr unsigned long long kRowStrides = (unsigned long long)kStrideA | ((unsigned long long)kStrideB << 16) | ((unsigned long long)kStrideC << 32) |
-                                               ((unsigned long long)kStrideD << 48);
-    constexpr uint32_t kTubeStrides = (uint32_t)kTubeSA | ((uint32_t)kTubeSB << 8) | ((uint32_t)kTubeSC << 16) | ((uint32_t)kTubeSD << 24);
-    static_assert(kStrideA < 65536 && kTubeSA < 256 && kStrideD == 1, "packed stride constants");
-    int ss[4], ts[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int d = (ord >> (2 * j)) & 3;
-        ss[j] = (int)((uint32_t)(kRowStrides >> (16 * d)) & 0xFFFFu);
-        ts[j] = (int)((kTubeStrides >> (8 * d)) & 0xFFu);
-    }
-    {
-        p.tslot[0] = tube_slot(h[0], h[1], h[2], h[3]);
-        p.tslot[1] = p.tslot[0] + ts[0];
-        p.tslot[2] = p.tslot[1] + ts[1];
-        p.tslot[3] = p.tslot[2] + ts[2];
-        p.tslot[4] = p.tslot[3] + ts[3];
-        const int hx = imax(imax(h[0], h[1]), imax(h[2], h[3])), hn = imin(imin(h[0], h[1]), imin(h[2], h[3]));
-        p.in_tube = hx - hn <= 1 && hn >= 0 && hx <= 15;
-    }
-    p.idx[0] = h[0] * kStrideA + h[1] * kStrideB + h[2] * kStrideC + h[3];
-    p.idx[1] = p.idx[0] + ss[0];
-    p.idx[2] = p.idx[1] + ss[1];
-    p.idx[3] = p.idx[2] + ss[2];
-    p.idx[4] = p.idx[3] + ss[3];
-    ft_weights((float)kQ, fs, p.wt);
-}
+// (FtPass and ft_pass_setup(), the per-pass set-up of every kernel here: mulut_ft.h)
 
 // pred after all passes of the stage for one site (the order of additions and roundings is the reference's)
 template <int U>

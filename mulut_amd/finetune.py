@@ -27,6 +27,14 @@ class _StageFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, modes, is_last, u, interval, *weights):
+        # the kernels take raw pointers: a tensor of another type or on another device would be read as float32 levels at an address
+        # of this device, so it is refused here, before any library call (as MuLUTEngine._dev_u8 refuses for inference)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+            raise TypeError("x must be a float32 CUDA tensor [B, C, H, W] (got {} on {})".format(
+                getattr(x, "dtype", type(x).__name__), getattr(x, "device", "the host")))
+        for w in weights:
+            if w.device != x.device:
+                raise ValueError("a table lives on {}, x on {}".format(w.device, x.device))
         lib = _native.load()
         x = x.contiguous()
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
