@@ -222,6 +222,16 @@ int mulut_debug_read(mulut_ctx *ctx, unsigned long long *out, int cap, int reset
  *                                (the rounding is a BPDA identity, :59-67; the clamp passes gradient on its closed interval) */
 int mulut_ft_quantize(int device, const float *const *weights, float *const *weights_q, int M, long long n, void *stream);
 int mulut_ft_quantize_backward(int device, const float *const *weights, float *const *grad, int M, long long n, void *stream);
+/* One step of the fine-tune optimiser (sr/3_finetune_lut.py:86: Adam with L2 weight decay added to the gradient, no amsgrad) over T
+ * tensors of n[t] floats each in one launch (chunks of 32 tensors), in place on the current stream:
+ *   g = grads + weight_decay * params;  exp_avg += (g - exp_avg) (1 - beta1);  exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) g g;
+ *   params -= lr / (1 - beta1^step) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps)
+ * `step` is the number of this step, 1 for the first.  Everything in memory is float32; between the loads and the stores the arithmetic
+ * is float64, so each stored value is the float64 result rounded once.  A NULL pointer, T < 1, n[t] < 1, step < 1 or a beta outside
+ * [0, 1) returns MULUT_EINVAL before the device is touched.  Nothing outside the n[t] floats of each tensor is read or written. */
+int mulut_ft_adam(int device, float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                  const long long *n, int T, long long step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                  void *stream);
 int mulut_ft_stage_forward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,
                            int B, int C, int H, int W, float *out, void *stream);
 int mulut_ft_stage_backward(int device, const float *const *weights_q, const char *modes, int is_last, int u, const float *x,

@@ -19,7 +19,7 @@ EXPORTS = [
     "mulut_version", "mulut_strerror", "mulut_last_hip_error", "mulut_create", "mulut_destroy",
     "mulut_configure", "mulut_set_lut", "mulut_read_table_image", "mulut_pass", "mulut_stage", "mulut_pipeline",
     "mulut_pipeline_rows", "mulut_halo", "mulut_reserve", "mulut_set_stage_timing", "mulut_last_stage_ms", "mulut_last_kernel_ms",
-    "mulut_set_tuning", "mulut_kernel_name", "mulut_ft_stage_forward", "mulut_ft_stage_backward", "mulut_ft_quantize", "mulut_ft_quantize_backward",
+    "mulut_set_tuning", "mulut_kernel_name", "mulut_ft_stage_forward", "mulut_ft_stage_backward", "mulut_ft_quantize", "mulut_ft_quantize_backward", "mulut_ft_adam",
     "mulut_ft_stage_forward_mask", "mulut_ft_stage_backward_mask", "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward",
     "mulut_ft_wide_stage_forward", "mulut_ft_wide_stage_backward", "mulut_ft_crop_batch",
     "mulut_eval_ws_doubles", "mulut_eval_y", "mulut_last_detail_counters", "mulut_debug_read",
@@ -183,6 +183,9 @@ def load(path=None):
     L.mulut_kernel_name.restype = c_char_p
     L.mulut_ft_quantize.argtypes = [i, p, p, i, ctypes.c_longlong, p]
     L.mulut_ft_quantize_backward.argtypes = [i, p, p, i, ctypes.c_longlong, p]
+    d = ctypes.c_double
+    L.mulut_ft_adam.argtypes = [i, p, p, p, p, p, i, ctypes.c_longlong, d, d, d, d, d, p]
+    L.mulut_ft_adam.restype = i
     L.mulut_eval_ws_doubles.argtypes = [i, i]
     L.mulut_eval_ws_doubles.restype = ctypes.c_longlong
     L.mulut_eval_y.argtypes = [i, p, p, i, i, i, p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double),

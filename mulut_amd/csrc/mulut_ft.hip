@@ -531,9 +531,67 @@ __global__ void __launch_bounds__(256) ft_quantize_kernel(FtQuantArgs a) {
     else a.o[m][i] = r != r ? r : fminf(fmaxf(r, -127.0f), 127.0f);      // torch.clamp keeps NaN (fminf / fmaxf drop it): a diverged run must show
 }
 
+// The optimiser's step (sr/3_finetune_lut.py:86: Adam, L2 weight decay in the gradient, no amsgrad) over every table of a run in one
+// launch.  Parameters and moments are float32 in memory, as the reference holds them; the arithmetic between the loads and the three
+// stores is float64, so each stored value is the float64 Adam's, rounded once -- the step is bound by its seven memory streams and the
+// float64 operations cost it nothing.  The bias corrections come from the host (1 - beta^step, in double).
+constexpr int kMaxAdamTensors = 32;
+struct FtAdamArgs {
+    float *p[kMaxAdamTensors], *m[kMaxAdamTensors], *v[kMaxAdamTensors];
+    const float *g[kMaxAdamTensors];
+    long long n[kMaxAdamTensors];
+    double beta1, beta2, eps, weight_decay, step_size, bc2_sqrt;
+};
+__global__ void __launch_bounds__(256) ft_adam_kernel(FtAdamArgs a) {
+    const int t = (int)blockIdx.y;
+    const long long n = a.n[t], stride = (long long)gridDim.x * 256;
+    float *__restrict__ P = a.p[t], *__restrict__ M = a.m[t], *__restrict__ V = a.v[t];
+    const float *__restrict__ G = a.g[t];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        double p = (double)P[i], g = (double)G[i];
+        if (a.weight_decay != 0.0) g += a.weight_decay * p;
+        const double m = (double)M[i] + (g - (double)M[i]) * (1.0 - a.beta1);
+        const double v = (double)V[i] * a.beta2 + (1.0 - a.beta2) * g * g;
+        p -= a.step_size * (m / (sqrt(v) / a.bc2_sqrt + a.eps));
+        P[i] = (float)p;
+        M[i] = (float)m;
+        V[i] = (float)v;
+    }
+}
+
 }  // namespace mulut
 
 using namespace mulut;
+
+int mulut_ft_adam(int device, float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                  const long long *n, int T, long long step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                  void *stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !n || T < 1 || step < 1) return MULUT_EINVAL;
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return MULUT_EINVAL;
+    for (int t = 0; t < T; ++t)
+        if (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t] || n[t] <= 0) return MULUT_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    for (int t0 = 0; t0 < T; t0 += kMaxAdamTensors) {
+        FtAdamArgs a;
+        memset(&a, 0, sizeof(a));
+        const int cnt = T - t0 < kMaxAdamTensors ? T - t0 : kMaxAdamTensors;
+        long long most = 0;
+        for (int t = 0; t < cnt; ++t) {
+            a.p[t] = params[t0 + t];
+            a.g[t] = grads[t0 + t];
+            a.m[t] = exp_avg[t0 + t];
+            a.v[t] = exp_avg_sq[t0 + t];
+            a.n[t] = n[t0 + t];
+            most = a.n[t] > most ? a.n[t] : most;
+        }
+        a.beta1 = beta1, a.beta2 = beta2, a.eps = eps, a.weight_decay = weight_decay, a.step_size = lr / bc1, a.bc2_sqrt = sqrt(bc2);
+        long long nb = (most + 255) / 256;
+        if (nb > 4096) nb = 4096;      // grid-stride beyond that: 2^20 threads per table keep every CU busy
+        hipLaunchKernelGGL(ft_adam_kernel, dim3((unsigned)nb, (unsigned)cnt), dim3(256), 0, (hipStream_t)stream, a);
+    }
+    return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
+}
 
 static int ft_quantize(int device, const float *const *w, float *const *o, int M, long long n, bool backward, void *stream) {
     if (!w || !o || n <= 0) return MULUT_EINVAL;

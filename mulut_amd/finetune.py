@@ -175,3 +175,47 @@ class MuLUTWide(MuLUT):
     def _check_interval(interval):
         if interval not in (4, 5, 6):
             raise ValueError("mulut_amd.finetune.MuLUTWide takes interval 4, 5 or 6 (got {})".format(interval))
+
+
+class Adam(torch.optim.Optimizer):
+    """The reference's optimiser (sr/3_finetune_lut.py:86: torch.optim.Adam with L2 weight decay, no amsgrad) as one HIP launch over
+    every table of a parameter group (mulut_ft_adam): float32 parameters and moments, the step's arithmetic in float64 -- each stored
+    value is the float64 Adam's rounded once.  State as torch's: ``state[p]`` holds ``step`` (a float32 scalar on the host),
+    ``exp_avg`` and ``exp_avg_sq``; learning-rate schedulers drive ``param_groups[..]['lr']`` as they do torch's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("invalid Adam setting: lr {}, betas {}, eps {}, weight_decay {}".format(lr, betas, eps, weight_decay))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _native.load()
+        for group in self.param_groups:
+            by_step = {}      # (device, number of the step) -> parameters: one launch each (one in all for a module's tables)
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.dtype == torch.float32 and p.grad.device == p.device):
+                    raise TypeError("mulut_amd.finetune.Adam steps contiguous float32 CUDA parameters with float32 gradients on their device")
+                st = self.state[p]
+                if not st:
+                    st["step"] = torch.tensor(0.0)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["step"] += 1
+                by_step.setdefault((p.device, int(st["step"].item())), []).append(p)
+            for (device, step), ps in by_step.items():
+                grads = [p.grad.contiguous() for p in ps]
+                n = (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps])
+                rc = lib.mulut_ft_adam(device.index, _ptr_array(ps), _ptr_array(grads), _ptr_array([self.state[p]["exp_avg"] for p in ps]),
+                                       _ptr_array([self.state[p]["exp_avg_sq"] for p in ps]), n, len(ps), step, float(group["lr"]),
+                                       group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"],
+                                       ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+                if rc:
+                    raise RuntimeError(lib.mulut_strerror(rc).decode())
+        return loss

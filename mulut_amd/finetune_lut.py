@@ -27,7 +27,7 @@ kernel write it from the pair's HR slot of the pool straight into its LR slot; `
 ``--valEngine`` also scores the tables on the path users deploy: at every validation point, and once after the last iteration, the
 current parameters are installed into one ``MuLUTEngine`` (``MuLUT.install_into``: quantised as they will be exported) and every validation image runs through ``engine.pipeline``, scored by ``mulut_eval_y`` and logged with the
 test script's line behind the iteration.  ``valid_steps`` rounds after every pass (the module's forward); the deployed cascade does not,
-which is the reference's own 30.60 against 30.61 dB on Set5 -- with the flag the deployed number is in the log while the run goes on.
+which is 30.605 against 30.608 dB on Set5 for the shipped tables (both print as 30.61) -- with the flag the deployed number is in the log while the run goes on.
 """
 import argparse
 import ctypes
@@ -41,7 +41,7 @@ import torch
 import torch.nn.functional as F
 from PIL import Image
 
-from .finetune import MuLUT, MuLUTInterval, MuLUTWide
+from .finetune import Adam, MuLUT, MuLUTInterval, MuLUTWide
 
 
 class _PendingLR:
@@ -215,13 +215,13 @@ class DeviceCropProvider:
 def valid_steps(net, opt, it, log=print):
     """Twin of sr/3_finetune_lut.py:23-65: datasets under {valDir}/{dataset}/HR with LR_bicubic/X{scale}; a dataset that is
     not on disk is skipped (the reference's Provider would have failed at start-up instead)."""
-    import ctypes
     from . import _native
+    from .metrics import modcrop
     lib = _native.load()
     datasets = _val_datasets(opt)
     was_training = net.training
     net.eval()
-    results = {}
+    results, per_image = {}, {}
     with torch.no_grad():
         for ds in datasets:
             hr_dir = os.path.join(opt.valDir, ds, "HR")
@@ -233,13 +233,18 @@ def valid_steps(net, opt, it, log=print):
             for fn in sorted(os.listdir(hr_dir)):
                 lb = np.array(Image.open(os.path.join(hr_dir, fn)))
                 im = np.array(Image.open(os.path.join(opt.valDir, ds, "LR_bicubic", "X%d" % opt.scale, fn)))
-                if im.ndim == 2:                                   # grey images are replicated to three channels (sr/data.py)
-                    im, lb = np.stack([im] * 3, 2), np.stack([lb] * 3, 2)
+                lb = modcrop(lb, opt.scale)                        # sr/data.py:144: rows and columns beyond a multiple of the scale are dropped
+                if lb.ndim == 2:                                   # a grey HR and a grey LR are replicated to three channels, each on
+                    lb = np.stack([lb] * 3, 2)                     # its own (sr/data.py:145-158)
+                if im.ndim == 2:
+                    im = np.stack([im] * 3, 2)
+                if (im.shape[0] * opt.scale, im.shape[1] * opt.scale) != lb.shape[:2] or im.shape[2] != 3 or lb.shape[2] != 3:      # :163-166
+                    raise ValueError("{}/{}: LR {} x scale {} is not the modcropped HR {}".format(ds, fn, im.shape, opt.scale, lb.shape))
                 x = torch.from_numpy(np.ascontiguousarray(im.transpose(2, 0, 1)[None]).astype(np.float32) / 255.0).cuda()
                 pred = net(x) * 255.0
                 pred_u8 = torch.round(torch.clamp(pred[0].permute(1, 2, 0), 0, 255)).to(torch.uint8).contiguous()
                 H, W = pred_u8.shape[:2]
-                gt = torch.from_numpy(np.ascontiguousarray(lb[:H, :W, :3])).cuda()
+                gt = torch.from_numpy(np.ascontiguousarray(lb)).cuda()
                 n = int(lib.mulut_eval_ws_doubles(H, W))
                 ws = torch.empty(n, dtype=torch.float64, device="cuda")
                 ps, ss = ctypes.c_double(), ctypes.c_double()
@@ -255,8 +260,10 @@ def valid_steps(net, opt, it, log=print):
                 Image.fromarray(pred_u8.cpu().numpy()).save(os.path.join(out_dir, '{}_lutft.png'.format((ds + '_' + fn[:-4]).split('_')[-1])))
             if psnrs:
                 results[ds] = (float(np.mean(psnrs)), float(np.mean(ssims)))
+                per_image[ds] = np.stack([psnrs, ssims], 1)
                 log('Iter {} | Dataset {} | AVG PSNR: {:02f}, AVG: SSIM: {:04f}'.format(it, ds, results[ds][0], results[ds][1]))
     net.train(was_training)
+    opt.valResults = per_image      # {dataset: float64 array [images, 2]} of this validation, as opt.valEngineResults for the engine's
     return results
 
 
@@ -323,71 +330,94 @@ def build_parser():
     return p
 
 
-def finetune(opt, log=print):
-    wide = any(m in "eho" for m in opt.modes)      # the reference's module stops at s, d, y (sr/model.py:119-121)
-    net = (MuLUTWide if wide else MuLUTInterval if opt.interval in (5, 6) else MuLUT)(opt.expDir, opt.stages, list(opt.modes), upscale=opt.scale, interval=opt.interval).cuda()
-    params = [p for p in net.parameters() if p.requires_grad]
-    optim = torch.optim.Adam(params, lr=opt.lr0, betas=(0.9, 0.999), eps=1e-8, weight_decay=opt.weightDecay, amsgrad=False,
-                             fused=True)      # the same update as one launch over the six tables (the default is ~10 per step)
-    if opt.lr1 < 0:                                                        # sr/3_finetune_lut.py:89-95
-        lf = lambda x: (((1 + math.cos(x * math.pi / opt.totalIter)) / 2) ** 1.0) * 0.8 + 0.2   # noqa: E731
-    else:
-        lr_b = opt.lr1 / opt.lr0
-        lr_a = 1 - lr_b
-        lf = lambda x: (((1 + math.cos(x * math.pi / opt.totalIter)) / 2) ** 1.0) * lr_a + lr_b   # noqa: E731
-    sched = torch.optim.lr_scheduler.LambdaLR(optim, lr_lambda=lf)
-    make_lr = getattr(opt, "makeLR", False)
-    if getattr(opt, "hostData", False):
-        data = CropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, make_lr, log)
-    else:
-        try:      # the set stays on the device for the whole run: at most half of what is free now
-            data = DeviceCropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, max_bytes=torch.cuda.mem_get_info()[0] // 2,
-                                      make_lr=make_lr, log=log)
-        except TrainingSetTooLarge as e:
-            log("{} | training set of {} bytes exceeds half the free device memory ({}): batches are cut on the host".format(opt.expDir, e.nbytes, e.limit))
-            data = e.host
-    if getattr(opt, "valoutDir", None) is None:
-        opt.valoutDir = os.path.join(opt.expDir, "val")
-    engine, engine_at = None, 0
-    if getattr(opt, "valEngine", False):      # one engine for the run: later installs rewrite its tables in place
-        from .engine import MuLUTEngine
-        engine = MuLUTEngine(next(net.parameters()).device.index).configure(opt.stages, opt.modes, opt.scale, opt.interval)
-        opt.valEngineResults = {}              # {dataset: [images, 2]} of the last engine validation, for callers
-    # the loop never waits for the device per step: every loss goes into this vector, read at the display points and at the end
-    loss_buf = torch.zeros(opt.totalIter, dtype=torch.float32, device="cuda")
-    losses, t_mark = [], time.time()
-    for i in range(1, opt.totalIter + 1):
-        im, lb = data.next()
-        optim.zero_grad()
+class FinetuneRun:
+    """One fine-tune run (sr/3_finetune_lut.py:80-171) in three parts: what is built before the loop, one iteration, and what follows
+    the last one.  ``finetune()`` is ``run = FinetuneRun(opt, log); step() x totalIter; run.finish()``; a caller that drives the steps
+    itself can look at ``net``, ``optim``, ``sched`` and ``loss_buf`` between two of them."""
+
+    def __init__(self, opt, log=print):
+        self.opt, self.log = opt, log
+        wide = any(m in "eho" for m in opt.modes)      # the reference's module stops at s, d, y (sr/model.py:119-121)
+        self.net = (MuLUTWide if wide else MuLUTInterval if opt.interval in (5, 6) else MuLUT)(opt.expDir, opt.stages, list(opt.modes), upscale=opt.scale, interval=opt.interval).cuda()
+        params = [p for p in self.net.parameters() if p.requires_grad]
+        # the reference's Adam as one launch over the six tables, its arithmetic in float64 (torch's default is ~10 launches per step; its
+        # fused=True is one, but strays from float64 Adam by hundreds of float32 ulps on an element that lands near zero, as every float32 Adam does)
+        self.optim = Adam(params, lr=opt.lr0, betas=(0.9, 0.999), eps=1e-8, weight_decay=opt.weightDecay)
+        if opt.lr1 < 0:                                                        # sr/3_finetune_lut.py:89-95
+            lf = lambda x: (((1 + math.cos(x * math.pi / opt.totalIter)) / 2) ** 1.0) * 0.8 + 0.2   # noqa: E731
+        else:
+            lr_b = opt.lr1 / opt.lr0
+            lr_a = 1 - lr_b
+            lf = lambda x: (((1 + math.cos(x * math.pi / opt.totalIter)) / 2) ** 1.0) * lr_a + lr_b   # noqa: E731
+        self.sched = torch.optim.lr_scheduler.LambdaLR(self.optim, lr_lambda=lf)
+        make_lr = getattr(opt, "makeLR", False)
+        if getattr(opt, "hostData", False):
+            self.data = CropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, make_lr, log)
+        else:
+            try:      # the set stays on the device for the whole run: at most half of what is free now
+                self.data = DeviceCropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, max_bytes=torch.cuda.mem_get_info()[0] // 2,
+                                               make_lr=make_lr, log=log)
+            except TrainingSetTooLarge as e:
+                log("{} | training set of {} bytes exceeds half the free device memory ({}): batches are cut on the host".format(opt.expDir, e.nbytes, e.limit))
+                self.data = e.host
+        if getattr(opt, "valoutDir", None) is None:
+            opt.valoutDir = os.path.join(opt.expDir, "val")
+        self.engine, self.engine_at = None, 0
+        if getattr(opt, "valEngine", False):      # one engine for the run: later installs rewrite its tables in place
+            from .engine import MuLUTEngine
+            self.engine = MuLUTEngine(next(self.net.parameters()).device.index).configure(opt.stages, opt.modes, opt.scale, opt.interval)
+            opt.valEngineResults = {}              # {dataset: [images, 2]} of the last engine validation, for callers
+        # the loop never waits for the device per step: every loss goes into this vector, read at the display points and at the end
+        self.loss_buf = torch.zeros(opt.totalIter, dtype=torch.float32, device="cuda")
+        self.losses, self.t_mark, self.i = [], time.time(), 0
+
+    def step(self):
+        """Iteration self.i + 1 (sr/3_finetune_lut.py:118-159).  Returns nothing: no wait for the device but at a display point."""
+        opt, log, net = self.opt, self.log, self.net
+        self.i += 1
+        i, losses = self.i, self.losses
+        im, lb = self.data.next()
+        self.optim.zero_grad()
         loss = F.mse_loss(net(im), lb)
         loss.backward()
-        optim.step()
-        sched.step()
-        loss_buf[i - 1] = loss.detach()
+        self.optim.step()
+        self.sched.step()
+        self.loss_buf[i - 1] = loss.detach()
         if i % opt.displayStep == 0:
-            losses.extend(loss_buf[len(losses):i].tolist())        # (waits for the device)
+            losses.extend(self.loss_buf[len(losses):i].tolist())        # (waits for the device)
             # rT: wall time per iteration since the last display point (or the start), validation left out
             log("{} | Iter:{:6d}, Sample:{:6d}, GPixel:{:.2e}, rT:{:.4f}".format(opt.expDir, i, i * opt.batchSize,
                                                                                sum(losses[i - opt.displayStep:i]) / opt.displayStep,
-                                                                               (time.time() - t_mark) / opt.displayStep))
-            t_mark = time.time()
+                                                                               (time.time() - self.t_mark) / opt.displayStep))
+            self.t_mark = time.time()
         if getattr(opt, "valStep", 0) and (i % opt.valStep == 0 or i == 1) and os.path.isdir(getattr(opt, "valDir", "")):   # :152-158
             t_val = time.time()
             valid_steps(net, opt, i, log)
-            if engine is not None:
-                opt.valEngineResults, engine_at = engine_valid_steps(net, engine, opt, i, log), i
-            t_mark += time.time() - t_val
-    losses.extend(loss_buf[len(losses):opt.totalIter].tolist())
-    if engine is not None:
-        if engine_at != opt.totalIter and os.path.isdir(getattr(opt, "valDir", "")):      # the tables as they are exported below
-            opt.valEngineResults = engine_valid_steps(net, engine, opt, opt.totalIter, log)
-        engine.close()
-    if isinstance(data, DeviceCropProvider) and int(data.bad.item()):
-        raise RuntimeError("mulut_ft_crop_batch refused %d samples" % int(data.bad.item()))
-    for key, table in net.export_int8().items():                          # :162-169
-        np.save(os.path.join(opt.expDir, "LUT_ft_x{}_{}bit_int8_{}.npy".format(opt.scale, opt.interval, key)), table)
-    log("Finetuned LUT saved to {}".format(opt.expDir))
-    return losses
+            if self.engine is not None:
+                opt.valEngineResults, self.engine_at = engine_valid_steps(net, self.engine, opt, i, log), i
+            self.t_mark += time.time() - t_val
+
+    def finish(self):
+        """The last read-back, the engine's score of the tables as they are exported, the export (:162-171).  Returns the losses."""
+        opt, log, net, data, losses = self.opt, self.log, self.net, self.data, self.losses
+        losses.extend(self.loss_buf[len(losses):self.i].tolist())
+        if self.engine is not None:
+            if self.engine_at != opt.totalIter and os.path.isdir(getattr(opt, "valDir", "")):      # the tables as they are exported below
+                opt.valEngineResults = engine_valid_steps(net, self.engine, opt, opt.totalIter, log)
+            self.engine.close()
+        if isinstance(data, DeviceCropProvider) and int(data.bad.item()):
+            raise RuntimeError("mulut_ft_crop_batch refused %d samples" % int(data.bad.item()))
+        for key, table in net.export_int8().items():                          # :162-169
+            np.save(os.path.join(opt.expDir, "LUT_ft_x{}_{}bit_int8_{}.npy".format(opt.scale, opt.interval, key)), table)
+        log("Finetuned LUT saved to {}".format(opt.expDir))
+        return losses
+
+
+def finetune(opt, log=print):
+    run = FinetuneRun(opt, log)
+    for _ in range(opt.totalIter):
+        run.step()
+    return run.finish()
 
 
 def main(argv=None):

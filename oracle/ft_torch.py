@@ -41,13 +41,24 @@ def _case_order(fa, fb, fc, fd):
     return w(fab & fbc, g1, w(fab & fac, g2, w(fab, g3, w(fac, g4, w(fbc, g5, g6)))))
 
 
-def interp_batch(weight, upscale, mode, img_in, bd, interval=4, quantised=False):
+def quantise_f32(weight):
+    """clamp(round_func(weight * 127), -127, 127) (sr/model.py:74-76) with the product, the rounding and the clamp's test done in
+    float32 -- where the reference decides its ties -- for a `weight` of any float type that holds float32 values: the quantised table
+    in weight's own type, with the BPDA gradient 127 where the rounded value lies in [-127, 127] (torch.clamp passes both ends)."""
+    r = torch.round(weight.detach().to(torch.float32) * 127)
+    passes = ((r >= -127) & (r <= 127)).to(weight.dtype)
+    lin = weight * 127 * passes
+    return lin + (torch.clamp(r, -127, 127).to(weight.dtype) - lin).detach()
+
+
+def interp_batch(weight, upscale, mode, img_in, bd, interval=4, quantised=False, quant_f32=False):
     """InterpTorchBatch (sr/model.py:69-287): weight [L^4, u*u] (learnable, int8/127 scale), img_in [B,C,h+bd,w+bd].
-    quantised: `weight` already is the quantised table (what the stage kernels of the C ABI are handed)."""
+    quantised: `weight` already is the quantised table (what the stage kernels of the C ABI are handed).
+    quant_f32: quantise in float32 whatever weight's type is (quantise_f32): a float64 run then takes the reference's tables."""
     if mode not in PATTERNS:
         raise ValueError("Mode {} not implemented.".format(mode))
     q, L = 2 ** interval, 2 ** (8 - interval) + 1
-    wq = weight if quantised else torch.clamp(round_bpda(weight * 127), -127, 127)
+    wq = weight if quantised else quantise_f32(weight) if quant_f32 else torch.clamp(round_bpda(weight * 127), -127, 127)
     B, C, Hp, Wp = img_in.shape
     h, w = Hp - bd, Wp - bd
     crops = [img_in[:, :, di:di + h, dj:dj + w] for di, dj in PATTERNS[mode]]
@@ -68,7 +79,7 @@ def interp_batch(weight, upscale, mode, img_in, bd, interval=4, quantised=False)
     return out / q
 
 
-def stage(tables, x, modes, is_last, u, interval=4, quantised=False):
+def stage(tables, x, modes, is_last, u, interval=4, quantised=False, quant_f32=False):
     """One stage of MuLUT.forward (sr/model.py:296-309) on x in 0..255: all modes x 4 rotations, pred rounded after every pass,
     then the stage's clamp and round.  tables: one [L^4, u*u] tensor per mode, in the order of `modes`.  Returns (stage output,
     un-clamped pred).  quantised: the tables are taken as quantised already (no * 127, round, clamp), so their gradients are those of
@@ -79,15 +90,21 @@ def stage(tables, x, modes, is_last, u, interval=4, quantised=False):
         pad = PAD[mode]
         for r in range(4):
             t = F.pad(torch.rot90(x, r, [2, 3]), (0, pad, 0, pad), mode="replicate")
-            pred = pred + torch.rot90(interp_batch(wgt, u, mode, t, pad, interval, quantised), (4 - r) % 4, [2, 3])
+            pred = pred + torch.rot90(interp_batch(wgt, u, mode, t, pad, interval, quantised, quant_f32), (4 - r) % 4, [2, 3])
             pred = round_bpda(pred)
     return round_bpda(torch.clamp(pred / avg + bias, 0, 255)), pred
 
 
-def forward(weights, x, stages, modes, upscale, interval=4):
-    """MuLUT.forward (sr/model.py:289-312).  weights: dict 's{stage}_{mode}' -> tensor [L^4, u*u] (requires_grad ok)."""
-    x = x * 255.0
+def forward(weights, x, stages, modes, upscale, interval=4, quant_f32=False, preds=None):
+    """MuLUT.forward (sr/model.py:289-312).  weights: dict 's{stage}_{mode}' -> tensor [L^4, u*u] (requires_grad ok).
+    quant_f32: see interp_batch -- with float64 weights and x (holding float32 values), the input's * 255 and the quantisation are
+    done in float32, as the reference does them, and everything after them runs in float64.
+    preds: a list that receives every stage's un-clamped pred (detached)."""
+    x = (x.to(torch.float32) * 255.0).to(x.dtype) if quant_f32 else x * 255.0
     for s in range(stages):
         last = s + 1 == stages
-        x, _ = stage([weights["s{}_{}".format(s + 1, mode)] for mode in modes], x, modes, last, upscale if last else 1, interval)
+        x, pred = stage([weights["s{}_{}".format(s + 1, mode)] for mode in modes], x, modes, last, upscale if last else 1, interval,
+                        quant_f32=quant_f32)
+        if preds is not None:
+            preds.append(pred.detach())
     return x / 255.0

@@ -5,7 +5,7 @@ bs 32 and bs 256, crop 48, 2-stage sdy x4, on 8 synthetic 340 x 510 / 1360 x 204
 
 A run is three display intervals; what is reported is the wall time per iteration between two display points (the driver's rT, taken
 here from the clock at its log calls: the log line rounds rT to 0.1 ms) of the second and third -- the first holds the warm-up.  Beside it, in the same process:
-  step_alone_ms     the step (forward + backward + fused Adam) on one fixed device batch, steps queued back to back
+  step_alone_ms     the step (forward + backward + the driver's Adam) on one fixed device batch, steps queued back to back
   crop_kernel_ms    device-event time of mulut_ft_crop_batch alone (draws already on the device), launches back to back
   fill_ms           device-event time of a plain fill of the same two output tensors, measured in rounds alternating with the kernel's
     python tools/ft_driver_bench.py --out profiles/ft_driver_ab.json
@@ -105,9 +105,9 @@ def kernel_and_fill(train, bs, rounds=15, reps=20):
 
 
 def step_alone(exp, batch, steps):
-    from mulut_amd.finetune import MuLUT
+    from mulut_amd.finetune import Adam, MuLUT
     net = MuLUT(exp, 2, list("sdy"), upscale=SCALE, interval=4).cuda()
-    optim = torch.optim.Adam([p for p in net.parameters() if p.requires_grad], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, fused=True)
+    optim = Adam([p for p in net.parameters() if p.requires_grad], lr=1e-3, betas=(0.9, 0.999), eps=1e-8)      # the driver's
     im, lb = batch
 
     def step():
