@@ -289,6 +289,15 @@ int mulut_ft_wide_stage_backward(int device, int interval, const float *const *w
 typedef struct { long long lr_off, hr_off; int lr_h, lr_w, hr_h, hr_w, ch, pad; } mulut_ft_pair;   /* 40 bytes, offsets into pool */
 int mulut_ft_crop_batch(int device, const unsigned char *pool, long long pool_bytes, const mulut_ft_pair *pairs, int n_pairs,
                         const int *draws, int B, int sz, int scale, float *im, float *lb, int *bad, void *stream);
+/* The module's output as the bytes the validation loop scores and saves, in one launch: replaces
+ *   pred = model_G(im) * 255.0;  np.round(np.clip(np.transpose(pred, [1, 2, 0]), 0, 255)).astype(np.uint8)      (sr/3_finetune_lut.py:50-54)
+ *   pred    : device float32 planar [3][H][W], the module's output in 0..1
+ *   out_hwc : device uint8 [H][W][3] at ANY byte address; nothing outside out_hwc[0, H*W*3) is written
+ * byte = rintf(fminf(fmaxf(pred * 255.0f, 0.0f), 255.0f)): the float32 product, the clamp and round-half-to-even, the same byte as
+ * the expression above for every finite input and both infinities.  What a NaN becomes is UNSPECIFIED (some byte; no fault).
+ * Refusals as for mulut_ft_crop_batch, before the device is touched: NULL pred or out_hwc, or a non-positive H or W MULUT_EINVAL;
+ * then H * W * 3 >= 2^31 MULUT_EUNSUPPORTED.  Stateless and stream-ordered, like the calls above. */
+int mulut_ft_val_pack(int device, const float *pred, int H, int W, unsigned char *out_hwc, void *stream);
 
 /* ---- device-side evaluation (not on the inference path) ---------------------------------------------------
  * Y-channel PSNR and SSIM of a super-resolved frame against its ground truth, exactly as the test script scores
@@ -300,6 +309,35 @@ int mulut_ft_crop_batch(int device, const unsigned char *pool, long long pool_by
 long long mulut_eval_ws_doubles(int H, int W);
 int mulut_eval_y(int device, const void *gt_hwc, const void *out_hwc, int H, int W, int shave, double *ws, long long ws_doubles,
                  double *psnr, double *ssim, void *stream);
+/* The same score for a LIST of pairs of different sizes in one stream-ordered call: the scoring of the fine-tune driver's validation
+ * loop (sr/3_finetune_lut.py:23-65, PSNR and cal_ssim at :56-58) without a wait per image.  Ground truths lie in one device pool
+ * of bytes, the outputs to score in another; an item names one pair by its byte offsets into the two pools (uint8 [H][W][3], no
+ * alignment asked of either offset) and states the size of each pool, so the plan can vouch for every address it will form.
+ * mulut_eval_plan_create (sr/3_finetune_lut.py:23-65): `items` is a HOST array of n entries.  Checked on the host, in this order, each
+ *   class over the whole list before the next, and before the device is touched: a NULL `items` or `plan`, n < 1 or shave < 0
+ *   MULUT_EINVAL; an item with H or W below 11 (the SSIM window) or not larger than 2 * shave MULUT_ESHAPE; an item with a negative
+ *   offset or not wholly inside the pool size it states MULUT_EINVAL; 2^31 workgroups or more in one launch (the list's squared-error
+ *   blocks, min(1024, ceil(interior / 256)) per item, or its 32 x 32 SSIM tiles) MULUT_EUNSUPPORTED.  Then one allocation and one
+ *   blocking copy (not capturable): the item table, the map from workgroup to (item, block or tile) of each launch, and the
+ *   workspace of one double per workgroup.  *plan is NULL after any failure.
+ * mulut_eval_plan_run (sr/3_finetune_lut.py:56-58): three kernel launches on `stream` and nothing else -- it allocates nothing and
+ *   waits for nothing, so it can be captured into a hipGraph, and a replay scores the pools as they are in memory then.  gt_pool and
+ *   out_pool are device pointers to at least the bytes the items stated.  Leaves sums[i][0] = item i's summed squared Y error over
+ *   the shaved interior and sums[i][1] = its summed SSIM map, n x 2 DEVICE doubles.  Each sum is made of the partial sums
+ *   mulut_eval_y makes for that pair, added in the same order by one lane (no atomics): mulut_eval_finish of the two gives
+ *   mulut_eval_y's two doubles bit for bit.  The workspace belongs to the plan: runs of ONE plan must be ordered one behind the
+ *   other (one stream, or events); different plans are independent.  NULL plan, pool or sums MULUT_EINVAL.
+ * mulut_eval_plan_destroy: frees the allocation (hipFree waits for work in flight on the device) and the plan.
+ * mulut_eval_finish (common/utils.py:63-72,101; host only, needs no device): the two sums of one H x W pair to (PSNR, SSIM) -- the
+ *   float32 mean of the squared error, sqrt, 20 log10(255 / rmse) (inf for sse = 0), and the SSIM sum over its (H-10)(W-10) windows.
+ *   mulut_eval_y ends in this call.  NULL psnr or ssim, H, W <= 0 or shave < 0 MULUT_EINVAL; H or W below 11 or not above 2 * shave
+ *   MULUT_ESHAPE. */
+typedef struct { long long gt_off, out_off; int H, W; long long gt_pool_bytes, out_pool_bytes; } mulut_eval_item;   /* 40 bytes */
+typedef struct mulut_eval_plan mulut_eval_plan;
+int mulut_eval_plan_create(int device, const mulut_eval_item *items, int n, int shave, mulut_eval_plan **plan);
+int mulut_eval_plan_run(const mulut_eval_plan *plan, const void *gt_pool, const void *out_pool, double *sums, void *stream);
+int mulut_eval_plan_destroy(mulut_eval_plan *plan);
+int mulut_eval_finish(double sse, double ssim_sum, int H, int W, int shave, double *psnr, double *ssim);
 
 /* ---- LR images made on the device (not on the inference path) ------------------------------------------------
  * Pillow's bicubic resampling of 8-bit images, byte for byte: what sr/Test_dataset.py:24-25 does with

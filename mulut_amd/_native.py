@@ -21,8 +21,8 @@ EXPORTS = [
     "mulut_pipeline_rows", "mulut_halo", "mulut_reserve", "mulut_set_stage_timing", "mulut_last_stage_ms", "mulut_last_kernel_ms",
     "mulut_set_tuning", "mulut_kernel_name", "mulut_ft_stage_forward", "mulut_ft_stage_backward", "mulut_ft_quantize", "mulut_ft_quantize_backward", "mulut_ft_adam",
     "mulut_ft_stage_forward_mask", "mulut_ft_stage_backward_mask", "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward",
-    "mulut_ft_wide_stage_forward", "mulut_ft_wide_stage_backward", "mulut_ft_crop_batch",
-    "mulut_eval_ws_doubles", "mulut_eval_y", "mulut_last_detail_counters", "mulut_debug_read",
+    "mulut_ft_wide_stage_forward", "mulut_ft_wide_stage_backward", "mulut_ft_crop_batch", "mulut_ft_val_pack",
+    "mulut_eval_ws_doubles", "mulut_eval_y", "mulut_eval_plan_create", "mulut_eval_plan_run", "mulut_eval_plan_destroy", "mulut_eval_finish", "mulut_last_detail_counters", "mulut_debug_read",
     "mulut_resample_coeffs", "mulut_resample_plan_create", "mulut_resample_plan_destroy", "mulut_resample_run",
 ]
 
@@ -191,6 +191,13 @@ def load(path=None):
     L.mulut_eval_y.argtypes = [i, p, p, i, i, i, p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double),
                                ctypes.POINTER(ctypes.c_double), p]
     L.mulut_eval_y.restype = i
+    L.mulut_eval_plan_create.argtypes = [i, p, i, i, ctypes.POINTER(p)]
+    L.mulut_eval_plan_run.argtypes = [p, p, p, p, p]
+    L.mulut_eval_plan_destroy.argtypes = [p]
+    L.mulut_eval_finish.argtypes = [d, d, i, i, i, ctypes.POINTER(d), ctypes.POINTER(d)]
+    L.mulut_ft_val_pack.argtypes = [i, p, i, i, p, p]
+    for name in ("mulut_eval_plan_create", "mulut_eval_plan_run", "mulut_eval_plan_destroy", "mulut_eval_finish", "mulut_ft_val_pack"):
+        getattr(L, name).restype = i
     i32p = ctypes.POINTER(ctypes.c_int32)
     L.mulut_resample_coeffs.argtypes = [i, i, i32p, i32p, i32p, ctypes.c_longlong]
     L.mulut_resample_plan_create.argtypes = [i, i, i, i, i, ctypes.POINTER(p)]

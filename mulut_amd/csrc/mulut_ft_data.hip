@@ -26,6 +26,10 @@
 //                     whatever the device's division flags are) and staged in LDS once per workgroup.
 // The draws are device-resident, so the host cannot vet them: the kernel does, once per workgroup, with compares that are uniform
 // in it.  A sample that fails is written as zeros and counted once in *bad; no address is formed from it.
+//
+//   ft_val_pack_kernel  the other end of the loop's data: the module's output for one validation image (float32 planar, 0..1) to the
+//                     packed bytes the validation scores and saves, sr/3_finetune_lut.py:50-54 -- times 255, clamp, round half to
+//                     even -- in one launch, into a slot of a pool at any byte address.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mulut.h"
@@ -151,7 +155,36 @@ __global__ void __launch_bounds__(kCropNT) ft_crop_kernel(CropArgs a) {
     }
 }
 
+constexpr int kPackNT = 256;
+
+// rintf rounds half to even in the default rounding mode, as torch.round and np.round do
+__device__ __forceinline__ unsigned char pack_byte(float v) { return (unsigned char)rintf(fminf(fmaxf(v * 255.0f, 0.0f), 255.0f)); }
+
+// one lane per pixel: three coalesced plane loads, three byte stores (a wave writes 192 consecutive bytes; any address)
+__global__ void __launch_bounds__(kPackNT) ft_val_pack_kernel(const float *pred, int n, unsigned char *out) {
+    const int i = (int)(blockIdx.x * (unsigned)kPackNT + threadIdx.x);
+    if (i >= n) return;
+    const unsigned char r = pack_byte(pred[i]), g = pack_byte(pred[(size_t)n + i]), b = pack_byte(pred[2 * (size_t)n + i]);
+    unsigned char *o = out + 3 * (size_t)i;
+    o[0] = r;
+    o[1] = g;
+    o[2] = b;
+}
+
 }  // namespace mulut
+
+/* sr/3_finetune_lut.py:50-54 */
+extern "C" int mulut_ft_val_pack(int device, const float *pred, int H, int W, unsigned char *out_hwc, void *stream) {
+    using namespace mulut;
+    if (!pred || !out_hwc) return MULUT_EINVAL;
+    if (H <= 0 || W <= 0) return MULUT_EINVAL;
+    const long long n = (long long)H * W;
+    if (n > ((1LL << 31) - 1) / 3) return MULUT_EUNSUPPORTED;      // H * W * 3 >= 2^31 (n * 3 itself may leave 64 bits)
+    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
+    hipLaunchKernelGGL(ft_val_pack_kernel, dim3((unsigned)((n + kPackNT - 1) / kPackNT)), dim3(kPackNT), 0, (hipStream_t)stream, pred, (int)n,
+                       out_hwc);
+    return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
+}
 
 extern "C" int mulut_ft_crop_batch(int device, const unsigned char *pool, long long pool_bytes, const mulut_ft_pair *pairs, int n_pairs,
                                    const int *draws, int B, int sz, int scale, float *im, float *lb, int *bad, void *stream) {

@@ -28,6 +28,14 @@ kernel write it from the pair's HR slot of the pool straight into its LR slot; `
 current parameters are installed into one ``MuLUTEngine`` (``MuLUT.install_into``: quantised as they will be exported) and every validation image runs through ``engine.pipeline``, scored by ``mulut_eval_y`` and logged with the
 test script's line behind the iteration.  ``valid_steps`` rounds after every pass (the module's forward); the deployed cascade does not,
 which is 30.605 against 30.608 dB on Set5 for the shipped tables (both print as 30.61) -- with the flag the deployed number is in the log while the run goes on.
+
+``--valResident`` (recommended whenever the run validates) takes the host out of a validation point.  ``DeviceValSet`` decodes the sets
+once per run with ``valid_steps``' checks and conversions and keeps them on the device; ``resident_valid_steps`` runs the module per image
+and ``mulut_ft_val_pack`` writes its bytes straight into an output pool, ``mulut_eval_plan_run`` scores a whole dataset in one
+stream-ordered call, the sums of all datasets are read back once, and the PNGs are copied out on a side stream and encoded by
+``--valWorkers`` threads (``ValWriter``) behind the loop.  ``--valSave every|last|never`` picks the points whose files are written.
+``resident_engine_valid_steps`` does the same for ``--valEngine``.  The log lines, ``opt.valResults`` and the files are those of the host
+loops, bit for bit; a set above a quarter of the free device memory falls back to ``valid_steps`` with one log line.
 """
 import argparse
 import ctypes
@@ -298,6 +306,261 @@ def engine_valid_steps(net, engine, opt, it, log=print):
     return results
 
 
+def val_png_name(ds, fn):
+    """The reference names a result after the LAST '_'-separated token of "{dataset}_{stem}" (sr/3_finetune_lut.py:41,61)."""
+    return '{}_lutft.png'.format((ds + '_' + fn[:-4]).split('_')[-1])
+
+
+class ValidationSetTooLarge(Exception):
+    """The resident validation set needs more device memory than the caller allows."""
+
+    def __init__(self, nbytes, limit):
+        super().__init__("validation set of %d bytes exceeds the %d allowed on the device" % (nbytes, limit))
+        self.nbytes, self.limit = nbytes, limit
+
+
+class ValWriter:
+    """The PNGs of a validation point, encoded behind the loop by a pool of `workers` threads (Pillow and zlib release the GIL).
+    submit() hands over one point's (path, array) list and returns without waiting for its files; it first joins the point before,
+    so the files of point k are complete before any file of point k + 1 is begun and at most one point is ever pending.  `ready`,
+    if given, is called once on a worker before the point's first file (the wait for the copy that fills the arrays).  A failed
+    write is raised by the next join() -- that of the next submit(), or the caller's last one -- not lost."""
+
+    def __init__(self, workers=4, encode=None):
+        from concurrent.futures import ThreadPoolExecutor
+        self._pool = ThreadPoolExecutor(max_workers=max(1, int(workers)), thread_name_prefix="valpng")
+        self._encode = encode or (lambda path, arr: Image.fromarray(arr).save(path))
+        self._pending = []
+
+    def submit(self, jobs, ready=None):
+        self.join()
+        gate = self._pool.submit(ready) if ready is not None else None
+
+        def one(path, arr):
+            if gate is not None:
+                gate.result()
+            self._encode(path, arr)
+        self._pending = ([gate] if gate is not None else []) + [self._pool.submit(one, path, arr) for path, arr in jobs]
+
+    def join(self):
+        pending, self._pending, first = self._pending, [], None
+        for f in pending:                      # every file is waited for, then the first failure is raised
+            try:
+                f.result()
+            except BaseException as e:         # noqa: B902
+                first = first or e
+        if first is not None:
+            raise first
+
+    def close(self):
+        try:
+            self.join()
+        finally:
+            self._pool.shutdown(wait=True)
+
+
+class DeviceValSet:
+    """The validation sets of valid_steps / engine_valid_steps, resident on the device for the whole run: built once from
+    {valDir}/{dataset}/HR and LR_bicubic/X{scale} with the checks and conversions valid_steps applies per image (modcrop, grey
+    replicated to three channels, the shape test and its error text).
+      gt_pool   uint8   every ground truth, HWC, back to back
+      out_pool  uint8   the same layout: image n's result goes where its ground truth lies in gt_pool
+      lr_pool   uint8   every LR image, HWC (what the engine takes)
+      lr_f32    float32 the same images as the module takes them, planar [1][3][h][w], the HOST's astype(float32) / 255.0 uploaded
+                        once (the device's division is a product with a rounded reciprocal: not the same float for every byte)
+      plans     one mulut_eval_plan per dataset over (gt_pool, out_pool); sums: device float64 [images][2], read back once per point
+    `max_bytes`: a set that needs more raises ValidationSetTooLarge before anything is allocated on the device."""
+
+    def __init__(self, opt, max_bytes=None, workers=4, encode=None):
+        from . import _native
+        from .metrics import modcrop
+        self.lib = _native.load()
+        self.scale = int(opt.scale)
+        self.sets, images, gt_bytes, lr_bytes = [], [], 0, 0
+        for ds in _val_datasets(opt):
+            hr_dir = os.path.join(opt.valDir, ds, "HR")
+            if not os.path.isdir(hr_dir):
+                continue
+            first, files = len(images), sorted(os.listdir(hr_dir))
+            for fn in files:
+                lb = np.array(Image.open(os.path.join(hr_dir, fn)))
+                im = np.array(Image.open(os.path.join(opt.valDir, ds, "LR_bicubic", "X%d" % opt.scale, fn)))
+                lb = modcrop(lb, opt.scale)
+                if lb.ndim == 2:
+                    lb = np.stack([lb] * 3, 2)
+                if im.ndim == 2:
+                    im = np.stack([im] * 3, 2)
+                if (im.shape[0] * opt.scale, im.shape[1] * opt.scale) != lb.shape[:2] or im.shape[2] != 3 or lb.shape[2] != 3:
+                    raise ValueError("{}/{}: LR {} x scale {} is not the modcropped HR {}".format(ds, fn, im.shape, opt.scale, lb.shape))
+                if lb.dtype != np.uint8 or im.dtype != np.uint8:
+                    raise ValueError("{}/{}: not a pair of 8-bit images".format(ds, fn))
+                images.append((np.ascontiguousarray(im), np.ascontiguousarray(lb), gt_bytes, lr_bytes))
+                gt_bytes, lr_bytes = gt_bytes + lb.size, lr_bytes + im.size
+            if files:
+                self.sets.append({"name": ds, "files": files, "first": first, "n": len(files), "out_dir": os.path.join(opt.valoutDir, ds)})
+        self.gt_bytes, self.lr_bytes = gt_bytes, lr_bytes
+        self.nbytes = 2 * gt_bytes + 5 * lr_bytes          # gt + out, LR bytes + LR floats
+        if max_bytes is not None and self.nbytes > max_bytes:
+            raise ValidationSetTooLarge(self.nbytes, max_bytes)
+        self.device = torch.empty(0).cuda().device
+        dev = self.device
+        self.gt_pool = torch.empty(gt_bytes, dtype=torch.uint8, device=dev)
+        self.out_pool = torch.zeros(gt_bytes, dtype=torch.uint8, device=dev)
+        self.lr_pool = torch.empty(lr_bytes, dtype=torch.uint8, device=dev)
+        self.lr_f32 = torch.empty(lr_bytes, dtype=torch.float32, device=dev)
+        self.shapes = []                                   # per image: (gt_off, H, W, lr_off, h, w)
+        for im, lb, g, l in images:                        # image by image
+            self.gt_pool[g:g + lb.size].copy_(torch.from_numpy(lb.reshape(-1)))
+            self.lr_pool[l:l + im.size].copy_(torch.from_numpy(im.reshape(-1)))
+            self.lr_f32[l:l + im.size].copy_(torch.from_numpy((np.ascontiguousarray(im.transpose(2, 0, 1)).astype(np.float32) / 255.0).reshape(-1)))
+            self.shapes.append((g, lb.shape[0], lb.shape[1], l, im.shape[0], im.shape[1]))
+        del images
+        self.sums = torch.zeros((len(self.shapes), 2), dtype=torch.float64, device=dev)
+        self.sums_host = torch.zeros((len(self.shapes), 2), dtype=torch.float64).pin_memory()
+        for s in self.sets:
+            items = np.zeros((s["n"], 5), np.int64)        # mulut_eval_item: gt_off, out_off, (H, W) as two int32, the two pool sizes
+            for k, (g, H, W, _, _, _) in enumerate(self.shapes[s["first"]:s["first"] + s["n"]]):
+                items[k, 0], items[k, 1], items[k, 3], items[k, 4] = g, g, gt_bytes, gt_bytes
+                items[k, 2:3].view(np.int32)[:] = (H, W)
+            plan = ctypes.c_void_p()
+            rc = self.lib.mulut_eval_plan_create(dev.index, items.ctypes.data, s["n"], self.scale, ctypes.byref(plan))
+            if rc:
+                self.close()
+                raise RuntimeError(self.lib.mulut_strerror(rc).decode())
+            s["plan"] = plan
+        torch.cuda.synchronize(dev)                        # the set is in place whatever stream a validation runs on
+        self.writer = ValWriter(workers, encode)
+        self.copy_stream, self.copied, self.out_host = None, None, None
+
+    def lr_tensor(self, n):
+        _, _, _, l, h, w = self.shapes[n]
+        return self.lr_f32[l:l + 3 * h * w].view(1, 3, h, w)
+
+    def lr_bytes_hwc(self, n):
+        _, _, _, l, h, w = self.shapes[n]
+        return self.lr_pool[l:l + 3 * h * w].view(h, w, 3)
+
+    def out_slot(self, n):
+        g, H, W = self.shapes[n][:3]
+        return self.out_pool[g:g + 3 * H * W]
+
+    def before_write(self):
+        """The output pool is not rewritten before its copy to the host has finished: the current stream waits for that copy (the
+        host does not)."""
+        if self.copied is not None:
+            torch.cuda.current_stream(self.device).wait_event(self.copied)
+
+    def score(self):
+        """One mulut_eval_plan_run per dataset on the current stream, then the point's only wait: the sums of all datasets read back
+        once.  Returns {dataset: float64 array [images, 2]} of (PSNR, SSIM), mulut_eval_finish applied per image."""
+        stream = torch.cuda.current_stream(self.device)
+        for s in self.sets:
+            rc = self.lib.mulut_eval_plan_run(s["plan"], self.gt_pool.data_ptr(), self.out_pool.data_ptr(),
+                                              self.sums[s["first"]:].data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+            if rc:
+                raise RuntimeError(self.lib.mulut_strerror(rc).decode())
+        self.sums_host.copy_(self.sums, non_blocking=True)
+        stream.synchronize()
+        sums, out = self.sums_host.numpy(), {}
+        ps, ss = ctypes.c_double(), ctypes.c_double()
+        for s in self.sets:
+            rows = []
+            for n in range(s["first"], s["first"] + s["n"]):
+                _, H, W = self.shapes[n][:3]
+                rc = self.lib.mulut_eval_finish(float(sums[n, 0]), float(sums[n, 1]), H, W, self.scale, ctypes.byref(ps), ctypes.byref(ss))
+                if rc:
+                    raise RuntimeError(self.lib.mulut_strerror(rc).decode())
+                rows.append((ps.value, ss.value))
+            out[s["name"]] = np.asarray(rows, dtype=np.float64)
+        return out
+
+    def save(self):
+        """The output pool as it is on the current stream now, to {valoutDir}/{dataset}/ behind the loop: a copy to pinned host memory
+        on a side stream, then the writer's threads.  Joins the files of the point before (ValWriter.submit); does not wait for
+        its own."""
+        self.writer.join()                                 # (the pinned buffer is theirs until they are done)
+        if self.out_host is None:
+            self.out_host = torch.empty(self.gt_bytes, dtype=torch.uint8).pin_memory()
+            self.copy_stream = torch.cuda.Stream(self.device)
+        produced = torch.cuda.Event()
+        produced.record(torch.cuda.current_stream(self.device))
+        self.copy_stream.wait_event(produced)
+        with torch.cuda.stream(self.copy_stream):
+            self.out_host.copy_(self.out_pool, non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record(self.copy_stream)
+        self.copied = copied
+        host, jobs = self.out_host.numpy(), []
+        for s in self.sets:
+            os.makedirs(s["out_dir"], exist_ok=True)
+            for k, fn in enumerate(s["files"]):
+                g, H, W = self.shapes[s["first"] + k][:3]
+                jobs.append((os.path.join(s["out_dir"], val_png_name(s["name"], fn)), host[g:g + 3 * H * W].reshape(H, W, 3)))
+        self.writer.submit(jobs, ready=copied.synchronize)
+
+    def join(self):
+        """Every file submitted so far is on disk (or its failure is raised here)."""
+        self.writer.join()
+
+    def close(self):
+        for s in self.sets:
+            if s.get("plan") is not None:
+                self.lib.mulut_eval_plan_destroy(s.pop("plan"))
+        if getattr(self, "writer", None) is not None:
+            self.writer.close()
+
+
+def _val_saves(opt, it):
+    """--valSave: every point's files, the final validation point's only, or none."""
+    mode = getattr(opt, "valSave", "every")
+    if mode == "last":
+        step = getattr(opt, "valStep", 0)
+        return it == (((opt.totalIter // step) * step or 1) if step else 1)      # (iteration 1 is the only point of a run shorter than valStep)
+    return mode == "every"
+
+
+def resident_valid_steps(net, vset, opt, it, log=print):
+    """valid_steps from a DeviceValSet: per image the module under no_grad and one mulut_ft_val_pack straight into the image's slot of
+    the output pool, per dataset one mulut_eval_plan_run, one read-back at the end of the point, the PNGs behind the loop.  The same
+    log lines, return value and opt.valResults as valid_steps, the same doubles."""
+    lib, was_training = vset.lib, net.training
+    net.eval()
+    vset.before_write()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(vset.device).cuda_stream)
+    with torch.no_grad():
+        for n in range(len(vset.shapes)):
+            pred = net(vset.lr_tensor(n)).contiguous()
+            _, H, W = vset.shapes[n][:3]
+            if tuple(pred.shape) != (1, 3, H, W) or pred.dtype != torch.float32:
+                raise ValueError("the module's output {} is not the ground truth's [1, 3, {}, {}]".format(tuple(pred.shape), H, W))
+            rc = lib.mulut_ft_val_pack(vset.device.index, pred.data_ptr(), H, W, vset.out_slot(n).data_ptr(), stream)
+            if rc:
+                raise RuntimeError(lib.mulut_strerror(rc).decode())
+    per_image = vset.score()
+    if _val_saves(opt, it):
+        vset.save()
+    results = {}
+    for ds, rows in per_image.items():
+        results[ds] = (float(np.mean(rows[:, 0].tolist())), float(np.mean(rows[:, 1].tolist())))
+        log('Iter {} | Dataset {} | AVG PSNR: {:02f}, AVG: SSIM: {:04f}'.format(it, ds, results[ds][0], results[ds][1]))
+    net.train(was_training)
+    opt.valResults = per_image
+    return results
+
+
+def resident_engine_valid_steps(net, engine, vset, opt, it, log=print):
+    """engine_valid_steps from a DeviceValSet: install_into, engine.pipeline from the uint8 LR pool into the output pool, the same
+    plans and read-back as resident_valid_steps.  The lines and arrays of engine_valid_steps.  (It saves no files, as that does not.)"""
+    net.install_into(engine)
+    vset.before_write()
+    for n in range(len(vset.shapes)):
+        engine.pipeline(vset.lr_bytes_hwc(n), out=vset.out_slot(n))
+    results = vset.score()
+    for ds in results:
+        log('Iter {} | Dataset {} | AVG LUT PSNR: {:.2f} SSIM: {:.4f}'.format(it, ds, np.mean(results[ds][:, 0]), np.mean(results[ds][:, 1])))
+    return results
+
+
 def build_parser():
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     # the flags sr/3_finetune_lut.py reads from TrainOptions (common/option.py:15-29,160-187)
@@ -327,6 +590,15 @@ def build_parser():
     p.add_argument('--valEngine', default=False, action='store_true',
                    help='also score the current tables on the inference engine (the deployed path) at every validation point and '
                         'after the last iteration')
+    p.add_argument('--valResident', default=False, action='store_true',
+                   help='validate from a device-resident set (DeviceValSet): decoded and uploaded once per run, scored in one call per '
+                        'dataset, PNGs written behind the loop -- the same log lines, numbers and files as without it')
+    p.add_argument('--valSave', choices=['every', 'last', 'never'], default='every',
+                   help='with --valResident: write the PNGs of every validation point, of the final one only, or none')
+    p.add_argument('--valWorkers', type=int, default=4, help='with --valResident: threads that encode the PNGs behind the loop')
+    p.add_argument('--valMaxBytes', type=int, default=None,
+                   help='with --valResident: device bytes the resident set may take (default: a quarter of the free device memory); '
+                        'a larger set is validated by the host loop')
     return p
 
 
@@ -367,6 +639,13 @@ class FinetuneRun:
             from .engine import MuLUTEngine
             self.engine = MuLUTEngine(next(self.net.parameters()).device.index).configure(opt.stages, opt.modes, opt.scale, opt.interval)
             opt.valEngineResults = {}              # {dataset: [images, 2]} of the last engine validation, for callers
+        self.vset = None
+        if getattr(opt, "valResident", False) and os.path.isdir(getattr(opt, "valDir", "")) and (getattr(opt, "valStep", 0) or self.engine is not None):
+            limit = getattr(opt, "valMaxBytes", None)
+            try:      # resident for the whole run: at most a quarter of what is free now
+                self.vset = DeviceValSet(opt, max_bytes=torch.cuda.mem_get_info()[0] // 4 if limit is None else limit, workers=getattr(opt, "valWorkers", 4))
+            except ValidationSetTooLarge as e:
+                log("{} | validation set of {} bytes exceeds the {} allowed on the device: validation runs on the host loop".format(opt.expDir, e.nbytes, e.limit))
         # the loop never waits for the device per step: every loss goes into this vector, read at the display points and at the end
         self.loss_buf = torch.zeros(opt.totalIter, dtype=torch.float32, device="cuda")
         self.losses, self.t_mark, self.i = [], time.time(), 0
@@ -392,19 +671,32 @@ class FinetuneRun:
             self.t_mark = time.time()
         if getattr(opt, "valStep", 0) and (i % opt.valStep == 0 or i == 1) and os.path.isdir(getattr(opt, "valDir", "")):   # :152-158
             t_val = time.time()
-            valid_steps(net, opt, i, log)
+            if self.vset is not None:
+                resident_valid_steps(net, self.vset, opt, i, log)
+            else:
+                valid_steps(net, opt, i, log)
             if self.engine is not None:
-                opt.valEngineResults, self.engine_at = engine_valid_steps(net, self.engine, opt, i, log), i
+                opt.valEngineResults, self.engine_at = self._engine_valid(i), i
             self.t_mark += time.time() - t_val
 
+    def _engine_valid(self, it):
+        if self.vset is not None:
+            return resident_engine_valid_steps(self.net, self.engine, self.vset, self.opt, it, self.log)
+        return engine_valid_steps(self.net, self.engine, self.opt, it, self.log)
+
     def finish(self):
-        """The last read-back, the engine's score of the tables as they are exported, the export (:162-171).  Returns the losses."""
+        """The last read-back, the engine's score of the tables as they are exported, the export (:162-171); with --valResident every
+        PNG is on disk when this returns, and a write that failed is raised here.  Returns the losses."""
         opt, log, net, data, losses = self.opt, self.log, self.net, self.data, self.losses
         losses.extend(self.loss_buf[len(losses):self.i].tolist())
-        if self.engine is not None:
-            if self.engine_at != opt.totalIter and os.path.isdir(getattr(opt, "valDir", "")):      # the tables as they are exported below
-                opt.valEngineResults = engine_valid_steps(net, self.engine, opt, opt.totalIter, log)
-            self.engine.close()
+        try:
+            if self.engine is not None:
+                if self.engine_at != opt.totalIter and os.path.isdir(getattr(opt, "valDir", "")):      # the tables as they are exported below
+                    opt.valEngineResults = self._engine_valid(opt.totalIter)
+                self.engine.close()
+        finally:
+            if self.vset is not None:
+                self.vset.close()
         if isinstance(data, DeviceCropProvider) and int(data.bad.item()):
             raise RuntimeError("mulut_ft_crop_batch refused %d samples" % int(data.bad.item()))
         for key, table in net.export_int8().items():                          # :162-169
