@@ -1004,6 +1004,20 @@ MULUT_HD uint32_t fix2_rotr(uint32_t x, uint32_t s) {      // s in {0, 16}
 MULUT_HD constexpr int fix2_partner(int p) { return 12 + (p >> 2) - 4 * (p & 3); }
 MULUT_HD constexpr int fix2_field_half(int set, int E) { return set * 16 + ((E & 1) * 4 + (E >> 2)) * 2 + ((E >> 1) & 1); }
 
+// Which listed samples need the full tables at all.  The tube kernels list a sample when a pass has key MSBs that span more than one step,
+// because an incremented vertex may then span three and lie outside the band.  That test is wider than the band walk needs: the vertices
+// with a non-zero weight are floor((x_i + s) / 16) per pixel value x_i for one shift s = 0 .. 16 each, so when the four VALUES of a pass
+// lie within kFix2Reach = 32 levels every such vertex spans at most two steps -- it is a row of the band, at its true slot (tube_slot is
+// the kernels' address arithmetic and injective on those rows).  The sample's bytes, which a tube kernel computes and stores for every
+// lane, flagged or not, are then exact already.  The bound is tight: at a range of 33 some shift gives a span of three
+// (tests/test_fix2_skip_cpu.py enumerates both).  A pass is "far" when the bound does not cover it.
+constexpr int kFix2Reach = 32;
+MULUT_HD constexpr bool fix2_pass_far(int va, int v0, int v1, int v2) {
+    const int mx = (va > v0 ? va : v0) > (v1 > v2 ? v1 : v2) ? (va > v0 ? va : v0) : (v1 > v2 ? v1 : v2);
+    const int mn = (va < v0 ? va : v0) < (v1 < v2 ? v1 : v2) ? (va < v0 ? va : v0) : (v1 < v2 ? v1 : v2);
+    return mx - mn > kFix2Reach;
+}
+
 // Entry decode: id = (n H + y) W + x < 2^30 without the division sequence.  For a divisor d >= 2 with 2^f <= d < 2^(f+1) take
 // s = f - 1 and magic = ceil(2^(32+s) / d) <= 2^31; the error e = magic d - 2^(32+s) is below d, and floor(id / d) ==
 // (id * magic) >> (32 + s) for every id with e * id < 2^(32+s) (Granlund-Montgomery), which `exact` states for id < 2^30.

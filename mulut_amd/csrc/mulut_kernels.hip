@@ -737,6 +737,8 @@ __device__ __forceinline__ void fix2_any_modes(const StageArgs &a, int (&s_sum)[
 // Rows are summed as packed 16-bit pairs and the group's LDS sums are the two sets of RotAcc<4> (mulut_core.h fix2_*): eight
 // ds_add_u32 per pass at lane-constant addresses, no selection by rotation.  The entry is decoded with reciprocals made once, its
 // clamps are taken once per entry, and pixel offsets inside a plane are 32-bit (the caller has checked that they fit).
+// The first trip (the anchor and the pass's three neighbours) also decides whether the entry needs the second at all: most entries of a
+// tube kernel on natural content hold the exact bytes already (see the skip inside the channel loop).
 __device__ __forceinline__ void fix2_four_modes(const StageArgs &a, int (&s_sum)[16][16]) {
     const uint32_t count = *a.fix_count;
     const int grp = (int)(threadIdx.x >> 4), ln = (int)(threadIdx.x & 15);
@@ -780,11 +782,20 @@ __device__ __forceinline__ void fix2_four_modes(const StageArgs &a, int (&s_sum)
         });
         uint8_t *out = const_cast<uint8_t *>(view_addr(a.out, n, c_lo, y * 4 + (ln >> 2), x * 4 + (ln & 3)));
         for (int c = c_lo; c < c_hi; ++c, pa += a.in.sC, pk[0] += a.in.sC, pk[1] += a.in.sC, pk[2] += a.in.sC, out += a.out.sC) {
+            const int va = (int)*pa;
+            int v0 = va, v1 = va, v2 = va;
+            if (act) { v0 = (int)*pk[0]; v1 = (int)*pk[1]; v2 = (int)*pk[2]; }
+            // An entry that names ONE channel (only < 3) was listed by a tube kernel (stage_tube_kernel, stage_tube2_kernel: they list
+            // nothing else), which has stored the sample's bytes from its band whether it flagged the sample or not.  When no pass of the
+            // sample is far (mulut_core.h fix2_pass_far, on the pixels and clamps the tube kernel read) those bytes are the result: no
+            // rows, no sums, no store.  An entry that names every channel (only == 3, whatever the launch's channel count) is a border
+            // column of the slab path, which nothing has computed yet: never skipped.  The group's sixteen lanes are one quarter of
+            // the wave's ballot.
+            const uint32_t far = (uint32_t)(__ballot(fix2_pass_far(va, v0, v1, v2)) >> (threadIdx.x & 48u)) & 0xFFFFu;
+            if (only != 3u && far == 0u) continue;      // group-uniform
             sum[ln] = 0;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            const int va = (int)*pa;
             if (act) {
-                const int v0 = (int)*pk[0], v1 = (int)*pk[1], v2 = (int)*pk[2];
                 int idx[5], w[5];
                 simplex4(va, v0, v1, v2, idx, w);
                 uint32_t row[5][4];

@@ -44,17 +44,44 @@ def flat_share(h, left, right, tw=16, th=4, halo=2):
     return round(flat / total, 5)
 
 
+def fix2_skip_share(x):
+    """Of the samples of x (uint8 HWC) the tube kernels list (a pass whose four key MSBs span more than one step), how many have all
+    twelve passes within 32 levels in their pixel VALUES (mulut_core.h fix2_pass_far): stage_up_fix2_kernel leaves those alone.  Same
+    clamps as the kernels on a whole frame: rows and columns replicated at the frame's edges."""
+    v, h = x.astype(np.int16), (x >> 4).astype(np.int16)
+    flagged, far = np.zeros(x.shape, bool), np.zeros(x.shape, bool)
+    for m in "sdy":
+        for r in range(4):
+            offs = [rot(r, di, dj) for di, dj in PAT[m]]
+            hs, vs = [h] + [shifted(h, *o) for o in offs], [v] + [shifted(v, *o) for o in offs]
+            flagged |= (np.maximum.reduce(hs) - np.minimum.reduce(hs)) > 1
+            far |= (np.maximum.reduce(vs) - np.minimum.reduce(vs)) > 32
+    return {"samples": int(x.size), "flagged": int(flagged.sum()), "flagged_and_skippable": int((flagged & ~far).sum()),
+            "far_but_not_flagged": int((far & ~flagged).sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dist", default="real")
     ap.add_argument("--h", type=int, default=1080)
     ap.add_argument("--w", type=int, default=1920)
     ap.add_argument("--stage", type=int, default=2, help="2: statistics of the final stage's input (= first-stage output); 1: of the first stage's input")
+    ap.add_argument("--skip-draws", type=int, default=0, help="K > 0: only the fix-up kernel's skippable share of the final stage's input, over draws 0 .. K - 1")
     a = ap.parse_args()
     png = os.path.join(ROOT, "tests", "golden", "DIV2K_LR_X4", "0001x4.png")
-    img = {"real": lambda: real_frames(1, a.h, a.w, png, 0), "natural": lambda: natural_frames(1, a.h, a.w, 3, 0),
-           "noise": lambda: noise_frames(1, a.h, a.w, 3, 0)}[a.dist]()[0]
+    frames = {"real": lambda n: real_frames(n, a.h, a.w, png, 0), "natural": lambda n: natural_frames(n, a.h, a.w, 3, 0),
+              "noise": lambda n: noise_frames(n, a.h, a.w, 3, 0)}[a.dist]
     luts = load_lut_dict(os.path.join(ROOT, "tests", "golden", "luts"), 2, "sdy", 4, 4, "LUT_ft")
+    if a.skip_draws > 0:
+        per = [fix2_skip_share(c_oracle.stage([luts["s1_%s" % m] for m in "sdy"], "sdy", False, f, 1)) for f in frames(a.skip_draws)]
+        tot = {k: sum(p[k] for p in per) for k in per[0]}
+        print(json.dumps({"dist": a.dist, "stage_input": 2, "frame": [a.h, a.w, 3], "draws": a.skip_draws,
+                          "rule": "flagged: a pass with key MSBs spanning more than one step; skippable: every pass within 32 levels",
+                          "flagged_share_of_samples": round(tot["flagged"] / tot["samples"], 5),
+                          "skippable_share_of_flagged": round(tot["flagged_and_skippable"] / max(tot["flagged"], 1), 5),
+                          "total": tot, "per_draw": per}, indent=1))
+        return
+    img = frames(1)[0]
     x = img if a.stage == 1 else c_oracle.stage([luts["s1_%s" % m] for m in "sdy"], "sdy", False, img, 1)
     h = (x >> 4).astype(np.int8)        # HWC MSBs
     H, W, C = h.shape
