@@ -127,6 +127,16 @@ def build(force=False, verbose=False):
     return LIB_PATH
 
 
+def check(rc, error=None):
+    """The test of a return code of the C ABI (MuLUTEngine._check apart, which adds its context's HIP error text): a negative one
+    raises RuntimeError with mulut_strerror's text -- or `error`, a class, with MuLUTError's "mulut error {rc}: {text}" -- and
+    anything else is handed back (some calls return a count)."""
+    if rc < 0:
+        text = load().mulut_strerror(rc).decode()
+        raise RuntimeError(text) if error is None else error("mulut error %d: %s" % (rc, text))
+    return rc
+
+
 def load(path=None):
     """Return the ctypes handle; builds the library first if its sources are newer.
     `path` (or $MULUT_LIB) selects another build of the same ABI, e.g. an A/B kernel variant."""

@@ -18,6 +18,30 @@ class MuLUTError(RuntimeError):
     pass
 
 
+def _dev_u8(t, name):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous()):
+        raise TypeError("%s must be a contiguous uint8 CUDA tensor" % name)
+    return t
+
+
+def eval_y(gt_hwc, out_hwc, shave, lib=None):
+    """(PSNR, SSIM) on the Y channel of two device uint8 HWC RGB images, as sr/4_test_lut.py:313-315 scores a result
+    (common/utils.py:42-101) -- computed on the device, on its current stream; only two doubles come back.
+    `lib`: another build of the library than the default one (MuLUTEngine passes its own)."""
+    gt, out = _dev_u8(gt_hwc, "gt"), _dev_u8(out_hwc, "out")
+    if gt.dim() != 3 or gt.shape[2] != 3 or gt.shape != out.shape or gt.device != out.device:
+        raise ValueError("eval_y wants two HWC RGB images of one shape, got %s and %s" % (tuple(gt.shape), tuple(out.shape)))
+    lib = lib or _native.load()
+    H, W = int(gt.shape[0]), int(gt.shape[1])
+    n = int(lib.mulut_eval_ws_doubles(H, W))
+    ws = torch.empty(n, dtype=torch.float64, device=gt.device)
+    psnr, ssim = ctypes.c_double(), ctypes.c_double()
+    _native.check(lib.mulut_eval_y(gt.device.index, gt.data_ptr(), out.data_ptr(), H, W, int(shave), ws.data_ptr(), n,
+                                   ctypes.byref(psnr), ctypes.byref(ssim), ctypes.c_void_p(torch.cuda.current_stream(gt.device).cuda_stream)),
+                  MuLUTError)
+    return psnr.value, ssim.value
+
+
 class MuLUTEngine:
     """Owns a ``mulut_ctx``.  Mirrors what the reference keeps in ``opt`` + ``lutDict``
     (sr/4_test_lut.py:320-333) and runs its stage loop (:279-306) on the GPU."""
@@ -62,8 +86,7 @@ class MuLUTEngine:
             self._check(-8)
 
     def _dev_u8(self, t, name):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous()):
-            raise TypeError("%s must be a contiguous uint8 CUDA tensor" % name)
+        _dev_u8(t, name)
         if t.device != self.device:
             raise ValueError("%s lives on %s, engine on %s" % (name, t.device, self.device))
         return t
@@ -236,19 +259,8 @@ class MuLUTEngine:
         return [int(buf[k]) for k in range(n)]
 
     def eval_y(self, gt_hwc, out_hwc, shave):
-        """(PSNR, SSIM) on the Y channel of two device uint8 HWC RGB images, as sr/4_test_lut.py:313-315 scores a result
-        (common/utils.py:42-101) -- computed on the device, only two doubles come back."""
-        gt = self._dev_u8(gt_hwc, "gt")
-        out = self._dev_u8(out_hwc, "out")
-        if gt.dim() != 3 or gt.shape[2] != 3 or gt.shape != out.shape:
-            raise ValueError("eval_y wants two HWC RGB images of one shape, got %s and %s" % (tuple(gt.shape), tuple(out.shape)))
-        H, W = int(gt.shape[0]), int(gt.shape[1])
-        n = int(self._lib.mulut_eval_ws_doubles(H, W))
-        ws = torch.empty(n, dtype=torch.float64, device=gt.device)
-        psnr, ssim = ctypes.c_double(), ctypes.c_double()
-        self._check(self._lib.mulut_eval_y(self.device.index, gt.data_ptr(), out.data_ptr(), H, W, int(shave), ws.data_ptr(), n,
-                                           ctypes.byref(psnr), ctypes.byref(ssim), self._stream()))
-        return psnr.value, ssim.value
+        """The module's eval_y on two images of this engine's device."""
+        return eval_y(self._dev_u8(gt_hwc, "gt"), self._dev_u8(out_hwc, "out"), shave, self._lib)
 
     def set_tuning(self, key, value):
         """Performance knobs that never change results, e.g. ("final_stage_kernel", 1)."""

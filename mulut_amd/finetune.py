@@ -45,9 +45,7 @@ class _StageFn(torch.autograd.Function):
             raise ValueError("the tables of a stage must be float32 of one shape")
         wq_all = torch.empty((len(ws), n), dtype=torch.float32, device=x.device)
         wq = [wq_all[m].view(w.shape) for m, w in enumerate(ws)]
-        rc = lib.mulut_ft_quantize(x.device.index, _ptr_array(ws), _ptr_array(wq), len(ws), n, stream)
-        if rc:
-            raise RuntimeError(lib.mulut_strerror(rc).decode())
+        _native.check(lib.mulut_ft_quantize(x.device.index, _ptr_array(ws), _ptr_array(wq), len(ws), n, stream))
         B, C, H, W = x.shape
         out = torch.empty((B, C, H * u, W * u), dtype=torch.float32, device=x.device)
         # where the stage's clamp passes gradient, 16 bits per site: saves the backward a recomputation of the stage forward
@@ -55,8 +53,9 @@ class _StageFn(torch.autograd.Function):
         # any list over s, d, y, e, h, o at interval 4, 5 or 6: for a list of s, d, y the launches of the narrow entry points
         rc = lib.mulut_ft_wide_stage_forward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
                                              x.data_ptr(), B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
-        if rc:
-            raise (ValueError if rc == -2 else RuntimeError)(lib.mulut_strerror(rc).decode())
+        if rc == -2:      # MULUT_EMODE: the reference's ValueError("Mode {} not implemented.")
+            raise ValueError(lib.mulut_strerror(rc).decode())
+        _native.check(rc)
         ctx.save_for_backward(x, wq_all, inside, *ws)
         ctx.cfg = (modes, is_last, u, interval)
         return out
@@ -73,15 +72,11 @@ class _StageFn(torch.autograd.Function):
         gwq = [g_all[m].view(w.shape) for m, w in enumerate(ws)]
         gx = torch.zeros_like(x)
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        rc = lib.mulut_ft_wide_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
-                                              x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
-                                              gx.data_ptr(), stream)
-        if rc:
-            raise RuntimeError(lib.mulut_strerror(rc).decode())
+        _native.check(lib.mulut_ft_wide_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                                       x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
+                                                       gx.data_ptr(), stream))
         # backward of clamp(round_func(w*127)): round is identity (BPDA), clamp passes inside [-127,127], x127 -- in place, one launch
-        rc = lib.mulut_ft_quantize_backward(x.device.index, _ptr_array(ws), _ptr_array(gwq), len(ws), ws[0].numel(), stream)
-        if rc:
-            raise RuntimeError(lib.mulut_strerror(rc).decode())
+        _native.check(lib.mulut_ft_quantize_backward(x.device.index, _ptr_array(ws), _ptr_array(gwq), len(ws), ws[0].numel(), stream))
         return (gx, None, None, None, None) + tuple(gwq)
 
 
@@ -212,10 +207,8 @@ class Adam(torch.optim.Optimizer):
             for (device, step), ps in by_step.items():
                 grads = [p.grad.contiguous() for p in ps]
                 n = (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps])
-                rc = lib.mulut_ft_adam(device.index, _ptr_array(ps), _ptr_array(grads), _ptr_array([self.state[p]["exp_avg"] for p in ps]),
-                                       _ptr_array([self.state[p]["exp_avg_sq"] for p in ps]), n, len(ps), step, float(group["lr"]),
-                                       group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"],
-                                       ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-                if rc:
-                    raise RuntimeError(lib.mulut_strerror(rc).decode())
+                _native.check(lib.mulut_ft_adam(device.index, _ptr_array(ps), _ptr_array(grads), _ptr_array([self.state[p]["exp_avg"] for p in ps]),
+                                                _ptr_array([self.state[p]["exp_avg_sq"] for p in ps]), n, len(ps), step, float(group["lr"]),
+                                                group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"],
+                                                ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
         return loss

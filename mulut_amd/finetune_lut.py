@@ -36,529 +36,22 @@ stream-ordered call, the sums of all datasets are read back once, and the PNGs a
 ``--valWorkers`` threads (``ValWriter``) behind the loop.  ``--valSave every|last|never`` picks the points whose files are written.
 ``resident_engine_valid_steps`` does the same for ``--valEngine``.  The log lines, ``opt.valResults`` and the files are those of the host
 loops, bit for bit; a set above a quarter of the free device memory falls back to ``valid_steps`` with one log line.
+The providers, their scan and their draw are defined in ``mulut_amd.ft_data``, everything named above that validates in
+``mulut_amd.ft_val``; this module is the parser and the loop, and carries those names as its own.
 """
 import argparse
-import ctypes
 import math
 import os
-import random
 import time
 
 import numpy as np
 import torch
 import torch.nn.functional as F
-from PIL import Image
 
 from .finetune import Adam, MuLUT, MuLUTInterval, MuLUTWide
-
-
-class _PendingLR:
-    """An LR image that DeviceCropProvider will have the resample kernel write straight into its pool slot: only its shape."""
-    dtype = np.dtype(np.uint8)
-
-    def __init__(self, shape):
-        self.shape, self.size = tuple(shape), int(np.prod(shape))
-
-
-class CropProvider:
-    """Random (LR crop, HR crop) batches, one colour channel each, flips + rot90 as sr/data.py:96-124."""
-
-    def __init__(self, path, scale, patch, batch, seed=None, make_lr=False, log=print, _defer=False):
-        self.scale, self.sz, self.batch = scale, patch, batch
-        self.rng = random.Random(seed)
-        hr_dir = os.path.join(path, "HR")
-        self.pairs = []
-        for fn in sorted(os.listdir(hr_dir)):
-            stem = fn[:-4]
-            for lr in (os.path.join(path, "LR", "X%d" % scale, "%sx%d.png" % (stem, scale)),
-                       os.path.join(path, "LR_bicubic", "X%d" % scale, fn)):
-                if os.path.exists(lr):
-                    hr_im = np.array(Image.open(os.path.join(hr_dir, fn)))
-                    lr_im = np.array(Image.open(lr))
-                    if hr_im.ndim == 2:
-                        hr_im, lr_im = hr_im[:, :, None], lr_im[:, :, None]
-                    if min(lr_im.shape[:2]) >= patch:
-                        self.pairs.append((lr_im, hr_im))
-                    break
-            else:
-                if make_lr:      # no LR twin on disk: the (w // s, h // s) bicubic image of sr/Test_dataset.py:24-25, no modcrop
-                    self._make_pair(Image.open(os.path.join(hr_dir, fn)), fn, patch, log, _defer)
-        if not self.pairs:
-            raise FileNotFoundError("no HR/LR training pairs with LR >= %d px under %s" % (patch, path))
-
-    def _make_pair(self, img, fn, patch, log, defer):
-        from .resample import bicubic, resize_image
-        s = self.scale
-        h, w = img.height // s, img.width // s
-        if min(h, w) < max(patch, 1):
-            return
-        hr_im = np.array(img)
-        if img.mode in ("L", "RGB"):
-            if hr_im.ndim == 2:
-                hr_im = hr_im[:, :, None]
-            lr_im = _PendingLR((h, w, hr_im.shape[2])) if defer else bicubic(hr_im, (h, w))
-        else:                                  # Pillow on the host, one log line
-            lr_im = np.array(resize_image(img, (w, h), log, fn))
-            if hr_im.ndim == 2:
-                hr_im, lr_im = hr_im[:, :, None], lr_im[:, :, None]
-        self.pairs.append((lr_im, hr_im))
-
-    def materialise(self):
-        """Make the LR images a deferring scan left pending (on the device, copied back)."""
-        from .resample import bicubic
-        self.pairs = [(bicubic(hr_im, lr_im.shape[:2]) if isinstance(lr_im, _PendingLR) else lr_im, hr_im) for lr_im, hr_im in self.pairs]
-
-    def next(self):
-        ims, lbs = [], []
-        for _ in range(self.batch):
-            im, lb = self.rng.choice(self.pairs)
-            i = self.rng.randint(0, im.shape[0] - self.sz)
-            j = self.rng.randint(0, im.shape[1] - self.sz)
-            c = self.rng.randrange(im.shape[2])
-            s = self.scale
-            lb = lb[i * s:(i + self.sz) * s, j * s:(j + self.sz) * s, c]
-            im = im[i:i + self.sz, j:j + self.sz, c]
-            if self.rng.uniform(0, 1) < 0.5:
-                lb, im = np.fliplr(lb), np.fliplr(im)
-            if self.rng.uniform(0, 1) < 0.5:
-                lb, im = np.flipud(lb), np.flipud(im)
-            k = self.rng.choice([0, 1, 2, 3])
-            lbs.append(np.rot90(lb, k).astype(np.float32)[None] / 255.0)
-            ims.append(np.rot90(im, k).astype(np.float32)[None] / 255.0)
-        return torch.from_numpy(np.stack(ims)).cuda(), torch.from_numpy(np.stack(lbs)).cuda()
-
-
-class TrainingSetTooLarge(Exception):
-    """The packed training set is larger than the caller allows on the device; ``host`` is the loaded CropProvider (same seed, no
-    draw taken yet) to go on with."""
-
-    def __init__(self, nbytes, limit, host):
-        super().__init__("training set of %d bytes exceeds the %d allowed on the device" % (nbytes, limit))
-        self.nbytes, self.limit, self.host = nbytes, limit, host
-
-
-class DeviceCropProvider:
-    """CropProvider's batches, bit for bit for the same seed, cut on the device (mulut_ft_crop_batch): the pairs CropProvider accepts,
-    in its order, lie in one uint8 device tensor as the PNGs decode; next() draws pair, i, j, c, the two flips and k per sample from
-    random.Random(seed) in CropProvider's order, sends those B x 6 integers through a ring of pinned buffers and launches once on
-    the current stream.  next() never waits for the device unless the host is RING batches ahead of it: a slot's event, recorded
-    behind its copy, is waited for before the slot is rewritten."""
-    RING = 32
-
-    def __init__(self, path, scale, patch, batch, seed=None, max_bytes=None, make_lr=False, log=print):
-        host = CropProvider(path, scale, patch, batch, seed, make_lr, log, _defer=True)      # the same scan: the same pairs in the same order
-        self.scale, self.sz, self.batch = scale, patch, batch
-        self.rng = host.rng
-        table, off = np.zeros((len(host.pairs), 10), np.int32), 0
-        t64 = table.view(np.int64)                                 # mulut_ft_pair: two 64-bit offsets, then lr_h, lr_w, hr_h, hr_w, ch, pad
-        for n, (lr_im, hr_im) in enumerate(host.pairs):
-            if lr_im.dtype != np.uint8 or hr_im.dtype != np.uint8 or lr_im.shape[2] != hr_im.shape[2]:
-                raise ValueError("pair %d is not a pair of 8-bit images with the same channels (--hostData takes it)" % n)
-            t64[n, 0], t64[n, 1] = off, off + lr_im.size
-            table[n, 4:9] = lr_im.shape[0], lr_im.shape[1], hr_im.shape[0], hr_im.shape[1], lr_im.shape[2]
-            off += lr_im.size + hr_im.size
-        self.pool_bytes = off
-        if max_bytes is not None and off > max_bytes:
-            host.materialise()
-            raise TrainingSetTooLarge(off, max_bytes, host)
-        self.shapes = [im.shape for im, _ in host.pairs]           # (lr_h, lr_w, ch) per pair: all the draws need
-        self.device = torch.empty(0).cuda().device
-        self.pool = torch.empty(off, dtype=torch.uint8, device=self.device)
-        for n, (lr_im, hr_im) in enumerate(host.pairs):            # image by image: no second copy of the set on the host
-            a = int(t64[n, 0])
-            hr_slot = self.pool[a + lr_im.size:a + lr_im.size + hr_im.size]
-            hr_slot.copy_(torch.from_numpy(np.ascontiguousarray(hr_im).reshape(-1)))
-            if isinstance(lr_im, _PendingLR):                      # --makeLR: the kernel writes the pair's LR slot from its HR slot
-                from .resample import bicubic
-                bicubic(hr_slot.view(hr_im.shape), lr_im.shape[:2], out=self.pool[a:a + lr_im.size])
-            else:
-                self.pool[a:a + lr_im.size].copy_(torch.from_numpy(np.ascontiguousarray(lr_im).reshape(-1)))
-        self.table = torch.from_numpy(table).cuda()
-        self.bad = torch.zeros(1, dtype=torch.int32).cuda()         # samples the kernel refused: stays 0 (the draws are legal by construction)
-        if self.pool.is_cuda:
-            torch.cuda.synchronize(self.device)                    # the set is in place whatever stream next() is called on
-        self._ring, self._events, self._slot, self._lib = None, None, 0, None
-
-    def draw(self, out=None):
-        """The host half of next(): the batch's draws as int32 [B][6] = pair, i, j, c, flips (bit 0 lr, bit 1 ud), k."""
-        out = np.empty((self.batch, 6), np.int32) if out is None else out
-        rng, sz, shapes, pairs, ks, rows = self.rng, self.sz, self.shapes, range(len(self.shapes)), [0, 1, 2, 3], []
-        for _ in range(self.batch):
-            n = rng.choice(pairs)
-            h, w, ch = shapes[n]
-            i = rng.randint(0, h - sz)
-            j = rng.randint(0, w - sz)
-            c = rng.randrange(ch)
-            lr = rng.uniform(0, 1) < 0.5
-            ud = rng.uniform(0, 1) < 0.5
-            rows.append((n, i, j, c, lr + 2 * ud, rng.choice(ks)))
-        out[:] = rows
-        return out
-
-    def next(self):
-        if self._ring is None:
-            from . import _native
-            self._lib = _native.load()
-            self._ring = [torch.empty((self.batch, 6), dtype=torch.int32).pin_memory() for _ in range(self.RING)]
-            self._events = [None] * self.RING
-        slot, self._slot = self._slot, (self._slot + 1) % self.RING
-        if self._events[slot] is not None:
-            self._events[slot].synchronize()                       # (returns at once unless the host is RING batches ahead)
-        else:
-            self._events[slot] = torch.cuda.Event()
-        self.draw(self._ring[slot].numpy())
-        stream = torch.cuda.current_stream(self.device)
-        draws = self._ring[slot].to(self.device, non_blocking=True)
-        self._events[slot].record(stream)
-        im = torch.empty((self.batch, 1, self.sz, self.sz), dtype=torch.float32, device=self.device)
-        lb = torch.empty((self.batch, 1, self.sz * self.scale, self.sz * self.scale), dtype=torch.float32, device=self.device)
-        rc = self._lib.mulut_ft_crop_batch(self.device.index, self.pool.data_ptr(), self.pool_bytes, self.table.data_ptr(), len(self.shapes),
-                                           draws.data_ptr(), self.batch, self.sz, self.scale, im.data_ptr(), lb.data_ptr(),
-                                           self.bad.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
-        if rc:
-            raise RuntimeError(self._lib.mulut_strerror(rc).decode())
-        return im, lb
-
-
-def valid_steps(net, opt, it, log=print):
-    """Twin of sr/3_finetune_lut.py:23-65: datasets under {valDir}/{dataset}/HR with LR_bicubic/X{scale}; a dataset that is
-    not on disk is skipped (the reference's Provider would have failed at start-up instead)."""
-    from . import _native
-    from .metrics import modcrop
-    lib = _native.load()
-    datasets = _val_datasets(opt)
-    was_training = net.training
-    net.eval()
-    results, per_image = {}, {}
-    with torch.no_grad():
-        for ds in datasets:
-            hr_dir = os.path.join(opt.valDir, ds, "HR")
-            if not os.path.isdir(hr_dir):
-                continue
-            out_dir = os.path.join(opt.valoutDir, ds)
-            os.makedirs(out_dir, exist_ok=True)
-            psnrs, ssims = [], []
-            for fn in sorted(os.listdir(hr_dir)):
-                lb = np.array(Image.open(os.path.join(hr_dir, fn)))
-                im = np.array(Image.open(os.path.join(opt.valDir, ds, "LR_bicubic", "X%d" % opt.scale, fn)))
-                lb = modcrop(lb, opt.scale)                        # sr/data.py:144: rows and columns beyond a multiple of the scale are dropped
-                if lb.ndim == 2:                                   # a grey HR and a grey LR are replicated to three channels, each on
-                    lb = np.stack([lb] * 3, 2)                     # its own (sr/data.py:145-158)
-                if im.ndim == 2:
-                    im = np.stack([im] * 3, 2)
-                if (im.shape[0] * opt.scale, im.shape[1] * opt.scale) != lb.shape[:2] or im.shape[2] != 3 or lb.shape[2] != 3:      # :163-166
-                    raise ValueError("{}/{}: LR {} x scale {} is not the modcropped HR {}".format(ds, fn, im.shape, opt.scale, lb.shape))
-                x = torch.from_numpy(np.ascontiguousarray(im.transpose(2, 0, 1)[None]).astype(np.float32) / 255.0).cuda()
-                pred = net(x) * 255.0
-                pred_u8 = torch.round(torch.clamp(pred[0].permute(1, 2, 0), 0, 255)).to(torch.uint8).contiguous()
-                H, W = pred_u8.shape[:2]
-                gt = torch.from_numpy(np.ascontiguousarray(lb)).cuda()
-                n = int(lib.mulut_eval_ws_doubles(H, W))
-                ws = torch.empty(n, dtype=torch.float64, device="cuda")
-                ps, ss = ctypes.c_double(), ctypes.c_double()
-                rc = lib.mulut_eval_y(pred_u8.device.index, gt.data_ptr(), pred_u8.data_ptr(), H, W, int(opt.scale), ws.data_ptr(), n,
-                                      ctypes.byref(ps), ctypes.byref(ss),
-                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-                if rc:
-                    raise RuntimeError(lib.mulut_strerror(rc).decode())
-                psnrs.append(ps.value)
-                ssims.append(ss.value)
-                # the reference names the file after the LAST '_'-separated token of "{dataset}_{stem}" (sr/3_finetune_lut.py:41,61):
-                # Urban100's img_001.png becomes 001_lutft.png -- kept, a drop-in writes the same names
-                Image.fromarray(pred_u8.cpu().numpy()).save(os.path.join(out_dir, '{}_lutft.png'.format((ds + '_' + fn[:-4]).split('_')[-1])))
-            if psnrs:
-                results[ds] = (float(np.mean(psnrs)), float(np.mean(ssims)))
-                per_image[ds] = np.stack([psnrs, ssims], 1)
-                log('Iter {} | Dataset {} | AVG PSNR: {:02f}, AVG: SSIM: {:04f}'.format(it, ds, results[ds][0], results[ds][1]))
-    net.train(was_training)
-    opt.valResults = per_image      # {dataset: float64 array [images, 2]} of this validation, as opt.valEngineResults for the engine's
-    return results
-
-
-def _val_datasets(opt):
-    return ['Set5', 'Set14'] if opt.debug else ['Set5', 'Set14', 'B100', 'Urban100', 'Manga109']
-
-
-def engine_valid_steps(net, engine, opt, it, log=print):
-    """The validation sets on the deployed path: the module's current parameters installed into `engine` (install_into), then sr/4_test_lut.py's loop per dataset (:257-317: LR through the cascade, ground truth
-    modcropped, grey replicated, Y-PSNR / SSIM) with the test script's summary line behind the iteration.  Returns
-    {dataset: float64 array [images, 2]} -- what ``mulut_amd.test_lut`` with device metrics returns for the tables exported now."""
-    from .metrics import modcrop
-    net.install_into(engine)
-    results = {}
-    for ds in _val_datasets(opt):
-        hr_dir = os.path.join(opt.valDir, ds, "HR")
-        if not os.path.isdir(hr_dir):
-            continue
-        scores = []
-        for fn in sorted(os.listdir(hr_dir)):
-            im = np.array(Image.open(os.path.join(opt.valDir, ds, "LR_bicubic", "X%d" % opt.scale, fn)))
-            gt = modcrop(np.array(Image.open(os.path.join(hr_dir, fn))), opt.scale)
-            if im.ndim == 2:
-                im = np.stack([im] * 3, axis=2)
-            if gt.ndim == 2:
-                gt = np.stack([gt] * 3, axis=2)
-            out = engine.pipeline(torch.from_numpy(np.ascontiguousarray(im)).to(engine.device))
-            scores.append(engine.eval_y(torch.from_numpy(np.ascontiguousarray(gt)).to(engine.device), out, opt.scale))
-        if scores:
-            results[ds] = np.asarray(scores)
-            log('Iter {} | Dataset {} | AVG LUT PSNR: {:.2f} SSIM: {:.4f}'.format(it, ds, np.mean(results[ds][:, 0]), np.mean(results[ds][:, 1])))
-    return results
-
-
-def val_png_name(ds, fn):
-    """The reference names a result after the LAST '_'-separated token of "{dataset}_{stem}" (sr/3_finetune_lut.py:41,61)."""
-    return '{}_lutft.png'.format((ds + '_' + fn[:-4]).split('_')[-1])
-
-
-class ValidationSetTooLarge(Exception):
-    """The resident validation set needs more device memory than the caller allows."""
-
-    def __init__(self, nbytes, limit):
-        super().__init__("validation set of %d bytes exceeds the %d allowed on the device" % (nbytes, limit))
-        self.nbytes, self.limit = nbytes, limit
-
-
-class ValWriter:
-    """The PNGs of a validation point, encoded behind the loop by a pool of `workers` threads (Pillow and zlib release the GIL).
-    submit() hands over one point's (path, array) list and returns without waiting for its files; it first joins the point before,
-    so the files of point k are complete before any file of point k + 1 is begun and at most one point is ever pending.  `ready`,
-    if given, is called once on a worker before the point's first file (the wait for the copy that fills the arrays).  A failed
-    write is raised by the next join() -- that of the next submit(), or the caller's last one -- not lost."""
-
-    def __init__(self, workers=4, encode=None):
-        from concurrent.futures import ThreadPoolExecutor
-        self._pool = ThreadPoolExecutor(max_workers=max(1, int(workers)), thread_name_prefix="valpng")
-        self._encode = encode or (lambda path, arr: Image.fromarray(arr).save(path))
-        self._pending = []
-
-    def submit(self, jobs, ready=None):
-        self.join()
-        gate = self._pool.submit(ready) if ready is not None else None
-
-        def one(path, arr):
-            if gate is not None:
-                gate.result()
-            self._encode(path, arr)
-        self._pending = ([gate] if gate is not None else []) + [self._pool.submit(one, path, arr) for path, arr in jobs]
-
-    def join(self):
-        pending, self._pending, first = self._pending, [], None
-        for f in pending:                      # every file is waited for, then the first failure is raised
-            try:
-                f.result()
-            except BaseException as e:         # noqa: B902
-                first = first or e
-        if first is not None:
-            raise first
-
-    def close(self):
-        try:
-            self.join()
-        finally:
-            self._pool.shutdown(wait=True)
-
-
-class DeviceValSet:
-    """The validation sets of valid_steps / engine_valid_steps, resident on the device for the whole run: built once from
-    {valDir}/{dataset}/HR and LR_bicubic/X{scale} with the checks and conversions valid_steps applies per image (modcrop, grey
-    replicated to three channels, the shape test and its error text).
-      gt_pool   uint8   every ground truth, HWC, back to back
-      out_pool  uint8   the same layout: image n's result goes where its ground truth lies in gt_pool
-      lr_pool   uint8   every LR image, HWC (what the engine takes)
-      lr_f32    float32 the same images as the module takes them, planar [1][3][h][w], the HOST's astype(float32) / 255.0 uploaded
-                        once (the device's division is a product with a rounded reciprocal: not the same float for every byte)
-      plans     one mulut_eval_plan per dataset over (gt_pool, out_pool); sums: device float64 [images][2], read back once per point
-    `max_bytes`: a set that needs more raises ValidationSetTooLarge before anything is allocated on the device."""
-
-    def __init__(self, opt, max_bytes=None, workers=4, encode=None):
-        from . import _native
-        from .metrics import modcrop
-        self.lib = _native.load()
-        self.scale = int(opt.scale)
-        self.sets, images, gt_bytes, lr_bytes = [], [], 0, 0
-        for ds in _val_datasets(opt):
-            hr_dir = os.path.join(opt.valDir, ds, "HR")
-            if not os.path.isdir(hr_dir):
-                continue
-            first, files = len(images), sorted(os.listdir(hr_dir))
-            for fn in files:
-                lb = np.array(Image.open(os.path.join(hr_dir, fn)))
-                im = np.array(Image.open(os.path.join(opt.valDir, ds, "LR_bicubic", "X%d" % opt.scale, fn)))
-                lb = modcrop(lb, opt.scale)
-                if lb.ndim == 2:
-                    lb = np.stack([lb] * 3, 2)
-                if im.ndim == 2:
-                    im = np.stack([im] * 3, 2)
-                if (im.shape[0] * opt.scale, im.shape[1] * opt.scale) != lb.shape[:2] or im.shape[2] != 3 or lb.shape[2] != 3:
-                    raise ValueError("{}/{}: LR {} x scale {} is not the modcropped HR {}".format(ds, fn, im.shape, opt.scale, lb.shape))
-                if lb.dtype != np.uint8 or im.dtype != np.uint8:
-                    raise ValueError("{}/{}: not a pair of 8-bit images".format(ds, fn))
-                images.append((np.ascontiguousarray(im), np.ascontiguousarray(lb), gt_bytes, lr_bytes))
-                gt_bytes, lr_bytes = gt_bytes + lb.size, lr_bytes + im.size
-            if files:
-                self.sets.append({"name": ds, "files": files, "first": first, "n": len(files), "out_dir": os.path.join(opt.valoutDir, ds)})
-        self.gt_bytes, self.lr_bytes = gt_bytes, lr_bytes
-        self.nbytes = 2 * gt_bytes + 5 * lr_bytes          # gt + out, LR bytes + LR floats
-        if max_bytes is not None and self.nbytes > max_bytes:
-            raise ValidationSetTooLarge(self.nbytes, max_bytes)
-        self.device = torch.empty(0).cuda().device
-        dev = self.device
-        self.gt_pool = torch.empty(gt_bytes, dtype=torch.uint8, device=dev)
-        self.out_pool = torch.zeros(gt_bytes, dtype=torch.uint8, device=dev)
-        self.lr_pool = torch.empty(lr_bytes, dtype=torch.uint8, device=dev)
-        self.lr_f32 = torch.empty(lr_bytes, dtype=torch.float32, device=dev)
-        self.shapes = []                                   # per image: (gt_off, H, W, lr_off, h, w)
-        for im, lb, g, l in images:                        # image by image
-            self.gt_pool[g:g + lb.size].copy_(torch.from_numpy(lb.reshape(-1)))
-            self.lr_pool[l:l + im.size].copy_(torch.from_numpy(im.reshape(-1)))
-            self.lr_f32[l:l + im.size].copy_(torch.from_numpy((np.ascontiguousarray(im.transpose(2, 0, 1)).astype(np.float32) / 255.0).reshape(-1)))
-            self.shapes.append((g, lb.shape[0], lb.shape[1], l, im.shape[0], im.shape[1]))
-        del images
-        self.sums = torch.zeros((len(self.shapes), 2), dtype=torch.float64, device=dev)
-        self.sums_host = torch.zeros((len(self.shapes), 2), dtype=torch.float64).pin_memory()
-        for s in self.sets:
-            items = np.zeros((s["n"], 5), np.int64)        # mulut_eval_item: gt_off, out_off, (H, W) as two int32, the two pool sizes
-            for k, (g, H, W, _, _, _) in enumerate(self.shapes[s["first"]:s["first"] + s["n"]]):
-                items[k, 0], items[k, 1], items[k, 3], items[k, 4] = g, g, gt_bytes, gt_bytes
-                items[k, 2:3].view(np.int32)[:] = (H, W)
-            plan = ctypes.c_void_p()
-            rc = self.lib.mulut_eval_plan_create(dev.index, items.ctypes.data, s["n"], self.scale, ctypes.byref(plan))
-            if rc:
-                self.close()
-                raise RuntimeError(self.lib.mulut_strerror(rc).decode())
-            s["plan"] = plan
-        torch.cuda.synchronize(dev)                        # the set is in place whatever stream a validation runs on
-        self.writer = ValWriter(workers, encode)
-        self.copy_stream, self.copied, self.out_host = None, None, None
-
-    def lr_tensor(self, n):
-        _, _, _, l, h, w = self.shapes[n]
-        return self.lr_f32[l:l + 3 * h * w].view(1, 3, h, w)
-
-    def lr_bytes_hwc(self, n):
-        _, _, _, l, h, w = self.shapes[n]
-        return self.lr_pool[l:l + 3 * h * w].view(h, w, 3)
-
-    def out_slot(self, n):
-        g, H, W = self.shapes[n][:3]
-        return self.out_pool[g:g + 3 * H * W]
-
-    def before_write(self):
-        """The output pool is not rewritten before its copy to the host has finished: the current stream waits for that copy (the
-        host does not)."""
-        if self.copied is not None:
-            torch.cuda.current_stream(self.device).wait_event(self.copied)
-
-    def score(self):
-        """One mulut_eval_plan_run per dataset on the current stream, then the point's only wait: the sums of all datasets read back
-        once.  Returns {dataset: float64 array [images, 2]} of (PSNR, SSIM), mulut_eval_finish applied per image."""
-        stream = torch.cuda.current_stream(self.device)
-        for s in self.sets:
-            rc = self.lib.mulut_eval_plan_run(s["plan"], self.gt_pool.data_ptr(), self.out_pool.data_ptr(),
-                                              self.sums[s["first"]:].data_ptr(), ctypes.c_void_p(stream.cuda_stream))
-            if rc:
-                raise RuntimeError(self.lib.mulut_strerror(rc).decode())
-        self.sums_host.copy_(self.sums, non_blocking=True)
-        stream.synchronize()
-        sums, out = self.sums_host.numpy(), {}
-        ps, ss = ctypes.c_double(), ctypes.c_double()
-        for s in self.sets:
-            rows = []
-            for n in range(s["first"], s["first"] + s["n"]):
-                _, H, W = self.shapes[n][:3]
-                rc = self.lib.mulut_eval_finish(float(sums[n, 0]), float(sums[n, 1]), H, W, self.scale, ctypes.byref(ps), ctypes.byref(ss))
-                if rc:
-                    raise RuntimeError(self.lib.mulut_strerror(rc).decode())
-                rows.append((ps.value, ss.value))
-            out[s["name"]] = np.asarray(rows, dtype=np.float64)
-        return out
-
-    def save(self):
-        """The output pool as it is on the current stream now, to {valoutDir}/{dataset}/ behind the loop: a copy to pinned host memory
-        on a side stream, then the writer's threads.  Joins the files of the point before (ValWriter.submit); does not wait for
-        its own."""
-        self.writer.join()                                 # (the pinned buffer is theirs until they are done)
-        if self.out_host is None:
-            self.out_host = torch.empty(self.gt_bytes, dtype=torch.uint8).pin_memory()
-            self.copy_stream = torch.cuda.Stream(self.device)
-        produced = torch.cuda.Event()
-        produced.record(torch.cuda.current_stream(self.device))
-        self.copy_stream.wait_event(produced)
-        with torch.cuda.stream(self.copy_stream):
-            self.out_host.copy_(self.out_pool, non_blocking=True)
-        copied = torch.cuda.Event()
-        copied.record(self.copy_stream)
-        self.copied = copied
-        host, jobs = self.out_host.numpy(), []
-        for s in self.sets:
-            os.makedirs(s["out_dir"], exist_ok=True)
-            for k, fn in enumerate(s["files"]):
-                g, H, W = self.shapes[s["first"] + k][:3]
-                jobs.append((os.path.join(s["out_dir"], val_png_name(s["name"], fn)), host[g:g + 3 * H * W].reshape(H, W, 3)))
-        self.writer.submit(jobs, ready=copied.synchronize)
-
-    def join(self):
-        """Every file submitted so far is on disk (or its failure is raised here)."""
-        self.writer.join()
-
-    def close(self):
-        for s in self.sets:
-            if s.get("plan") is not None:
-                self.lib.mulut_eval_plan_destroy(s.pop("plan"))
-        if getattr(self, "writer", None) is not None:
-            self.writer.close()
-
-
-def _val_saves(opt, it):
-    """--valSave: every point's files, the final validation point's only, or none."""
-    mode = getattr(opt, "valSave", "every")
-    if mode == "last":
-        step = getattr(opt, "valStep", 0)
-        return it == (((opt.totalIter // step) * step or 1) if step else 1)      # (iteration 1 is the only point of a run shorter than valStep)
-    return mode == "every"
-
-
-def resident_valid_steps(net, vset, opt, it, log=print):
-    """valid_steps from a DeviceValSet: per image the module under no_grad and one mulut_ft_val_pack straight into the image's slot of
-    the output pool, per dataset one mulut_eval_plan_run, one read-back at the end of the point, the PNGs behind the loop.  The same
-    log lines, return value and opt.valResults as valid_steps, the same doubles."""
-    lib, was_training = vset.lib, net.training
-    net.eval()
-    vset.before_write()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(vset.device).cuda_stream)
-    with torch.no_grad():
-        for n in range(len(vset.shapes)):
-            pred = net(vset.lr_tensor(n)).contiguous()
-            _, H, W = vset.shapes[n][:3]
-            if tuple(pred.shape) != (1, 3, H, W) or pred.dtype != torch.float32:
-                raise ValueError("the module's output {} is not the ground truth's [1, 3, {}, {}]".format(tuple(pred.shape), H, W))
-            rc = lib.mulut_ft_val_pack(vset.device.index, pred.data_ptr(), H, W, vset.out_slot(n).data_ptr(), stream)
-            if rc:
-                raise RuntimeError(lib.mulut_strerror(rc).decode())
-    per_image = vset.score()
-    if _val_saves(opt, it):
-        vset.save()
-    results = {}
-    for ds, rows in per_image.items():
-        results[ds] = (float(np.mean(rows[:, 0].tolist())), float(np.mean(rows[:, 1].tolist())))
-        log('Iter {} | Dataset {} | AVG PSNR: {:02f}, AVG: SSIM: {:04f}'.format(it, ds, results[ds][0], results[ds][1]))
-    net.train(was_training)
-    opt.valResults = per_image
-    return results
-
-
-def resident_engine_valid_steps(net, engine, vset, opt, it, log=print):
-    """engine_valid_steps from a DeviceValSet: install_into, engine.pipeline from the uint8 LR pool into the output pool, the same
-    plans and read-back as resident_valid_steps.  The lines and arrays of engine_valid_steps.  (It saves no files, as that does not.)"""
-    net.install_into(engine)
-    vset.before_write()
-    for n in range(len(vset.shapes)):
-        engine.pipeline(vset.lr_bytes_hwc(n), out=vset.out_slot(n))
-    results = vset.score()
-    for ds in results:
-        log('Iter {} | Dataset {} | AVG LUT PSNR: {:.2f} SSIM: {:.4f}'.format(it, ds, np.mean(results[ds][:, 0]), np.mean(results[ds][:, 1])))
-    return results
+from .ft_data import CropProvider, DeviceCropProvider, TrainingSetTooLarge, _PendingLR, draw_sample, scan_pairs  # noqa: F401
+from .ft_val import (DeviceValSet, ValidationSetTooLarge, ValShape, ValWriter, _val_datasets, _val_saves, engine_valid_steps,  # noqa: F401
+                     iter_val_pairs, resident_engine_valid_steps, resident_valid_steps, val_png_name, valid_steps)
 
 
 def build_parser():
@@ -608,6 +101,9 @@ class FinetuneRun:
     itself can look at ``net``, ``optim``, ``sched`` and ``loss_buf`` between two of them."""
 
     def __init__(self, opt, log=print):
+        for name, default in vars(build_parser().parse_args(["-e", ""])).items():      # a flag's default is build_parser()'s, for any caller's opt
+            if not hasattr(opt, name):
+                setattr(opt, name, default)
         self.opt, self.log = opt, log
         wide = any(m in "eho" for m in opt.modes)      # the reference's module stops at s, d, y (sr/model.py:119-121)
         self.net = (MuLUTWide if wide else MuLUTInterval if opt.interval in (5, 6) else MuLUT)(opt.expDir, opt.stages, list(opt.modes), upscale=opt.scale, interval=opt.interval).cuda()
@@ -622,30 +118,37 @@ class FinetuneRun:
             lr_a = 1 - lr_b
             lf = lambda x: (((1 + math.cos(x * math.pi / opt.totalIter)) / 2) ** 1.0) * lr_a + lr_b   # noqa: E731
         self.sched = torch.optim.lr_scheduler.LambdaLR(self.optim, lr_lambda=lf)
-        make_lr = getattr(opt, "makeLR", False)
-        if getattr(opt, "hostData", False):
-            self.data = CropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, make_lr, log)
+        if opt.hostData:
+            self.data = CropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, opt.makeLR, log)
         else:
             try:      # the set stays on the device for the whole run: at most half of what is free now
                 self.data = DeviceCropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, max_bytes=torch.cuda.mem_get_info()[0] // 2,
-                                               make_lr=make_lr, log=log)
+                                               make_lr=opt.makeLR, log=log)
             except TrainingSetTooLarge as e:
                 log("{} | training set of {} bytes exceeds half the free device memory ({}): batches are cut on the host".format(opt.expDir, e.nbytes, e.limit))
                 self.data = e.host
-        if getattr(opt, "valoutDir", None) is None:
+        if opt.valoutDir is None:
             opt.valoutDir = os.path.join(opt.expDir, "val")
         self.engine, self.engine_at = None, 0
-        if getattr(opt, "valEngine", False):      # one engine for the run: later installs rewrite its tables in place
+        if opt.valEngine:      # one engine for the run: later installs rewrite its tables in place
             from .engine import MuLUTEngine
             self.engine = MuLUTEngine(next(self.net.parameters()).device.index).configure(opt.stages, opt.modes, opt.scale, opt.interval)
             opt.valEngineResults = {}              # {dataset: [images, 2]} of the last engine validation, for callers
         self.vset = None
-        if getattr(opt, "valResident", False) and os.path.isdir(getattr(opt, "valDir", "")) and (getattr(opt, "valStep", 0) or self.engine is not None):
-            limit = getattr(opt, "valMaxBytes", None)
+        if opt.valResident and os.path.isdir(opt.valDir) and (opt.valStep or self.engine is not None):
             try:      # resident for the whole run: at most a quarter of what is free now
-                self.vset = DeviceValSet(opt, max_bytes=torch.cuda.mem_get_info()[0] // 4 if limit is None else limit, workers=getattr(opt, "valWorkers", 4))
+                self.vset = DeviceValSet(opt, max_bytes=torch.cuda.mem_get_info()[0] // 4 if opt.valMaxBytes is None else opt.valMaxBytes, workers=opt.valWorkers)
             except ValidationSetTooLarge as e:
                 log("{} | validation set of {} bytes exceeds the {} allowed on the device: validation runs on the host loop".format(opt.expDir, e.nbytes, e.limit))
+        # what a validation point runs, and what ends it, chosen here once: from the resident set or on the host loop
+        if self.vset is not None:
+            self.valid = lambda it: resident_valid_steps(self.net, self.vset, opt, it, log)
+            self.engine_valid = lambda it: resident_engine_valid_steps(self.net, self.engine, self.vset, opt, it, log)
+            self.close_valid = self.vset.close
+        else:
+            self.valid = lambda it: valid_steps(self.net, opt, it, log)
+            self.engine_valid = lambda it: engine_valid_steps(self.net, self.engine, opt, it, log)
+            self.close_valid = lambda: None
         # the loop never waits for the device per step: every loss goes into this vector, read at the display points and at the end
         self.loss_buf = torch.zeros(opt.totalIter, dtype=torch.float32, device="cuda")
         self.losses, self.t_mark, self.i = [], time.time(), 0
@@ -669,20 +172,12 @@ class FinetuneRun:
                                                                                sum(losses[i - opt.displayStep:i]) / opt.displayStep,
                                                                                (time.time() - self.t_mark) / opt.displayStep))
             self.t_mark = time.time()
-        if getattr(opt, "valStep", 0) and (i % opt.valStep == 0 or i == 1) and os.path.isdir(getattr(opt, "valDir", "")):   # :152-158
+        if opt.valStep and (i % opt.valStep == 0 or i == 1) and os.path.isdir(opt.valDir):   # :152-158
             t_val = time.time()
-            if self.vset is not None:
-                resident_valid_steps(net, self.vset, opt, i, log)
-            else:
-                valid_steps(net, opt, i, log)
+            self.valid(i)
             if self.engine is not None:
-                opt.valEngineResults, self.engine_at = self._engine_valid(i), i
+                opt.valEngineResults, self.engine_at = self.engine_valid(i), i
             self.t_mark += time.time() - t_val
-
-    def _engine_valid(self, it):
-        if self.vset is not None:
-            return resident_engine_valid_steps(self.net, self.engine, self.vset, self.opt, it, self.log)
-        return engine_valid_steps(self.net, self.engine, self.opt, it, self.log)
 
     def finish(self):
         """The last read-back, the engine's score of the tables as they are exported, the export (:162-171); with --valResident every
@@ -691,12 +186,11 @@ class FinetuneRun:
         losses.extend(self.loss_buf[len(losses):self.i].tolist())
         try:
             if self.engine is not None:
-                if self.engine_at != opt.totalIter and os.path.isdir(getattr(opt, "valDir", "")):      # the tables as they are exported below
-                    opt.valEngineResults = self._engine_valid(opt.totalIter)
+                if self.engine_at != opt.totalIter and os.path.isdir(opt.valDir):      # the tables as they are exported below
+                    opt.valEngineResults = self.engine_valid(opt.totalIter)
                 self.engine.close()
         finally:
-            if self.vset is not None:
-                self.vset.close()
+            self.close_valid()
         if isinstance(data, DeviceCropProvider) and int(data.bad.item()):
             raise RuntimeError("mulut_ft_crop_batch refused %d samples" % int(data.bad.item()))
         for key, table in net.export_int8().items():                          # :162-169

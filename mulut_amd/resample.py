@@ -34,12 +34,6 @@ def tile_w(channels=1, packed=True):
     return 256 // (4 * c) * 4
 
 
-def _check(lib, rc):
-    if rc < 0:
-        raise MuLUTError("mulut error %d: %s" % (rc, lib.mulut_strerror(rc).decode()))
-    return rc
-
-
 def coeffs(in_size, out_size):
     """One axis' tables as Pillow builds them (host only): (kk int32 [out][taps], xmin int32 [out], n int32 [out])."""
     lib = _native.load()
@@ -50,8 +44,8 @@ def coeffs(in_size, out_size):
     kk = np.zeros((out_size, taps), np.int32)
     xmin, n = np.zeros(out_size, np.int32), np.zeros(out_size, np.int32)
     i32p = ctypes.POINTER(ctypes.c_int32)
-    got = _check(lib, lib.mulut_resample_coeffs(in_size, out_size, kk.ctypes.data_as(i32p), xmin.ctypes.data_as(i32p), n.ctypes.data_as(i32p),
-                                                kk.size))
+    got = _native.check(lib.mulut_resample_coeffs(in_size, out_size, kk.ctypes.data_as(i32p), xmin.ctypes.data_as(i32p), n.ctypes.data_as(i32p), kk.size),
+                        MuLUTError)
     assert got == taps
     return kk, xmin, n
 
@@ -59,7 +53,7 @@ def coeffs(in_size, out_size):
 class _Plan:
     def __init__(self, lib, device, in_h, in_w, out_h, out_w):
         self._lib, self._h = lib, ctypes.c_void_p()
-        _check(lib, lib.mulut_resample_plan_create(device, in_h, in_w, out_h, out_w, ctypes.byref(self._h)))
+        _native.check(lib.mulut_resample_plan_create(device, in_h, in_w, out_h, out_w, ctypes.byref(self._h)), MuLUTError)
 
     def close(self):
         if self._h:
@@ -126,7 +120,7 @@ def bicubic(x, size, out=None):
     plan = _plan(t.device.index, int(in_h), int(in_w), out_h, out_w)
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-        _check(lib, lib.mulut_resample_run(plan._h, t.data_ptr(), layout, res.data_ptr(), layout, int(N), int(C), stream))
+        _native.check(lib.mulut_resample_run(plan._h, t.data_ptr(), layout, res.data_ptr(), layout, int(N), int(C), stream), MuLUTError)
     if out is not None:
         return out
     if as_numpy:

@@ -223,7 +223,7 @@ def test_driver_trains_with_either_provider(tmp_path, monkeypatch, host_data):
                                                   "--batchSize", "16", "--cropSize", "24", "--totalIter", "60", "--displayStep", "25", "--lr0", "1e-3",
                                                   "--seed", "0", "--valStep", "0"] + (["--hostData"] if host_data else []))
     losses = finetune_lut.finetune(opt, log=lines.append)
-    assert made == (["CropProvider"] if host_data else ["DeviceCropProvider", "CropProvider"])      # (the device provider scans through the host one)
+    assert made == (["CropProvider"] if host_data else ["DeviceCropProvider"])      # (the device provider scans for itself: ft_data.scan_pairs)
     assert len(losses) == 60 and all(isinstance(v, float) and np.isfinite(v) for v in losses)
     assert np.mean(losses[-15:]) < np.mean(losses[:15])
     shown = [ln for ln in lines if "Iter:" in ln]
