@@ -200,7 +200,8 @@ int mulut_debug_read(mulut_ctx *ctx, unsigned long long *out, int cap, int reset
  *   - "accumulates" means ADDS: after the call every element of grad_wq[m] and grad_x holds what it held before plus this call's
  *     gradient -- elements the batch does not touch are not written at all -- so gradients of several micro-batches may be summed
  *     by calling again without zeroing ("zero them first" is for the caller who wants one call's gradient).  The adds are float32
- *     atomics in no fixed order: bit-reproducible only where the sums are exact.
+ *     atomics in no fixed order: bit-reproducible only where the sums are exact (mulut_ft_exact_stage_backward, further down, is
+ *     the backward whose bits do not depend on that order).
  *   - alignment: float alignment (4 bytes) suffices for x, out, grad_out, grad_x and every table and gradient pointer, 2 bytes for
  *     `inside`; tables of one stage may lie back to back (rows * u*u floats apart).  Nothing outside x, weights_q[m], grad_out and
  *     `inside` is read, nothing outside out, `inside` (forward), grad_wq[m] and grad_x is written.
@@ -269,6 +270,35 @@ int mulut_ft_wide_stage_forward(int device, int interval, const float *const *we
 int mulut_ft_wide_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
                                  const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
                                  float *const *grad_wq, float *grad_x, void *stream);
+/* The BIT-REPRODUCIBLE backward of the same stage (sr/model.py:69-312, autograd's backward of it): arguments and meaning are those
+ * of mulut_ft_wide_stage_backward -- any list over s, d, y, e, h, o, interval 4, 5 or 6, u = 1..4, `inside` required, the forward
+ * is mulut_ft_wide_stage_forward, unchanged -- plus a workspace.  Every contribution to a gradient element is the float32 value the
+ * kernels above compute (the expressions are written once, mulut_amd/csrc/mulut_ft_exact.h), converted to a 64-bit fixed-point
+ * integer, round half to even, at a scale derived from max |grad_out| and the shape of the call alone; the integers are summed --
+ * integer addition is associative -- and each sum is converted to float32 once and ADDED to its destination with one float add
+ * ("accumulates" as above; an element whose integer sum is 0 is not written).
+ *   - the result is a pure function of the argument VALUES: the same bits for any order in which the hardware runs the work, for
+ *     any launch geometry, and -- grad_wq -- for any order of the samples in the batch (grad_x: the same permutation of its
+ *     planes).  tests/host_emul/ft_exact_host.cpp restates it on the CPU with plain int64 adds; the GPU tests ask equality.
+ *   - resolution: with gmax = max |grad_out|, one unit of a table sum is at most gmax * 2^(ceil(log2(4 B C H W)) - 60) (gmax * 2^-38
+ *     at 256 x 48 x 48 sites), one unit of an input sum at most gmax * 2^(4 + ceil(log2 u*u) + ceil(log2 N) - 60), N = 16 M
+ *     min((R + 1)^2, H W), R = max(2, reach of the list); a contribution below half a unit counts as 0.  No sum can leave +-2^62
+ *     for tables within +-127 (the quantised tables) and a finite grad_out.  A non-finite grad_out gives unspecified results
+ *     but no fault: no address depends on grad_out.
+ *   - ws: device memory, 8-byte aligned, of at least mulut_ft_exact_ws_bytes(...) bytes, which the call owns until it completes:
+ *     its content on entry is irrelevant, calls that share one ws must be ordered (one stream, or events).  Nothing outside x,
+ *     weights_q[m], grad_out, `inside` and ws is read, nothing outside grad_wq[m], grad_x and ws is written.
+ *   - a call is four kernel launches on `stream` (clear, maximum, accumulate, finish) and nothing else: it allocates nothing and waits
+ *     for nothing, and is capturable after one warm-up call, as above.
+ * Refusals, all before the device is touched, in the order of mulut_ft_wide_stage_backward (NULL grad_wq; then NULL weights_q,
+ * modes, x, inside or a non-positive size MULUT_EINVAL; interval outside 4..6, more than MULUT_MAX_MODES modes, u outside 1..4
+ * MULUT_EUNSUPPORTED; a letter outside the six MULUT_EMODE; a NULL table or gradient pointer MULUT_EINVAL); then NULL grad_out or
+ * grad_x MULUT_EINVAL; more than 2^31 - 1 sites (B C H W) MULUT_EUNSUPPORTED; a NULL or misaligned ws MULUT_EINVAL; ws_bytes below
+ * the query's value MULUT_EWORKSPACE.  mulut_ft_exact_ws_bytes returns the negative MULUT_E* code for arguments the call would refuse. */
+long long mulut_ft_exact_ws_bytes(int interval, const char *modes, int u, int B, int C, int H, int W);
+int mulut_ft_exact_stage_backward(int device, int interval, const float *const *weights_q, const char *modes, int is_last, int u,
+                                  const float *x, const float *grad_out, const unsigned short *inside, int B, int C, int H, int W,
+                                  float *const *grad_wq, float *grad_x, void *ws, long long ws_bytes, void *stream);
 /* A fine-tune batch cut on the device from a device-resident training set: DIV2K.__getitem__ (sr/data.py:91-121, restated by
  * CropProvider.next() of mulut_amd/finetune_lut.py) for B samples in one launch.  The reference draws and cuts in DataLoader
  * workers (sr/data.py:27-49); here the host draws six integers per sample and the device does the rest.

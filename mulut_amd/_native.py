@@ -8,8 +8,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 _LIBDIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(_LIBDIR, "libmulut_hip.so")
-SOURCES = ["mulut_kernels.hip", "mulut_k1.hip", "mulut_detail.hip", "mulut_interval.hip", "mulut_capi.hip", "mulut_ft.hip", "mulut_ft_interval.hip", "mulut_ft_data.hip", "mulut_eval.hip", "mulut_resample.hip"]
-HEADERS = ["mulut_core.h", "mulut_interval.h", "mulut_ft.h", "mulut_ft_interval.h", "mulut_kernels.h", "mulut_dev.h", "mulut_tube2_asm.inc", os.path.join("..", "..", "include", "mulut.h")]
+SOURCES = ["mulut_kernels.hip", "mulut_k1.hip", "mulut_detail.hip", "mulut_interval.hip", "mulut_capi.hip", "mulut_ft.hip", "mulut_ft_interval.hip", "mulut_ft_exact.hip", "mulut_ft_data.hip", "mulut_eval.hip", "mulut_resample.hip"]
+HEADERS = ["mulut_core.h", "mulut_interval.h", "mulut_ft.h", "mulut_ft_interval.h", "mulut_ft_exact.h", "mulut_kernels.h", "mulut_dev.h", "mulut_tube2_asm.inc", os.path.join("..", "..", "include", "mulut.h")]
 # -Wno-inline-asm: stage_tube2_kernel names registers ABOVE the register allocator's budget in its asm clobber lists on purpose
 # (tools/gen_tube2_asm.py); -Wno-pass-failed: its occupancy attribute is that budget, not an occupancy the kernel reaches
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-inline-asm", "-Wno-pass-failed"]
@@ -21,7 +21,7 @@ EXPORTS = [
     "mulut_pipeline_rows", "mulut_halo", "mulut_reserve", "mulut_set_stage_timing", "mulut_last_stage_ms", "mulut_last_kernel_ms",
     "mulut_set_tuning", "mulut_kernel_name", "mulut_ft_stage_forward", "mulut_ft_stage_backward", "mulut_ft_quantize", "mulut_ft_quantize_backward", "mulut_ft_adam",
     "mulut_ft_stage_forward_mask", "mulut_ft_stage_backward_mask", "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward",
-    "mulut_ft_wide_stage_forward", "mulut_ft_wide_stage_backward", "mulut_ft_crop_batch", "mulut_ft_val_pack",
+    "mulut_ft_wide_stage_forward", "mulut_ft_wide_stage_backward", "mulut_ft_exact_ws_bytes", "mulut_ft_exact_stage_backward", "mulut_ft_crop_batch", "mulut_ft_val_pack",
     "mulut_eval_ws_doubles", "mulut_eval_y", "mulut_eval_plan_create", "mulut_eval_plan_run", "mulut_eval_plan_destroy", "mulut_eval_finish", "mulut_last_detail_counters", "mulut_debug_read",
     "mulut_resample_coeffs", "mulut_resample_plan_create", "mulut_resample_plan_destroy", "mulut_resample_run",
 ]
@@ -189,6 +189,10 @@ def load(path=None):
     L.mulut_ft_interval_stage_backward.argtypes = [i, i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p]
     L.mulut_ft_wide_stage_forward.argtypes = [i, i, p, c_char_p, i, i, p, i, i, i, i, p, p, p]
     L.mulut_ft_wide_stage_backward.argtypes = [i, i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p]
+    L.mulut_ft_exact_ws_bytes.argtypes = [i, c_char_p, i, i, i, i, i]
+    L.mulut_ft_exact_ws_bytes.restype = ctypes.c_longlong
+    L.mulut_ft_exact_stage_backward.argtypes = [i, i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p, ctypes.c_longlong, p]
+    L.mulut_ft_exact_stage_backward.restype = i
     L.mulut_ft_crop_batch.argtypes = [i, p, ctypes.c_longlong, p, i, p, i, i, i, p, p, p, p]
     L.mulut_kernel_name.restype = c_char_p
     L.mulut_ft_quantize.argtypes = [i, p, p, i, ctypes.c_longlong, p]

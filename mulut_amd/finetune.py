@@ -72,23 +72,45 @@ class _StageFn(torch.autograd.Function):
         gwq = [g_all[m].view(w.shape) for m, w in enumerate(ws)]
         gx = torch.zeros_like(x)
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _native.check(lib.mulut_ft_wide_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
-                                                       x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
-                                                       gx.data_ptr(), stream))
+        if getattr(ctx, "exact", False):
+            # fixed-point sums (mulut_ft_exact_stage_backward): the same bits whatever order the hardware runs the waves in.  The
+            # workspace comes from torch's allocator on the current stream, so its reuse is ordered behind this call.
+            need = _native.check(lib.mulut_ft_exact_ws_bytes(int(interval), modes.encode(), int(u), B, C, H, W))
+            work = torch.empty(need // 8, dtype=torch.int64, device=x.device)
+            _native.check(lib.mulut_ft_exact_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                                            x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
+                                                            gx.data_ptr(), work.data_ptr(), need, stream))
+        else:
+            _native.check(lib.mulut_ft_wide_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                                           x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
+                                                           gx.data_ptr(), stream))
         # backward of clamp(round_func(w*127)): round is identity (BPDA), clamp passes inside [-127,127], x127 -- in place, one launch
         _native.check(lib.mulut_ft_quantize_backward(x.device.index, _ptr_array(ws), _ptr_array(gwq), len(ws), ws[0].numel(), stream))
         return (gx, None, None, None, None) + tuple(gwq)
 
 
+class _StageFnExact(_StageFn):
+    """The same stage with the bit-reproducible backward (``deterministic=True``): quantise, forward, mask and quantise-backward are
+    _StageFn's; the table and input gradients are summed in 64-bit fixed point (mulut_ft_exact_stage_backward)."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.exact = True
+        return _StageFn.forward(ctx, *args)
+
+
 class MuLUT(nn.Module):
     """PyTorch module for LUT-aware fine-tuning on the GPU (twin of sr/model.py:39-312), sampling interval 4.
-    Intervals 5 and 6 are ``MuLUTInterval``; mode lists with e, h or o are ``MuLUTWide``."""
+    Intervals 5 and 6 are ``MuLUTInterval``; mode lists with e, h or o are ``MuLUTWide``.
+    ``deterministic=True``: the backward sums every gradient in 64-bit fixed point instead of with float32 atomics -- the same bits
+    on every run (torch's ``use_deterministic_algorithms`` for this module; resolution and cost: DESIGN.md section 8)."""
 
     MODES = "sdy"       # the patterns the class takes
 
-    def __init__(self, lut_folder, stages, modes, upscale=4, interval=4):
+    def __init__(self, lut_folder, stages, modes, upscale=4, interval=4, deterministic=False):
         super().__init__()
         self._check_interval(interval)
+        self.deterministic = bool(deterministic)
         self.interval, self.upscale, self.stages = interval, upscale, stages
         self.modes = "".join(modes)
         for mode in self.modes:
@@ -113,7 +135,7 @@ class MuLUT(nn.Module):
             stage = s + 1
             last = stage == self.stages
             weights = [getattr(self, "weight_s{}_{}".format(stage, m)) for m in self.modes]
-            x = _StageFn.apply(x, self.modes, last, self.upscale if last else 1, self.interval, *weights)
+            x = (_StageFnExact if self.deterministic else _StageFn).apply(x, self.modes, last, self.upscale if last else 1, self.interval, *weights)
         return x / 255.0
 
     @staticmethod
@@ -147,8 +169,8 @@ class MuLUTInterval(MuLUT):
     tables of 6,561 / 625 rows, read from ``LUT_x{scale}_{interval}bit_int8_s{stage}_{mode}.npy`` as transfer_to_lut writes them;
     the stages run on the kernels of mulut_amd/csrc/mulut_ft_interval.hip."""
 
-    def __init__(self, lut_folder, stages, modes, upscale=4, interval=5):
-        super().__init__(lut_folder, stages, modes, upscale=upscale, interval=interval)
+    def __init__(self, lut_folder, stages, modes, upscale=4, interval=5, deterministic=False):
+        super().__init__(lut_folder, stages, modes, upscale=upscale, interval=interval, deterministic=deterministic)
 
     @staticmethod
     def _check_interval(interval):

@@ -36,6 +36,9 @@ stream-ordered call, the sums of all datasets are read back once, and the PNGs a
 ``--valWorkers`` threads (``ValWriter``) behind the loop.  ``--valSave every|last|never`` picks the points whose files are written.
 ``resident_engine_valid_steps`` does the same for ``--valEngine``.  The log lines, ``opt.valResults`` and the files are those of the host
 loops, bit for bit; a set above a quarter of the free device memory falls back to ``valid_steps`` with one log line.
+``--deterministic`` builds the module with ``deterministic=True``: every stage's backward is ``mulut_ft_exact_stage_backward`` (64-bit
+fixed-point gradient sums), and with a fixed ``--seed`` two runs write the same ``LUT_ft_*.npy`` bytes.  Everything else in the loop is as
+without the flag.
 The providers, their scan and their draw are defined in ``mulut_amd.ft_data``, everything named above that validates in
 ``mulut_amd.ft_val``; this module is the parser and the loop, and carries those names as its own.
 """
@@ -75,6 +78,10 @@ def build_parser():
     p.add_argument('--lr1', type=float, default=1e-4)
     p.add_argument('--weightDecay', type=float, default=0)
     p.add_argument('--seed', type=int, default=None)
+    p.add_argument('--deterministic', default=False, action='store_true',
+                   help='bit-reproducible training: the backward kernels sum every gradient in 64-bit fixed point instead of with '
+                        'float32 atomics, so a run is a pure function of its inputs and --seed (with --seed unset the draws differ '
+                        'from run to run: fix the seed to repeat a run)')
     p.add_argument('--hostData', default=False, action='store_true',
                    help='cut the batches on the host (CropProvider, the reference\'s path) instead of on the device')
     p.add_argument('--makeLR', default=False, action='store_true',
@@ -106,7 +113,13 @@ class FinetuneRun:
                 setattr(opt, name, default)
         self.opt, self.log = opt, log
         wide = any(m in "eho" for m in opt.modes)      # the reference's module stops at s, d, y (sr/model.py:119-121)
-        self.net = (MuLUTWide if wide else MuLUTInterval if opt.interval in (5, 6) else MuLUT)(opt.expDir, opt.stages, list(opt.modes), upscale=opt.scale, interval=opt.interval).cuda()
+        self.net = (MuLUTWide if wide else MuLUTInterval if opt.interval in (5, 6) else MuLUT)(opt.expDir, opt.stages, list(opt.modes), upscale=opt.scale, interval=opt.interval,
+                                                                                                deterministic=opt.deterministic).cuda()
+        if opt.deterministic:
+            # one unit of a table sum, as a multiple of the step's largest |grad_out| (include/mulut.h): 2^(ceil(log2(4 sites)) - 60)
+            log("{} | deterministic backward: 64-bit fixed-point gradient sums, resolution 2^{} of max |grad_out| per stage call{}".format(
+                opt.expDir, math.ceil(math.log2(4 * opt.batchSize * opt.cropSize * opt.cropSize)) - 60,
+                "" if opt.seed is not None else " (no --seed: the draws are not fixed)"))
         params = [p for p in self.net.parameters() if p.requires_grad]
         # the reference's Adam as one launch over the six tables, its arithmetic in float64 (torch's default is ~10 launches per step; its
         # fused=True is one, but strays from float64 Adam by hundreds of float32 ulps on an element that lands near zero, as every float32 Adam does)
