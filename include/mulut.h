@@ -400,6 +400,35 @@ int mulut_resample_plan_destroy(mulut_resample_plan *plan);
 int mulut_resample_run(const mulut_resample_plan *plan, const uint8_t *in, int in_layout, uint8_t *out, int out_layout, int N, int C,
                        void *stream);
 
+/* The trained network itself, fused: the per-site MLP of one `SRNet` (common/network.py:62-105, MuLUTUnit with dense=True: conv1
+ * 4 -> nf, conv2..conv5 densely connected, conv6 5*nf -> u*u, tanh) on the f32-input MFMA, activations in registers, weights streamed
+ * through LDS.  No context: a unit owns the device copy of its packed weights and nothing else.
+ *   mulut_net_unit_create   w[l] / b[l]: HOST pointers to conv(l+1)'s weight ([out][in], the reference's Conv2d weight read flat) and
+ *                           bias.  nf 1..64 and u 1..4 (padded with zero weights to the MFMA tile, which is exact); anything else
+ *                           MULUT_EUNSUPPORTED.  Packs on the host, allocates and uploads once; the other calls allocate nothing.
+ *   mulut_net_table         sr/2_transfer_to_lut.py:12-41,86-109: rows_dev = int8 [L^4][u*u], round_half_even(clamp(net, -1, 1) * 127)
+ *                           over the grid 0, q, ..., 256 - q, 255 (each / 255), row = the base-L digits a, b, c, d with a slowest, for
+ *                           interval 4, 5 or 6 (else MULUT_EUNSUPPORTED).  The grid values go to taps a, b, c, d whatever the pattern.
+ *   mulut_net_pass          sr/1_train_model.py:33-35: out = int8 planar [N][C][H*u][W*u] =
+ *                           rot90^-r(round(127 * net(pad(rot90^r(in / 255))))) for in = uint8 planar [N][C][H][W], pattern `mode`
+ *                           (s, d, y, e, h, o) and r in 0..3; the replicate padding of K - 1 on the bottom and right of the rotated
+ *                           image is index arithmetic on `in`.
+ *   mulut_net_stage         sr/1_train_model.py:29-43 in the 'valid' phase: strlen(modes) units x 4 rotations summed as integers per
+ *                           output sub-pixel, then clip(rhe(pred / (4 M) + 127), 0, 255) (is_last 0) or clip(rhe(pred / M), 0, 255)
+ *                           (is_last 1, with :101), rhe = round half even, done in integers (equal to the reference's float32).
+ *                           uint8 planar in and out.  The units must share u, the padded width (nf <= 32 or not) and the device:
+ *                           MULUT_ESHAPE otherwise.
+ * All three are stream-ordered, wait for nothing and allocate nothing.  Refused before any launch: a NULL pointer, r outside 0..3, an
+ * unknown pattern letter, an empty mode list, N, C, H or W < 1 (MULUT_EINVAL); more than MULUT_MAX_MODES modes, or
+ * N * C * H * W * u * u >= 2^31 (MULUT_EUNSUPPORTED). */
+typedef struct mulut_net_unit mulut_net_unit;
+int mulut_net_unit_create(int device, int nf, int u, const float *const w[6], const float *const b[6], mulut_net_unit **unit);
+int mulut_net_unit_destroy(mulut_net_unit *unit);
+int mulut_net_table(const mulut_net_unit *unit, int interval, int8_t *rows_dev, void *stream);
+int mulut_net_pass(const mulut_net_unit *unit, char mode, int r, const uint8_t *in, int N, int C, int H, int W, int8_t *out, void *stream);
+int mulut_net_stage(const mulut_net_unit *const units[], const char *modes, int is_last, const uint8_t *in, uint8_t *out, int N, int C,
+                    int H, int W, void *stream);
+
 /* Tuning knobs (never change results).
  * "final_stage_kernel" (scale 4, <= 3 modes): 0 = auto (= 6), 1 = full-table gather kernel, 5 = tube kernel on every tile (the tube
  *   bands of all modes resident in LDS; samples with a pass outside the tube are recomputed from the full table through a device

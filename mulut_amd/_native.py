@@ -8,8 +8,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 _LIBDIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(_LIBDIR, "libmulut_hip.so")
-SOURCES = ["mulut_kernels.hip", "mulut_k1.hip", "mulut_detail.hip", "mulut_interval.hip", "mulut_capi.hip", "mulut_ft.hip", "mulut_ft_interval.hip", "mulut_ft_exact.hip", "mulut_ft_data.hip", "mulut_eval.hip", "mulut_resample.hip"]
-HEADERS = ["mulut_core.h", "mulut_interval.h", "mulut_ft.h", "mulut_ft_interval.h", "mulut_ft_exact.h", "mulut_kernels.h", "mulut_dev.h", "mulut_tube2_asm.inc", os.path.join("..", "..", "include", "mulut.h")]
+SOURCES = ["mulut_kernels.hip", "mulut_k1.hip", "mulut_detail.hip", "mulut_interval.hip", "mulut_capi.hip", "mulut_ft.hip", "mulut_ft_interval.hip", "mulut_ft_exact.hip", "mulut_ft_data.hip", "mulut_eval.hip", "mulut_resample.hip", "mulut_net.hip"]
+HEADERS = ["mulut_core.h", "mulut_interval.h", "mulut_ft.h", "mulut_ft_interval.h", "mulut_ft_exact.h", "mulut_kernels.h", "mulut_dev.h", "mulut_net.h", "mulut_tube2_asm.inc", os.path.join("..", "..", "include", "mulut.h")]
 # -Wno-inline-asm: stage_tube2_kernel names registers ABOVE the register allocator's budget in its asm clobber lists on purpose
 # (tools/gen_tube2_asm.py); -Wno-pass-failed: its occupancy attribute is that budget, not an occupancy the kernel reaches
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-inline-asm", "-Wno-pass-failed"]
@@ -24,6 +24,7 @@ EXPORTS = [
     "mulut_ft_wide_stage_forward", "mulut_ft_wide_stage_backward", "mulut_ft_exact_ws_bytes", "mulut_ft_exact_stage_backward", "mulut_ft_crop_batch", "mulut_ft_val_pack",
     "mulut_eval_ws_doubles", "mulut_eval_y", "mulut_eval_plan_create", "mulut_eval_plan_run", "mulut_eval_plan_destroy", "mulut_eval_finish", "mulut_last_detail_counters", "mulut_debug_read",
     "mulut_resample_coeffs", "mulut_resample_plan_create", "mulut_resample_plan_destroy", "mulut_resample_run",
+    "mulut_net_unit_create", "mulut_net_unit_destroy", "mulut_net_table", "mulut_net_pass", "mulut_net_stage",
 ]
 
 _libs = {}
@@ -218,6 +219,14 @@ def load(path=None):
     L.mulut_resample_plan_destroy.argtypes = [p]
     L.mulut_resample_run.argtypes = [p, p, i, p, i, i, i, p]
     for name in ("mulut_resample_coeffs", "mulut_resample_plan_create", "mulut_resample_plan_destroy", "mulut_resample_run"):
+        getattr(L, name).restype = i
+    fpp = ctypes.POINTER(ctypes.POINTER(ctypes.c_float))
+    L.mulut_net_unit_create.argtypes = [i, i, i, fpp, fpp, ctypes.POINTER(p)]
+    L.mulut_net_unit_destroy.argtypes = [p]
+    L.mulut_net_table.argtypes = [p, i, p, p]
+    L.mulut_net_pass.argtypes = [p, ctypes.c_char, i, p, i, i, i, i, p, p]
+    L.mulut_net_stage.argtypes = [ctypes.POINTER(p), c_char_p, i, p, p, i, i, i, i, p]
+    for name in ("mulut_net_unit_create", "mulut_net_unit_destroy", "mulut_net_table", "mulut_net_pass", "mulut_net_stage"):
         getattr(L, name).restype = i
     for name in ("mulut_create", "mulut_destroy", "mulut_configure", "mulut_set_lut", "mulut_pass", "mulut_stage",
                  "mulut_pipeline", "mulut_pipeline_rows", "mulut_halo", "mulut_reserve", "mulut_set_stage_timing",

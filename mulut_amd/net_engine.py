@@ -1,0 +1,157 @@
+"""The trained network on the fused HIP forward (mulut_net_* of include/mulut.h, mulut_amd/csrc/mulut_net.hip): one NetEngine per
+`SRNets`, one device unit per `s{stage}_{mode}` module.
+
+What `network.SRNets` computes as a chain of torch operators with a [sites, 5 * nf] activation matrix per layer runs here as one kernel
+per call with the activations in registers: a table of sr/2_transfer_to_lut.py, one rotation pass, one stage or the whole cascade of
+sr/1_train_model.py's `mulut_predict(..., 'valid')`, bytes to bytes.  torch is used for device memory and streams only.
+"""
+import ctypes
+import re
+
+import numpy as np
+import torch
+
+from . import _native, network
+from .engine import MuLUTError
+from .lut_io import lut_rows
+
+_MODULE = re.compile(r"^s(\d+)_([a-z])$")
+
+
+def _dev(t, dtype, name):
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_cuda and t.is_contiguous()):
+        raise TypeError("%s must be a contiguous %s CUDA tensor" % (name, str(dtype).replace("torch.", "")))
+    return t
+
+
+class NetEngine:
+    """Owns a `mulut_net_unit` per module of `model_G` (an `SRNets`, also one rebuilt by `network.load_checkpoint`).  The weights are
+    read once, here: a later change of the module's parameters is not seen.  Every method takes and returns device tensors and
+    queues its work on torch's current stream."""
+
+    def __init__(self, model_G, device=0, lib_path=None):
+        self._lib = _native.load(lib_path)
+        self._units, self._u = {}, {}
+        if not torch.cuda.is_available():
+            raise MuLUTError("no GPU visible: mulut_amd has no CPU path")
+        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+        found = {}
+        for name, mod in model_G.named_children():
+            m = _MODULE.match(name)
+            if m and isinstance(getattr(mod, "model", None), network.MuLUTUnit):
+                found[(int(m.group(1)), m.group(2))] = mod
+        if not found:
+            raise MuLUTError("no s{stage}_{mode} module found: NetEngine wants an SRNets")
+        self.stages = max(s for s, _ in found)
+        self.modes = "".join(m for s, m in found if s == 1)      # in the module's own order, which is the order they were added in
+        self.scale = None
+        for s in range(1, self.stages + 1):
+            if "".join(m for t, m in found if t == s) != self.modes:
+                raise MuLUTError("stage %d does not hold the modes %r of stage 1" % (s, self.modes))
+        try:
+            for (s, mode), mod in found.items():
+                self._units[(s, mode)], self._u[(s, mode)] = self._create(mod)
+        except Exception:
+            self.close()
+            raise
+        us = {s: {self._u[(s, m)] for m in self.modes} for s in range(1, self.stages + 1)}
+        if any(len(v) != 1 for v in us.values()):
+            self.close()
+            raise MuLUTError("mulut error -4: the units of a stage differ in upscale")
+        self.scale = int(np.prod([next(iter(v)) for v in us.values()]))
+
+    # -- plumbing ---------------------------------------------------------------------------
+    def _check(self, rc):
+        _native.check(rc, MuLUTError)
+
+    def _create(self, srnet):
+        unit = srnet.model
+        if not isinstance(unit.conv2, network.DenseConv):
+            raise MuLUTError("mulut error -5: only dense=True units run on the fused forward")
+        nf, u = int(unit.conv1.conv.out_channels), int(unit.upscale)
+        layers = [unit.conv1.conv] + [c.conv1.conv for c in (unit.conv2, unit.conv3, unit.conv4, unit.conv5)] + [unit.conv6.conv]
+        ws = [np.ascontiguousarray(c.weight.detach().cpu().numpy().reshape(c.weight.shape[0], -1), dtype=np.float32) for c in layers]
+        bs = [np.ascontiguousarray((c.bias.detach().cpu().numpy() if c.bias is not None else np.zeros(c.weight.shape[0])), dtype=np.float32)
+              for c in layers]
+        want = [(nf, 4)] + [(nf, nf * k) for k in (1, 2, 3, 4)] + [(u * u, 5 * nf)]
+        if [w.shape for w in ws] != want:
+            raise MuLUTError("mulut error -4: layer shapes %r are not those of a dense unit, %r" % ([w.shape for w in ws], want))
+        fp = ctypes.POINTER(ctypes.c_float)
+        wp = (fp * 6)(*[w.ctypes.data_as(fp) for w in ws])
+        bp = (fp * 6)(*[b.ctypes.data_as(fp) for b in bs])
+        h = ctypes.c_void_p()
+        self._check(self._lib.mulut_net_unit_create(self.device.index, nf, u, wp, bp, ctypes.byref(h)))
+        return h, u
+
+    def close(self):
+        for h in getattr(self, "_units", {}).values():
+            self._lib.mulut_net_unit_destroy(h)
+        self._units = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _unit(self, stage, mode):
+        try:
+            return self._units[(int(stage), mode)]
+        except KeyError:
+            raise ValueError("Mode {} not implemented.".format(mode)) from None
+
+    def upscale(self, stage):
+        return self._u[(int(stage), self.modes[0])]
+
+    def _u8(self, x, name="x_u8"):
+        _dev(x, torch.uint8, name)
+        if x.device != self.device:
+            raise ValueError("%s lives on %s, engine on %s" % (name, x.device, self.device))
+        if x.dim() != 4:
+            raise ValueError("%s must be planar [N, C, H, W]" % name)
+        return x
+
+    # -- compute ------------------------------------------------------------------------------
+    def table(self, stage, mode, interval=4):
+        """int8 [L^4, 1, u, u] on the device: the table sr/2_transfer_to_lut.py:86-109 makes of this module."""
+        h, u = self._unit(stage, mode), self._u[(int(stage), mode)]
+        if interval not in (4, 5, 6):
+            self._check(-5)
+        out = torch.empty((lut_rows(interval), 1, u, u), dtype=torch.int8, device=self.device)
+        self._check(self._lib.mulut_net_table(h, int(interval), out.data_ptr(), self._stream()))
+        return out
+
+    def pass_(self, stage, mode, r, x_u8):
+        """int8 [N, C, H*u, W*u]: one (mode, rotation) term of sr/1_train_model.py:33-35, round(127 * net(...)) rotated back."""
+        h, u = self._unit(stage, mode), self._u[(int(stage), mode)]
+        x = self._u8(x_u8)
+        N, C, H, W = x.shape
+        out = torch.empty((N, C, H * u, W * u), dtype=torch.int8, device=self.device)
+        self._check(self._lib.mulut_net_pass(h, mode.encode()[:1], int(r), x.data_ptr(), N, C, H, W, out.data_ptr(), self._stream()))
+        return out
+
+    def stage(self, stage, x_u8, out=None):
+        """uint8 [N, C, H*u, W*u]: one stage of mulut_predict in the 'valid' phase (sr/1_train_model.py:29-43)."""
+        stage = int(stage)
+        handles = (ctypes.c_void_p * len(self.modes))(*[self._unit(stage, m).value for m in self.modes])
+        u = self.upscale(stage)
+        x = self._u8(x_u8)
+        N, C, H, W = x.shape
+        if out is None:
+            out = torch.empty((N, C, H * u, W * u), dtype=torch.uint8, device=self.device)
+        elif self._u8(out, "out").shape != (N, C, H * u, W * u):
+            raise ValueError("out has the wrong shape")
+        self._check(self._lib.mulut_net_stage(handles, self.modes.encode(), int(stage == self.stages), x.data_ptr(), out.data_ptr(),
+                                              N, C, H, W, self._stream()))
+        return out
+
+    def predict(self, x_u8):
+        """The whole cascade, bytes to bytes: np.round(np.clip(mulut_predict(model_G, x / 255, 'valid', opt), 0, 255)) of
+        sr/1_train_model.py:93-101."""
+        x = self._u8(x_u8)
+        for s in range(1, self.stages + 1):
+            x = self.stage(s, x)
+        return x

@@ -66,14 +66,19 @@ def transfer_one(model_G, opt, stage, mode, device=None, chunks=100):
     return np.concatenate(outputs, 0)
 
 
-def transfer(model_G, opt, device=None, save=True, engine=None):
+def transfer(model_G, opt, device=None, save=True, engine=None, net_engine=None):
     """All stages x modes (:80-116); returns {'s{stage}_{mode}': table} and writes the .npy files into opt.expDir.
     engine: a MuLUTEngine (configured for the interval) that is left holding the same tables -- ready to run without the files
-    being read back."""
+    being read back.
+    net_engine: a NetEngine of model_G; the tables then come from the fused kernel (mulut_net_table) instead of the torch operators
+    of `transfer_one` -- same files, names and shapes."""
     out = {}
     for s in range(opt.stages):
         for mode in opt.modes:
-            results = transfer_one(model_G, opt, s + 1, mode, device)
+            if net_engine is not None:
+                results = net_engine.table(s + 1, mode, opt.interval).cpu().numpy()
+            else:
+                results = transfer_one(model_G, opt, s + 1, mode, device)
             out["s{}_{}".format(s + 1, mode)] = results
             if engine is not None:
                 engine.set_lut(s + 1, mode, results)
@@ -84,15 +89,40 @@ def transfer(model_G, opt, device=None, save=True, engine=None):
     return out
 
 
+class TransferOptions(TestOptions):
+    """The test-time flags plus the two of this script: --fused, and the validation sets of sr/1_train_model.py for it."""
+
+    def initialize(self, parser):
+        parser = super().initialize(parser)
+        parser.add_argument('--fused', action='store_true', default=False,
+                            help="make the tables with the fused HIP forward of the network (mulut_net_table) instead of torch operators")
+        parser.add_argument('--valDir', type=str, default=None,
+                            help="with --fused: validate the loaded checkpoint on the sets under this folder first "
+                                 "(the 'AVG Val PSNR' lines of sr/1_train_model.py:70-117)")
+        parser.add_argument('--valoutDir', type=str, default=None, help='default: {expDir}/val')
+        return parser
+
+
 def main(argv=None):
-    opt = TestOptions().parse(argv)
+    opt = TransferOptions().parse(argv)
     device = torch.device("cuda", opt.device) if torch.cuda.is_available() else torch.device("cpu")
     modes = [m for m in opt.modes]
     model_cls = getattr(network, opt.model)                       # 'SRNets' (common/option.py default)
     model_G = model_cls(nf=opt.nf, scale=opt.scale, modes=modes, stages=opt.stages).to(device)
     lm = network.load_checkpoint(os.path.join(opt.expDir, "Model_{:06d}.pth".format(opt.loadIter)))
     model_G.load_state_dict(lm.state_dict(), strict=True)
-    return transfer(model_G, opt, device)
+    if opt.valDir is not None and not opt.fused:
+        raise SystemExit("--valDir validates on the fused forward: it needs --fused")
+    if not opt.fused:
+        return transfer(model_G, opt, device)
+    from .net_engine import NetEngine
+    from .net_val import net_valid_steps
+    net_engine = NetEngine(model_G, opt.device)
+    if opt.valDir is not None:
+        if opt.valoutDir is None:
+            opt.valoutDir = os.path.join(opt.expDir, "val")
+        net_valid_steps(net_engine, opt, opt.loadIter)
+    return transfer(model_G, opt, device, net_engine=net_engine)
 
 
 if __name__ == "__main__":
