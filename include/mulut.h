@@ -429,6 +429,43 @@ int mulut_net_pass(const mulut_net_unit *unit, char mode, int r, const uint8_t *
 int mulut_net_stage(const mulut_net_unit *const units[], const char *modes, int is_last, const uint8_t *in, uint8_t *out, int N, int C,
                     int H, int W, void *stream);
 
+/* ---- Training the network on the fused site body (mulut_net_train.hip): sr/1_train_model.py:26-45 in the 'train' phase and its
+ * gradient.  Everything here is float32 on the device and stream-ordered; nothing allocates but mulut_net_unit_create_train.
+ *   mulut_net_unit_create_train  a unit with BOTH streams -- the forward's and the backward's (the transposed weights in the same step
+ *                           format, mulut_net.h) -- allocated and zeroed; mulut_net_unit_destroy frees it.  nf, u as above.
+ *   mulut_net_unit_load_dev w_dev[l] / b_dev[l]: DEVICE pointers laid out as mulut_net_unit_create's host ones.  One small kernel on
+ *                           `stream` writes the forward stream exactly as the host pack does and, for a unit of
+ *                           mulut_net_unit_create_train, the backward stream in the same launch.  Works on either kind of unit.
+ *   mulut_net_pack_host     the host packs themselves, no device involved: the stream mulut_net_unit_create uploads (backward 0) or
+ *                           the backward stream (1) of HOST weights into `out`; returns the number of floats (MULUT_EWORKSPACE if
+ *                           cap is smaller).  What the device pack is tested against.
+ *   mulut_net_unit_read     copies a stream (backward 0 / 1) to `host` after a device synchronisation, for tests; returns the
+ *                           number of floats, MULUT_EWORKSPACE if cap is smaller, MULUT_EINVAL for the backward stream of a unit
+ *                           that has none.
+ *   mulut_net_stage_sum     pred = float32 planar [N][C][H*u][W*u] = sum over modes and r of rot90^-r(round(127 * net(pad(rot90^r(x)))))
+ *                           for x = float32 planar [N][C][H][W]: :30-35, before the stage's own arithmetic (:36-43).  The values
+ *                           are integers; the sum is made in integers, so two calls agree bit for bit.
+ *   mulut_net_backward_ws_bytes  the workspace for chunks of `sites` sites: 16 copies of a unit's gradient plus
+ *                           (4 + 10 nf + u*u) floats per site, sites rounded up to 128.  `sites` = 128 gives the smallest workspace
+ *                           mulut_net_stage_backward takes; the pixel count of the image lets every pass run as one chunk.
+ *   mulut_net_stage_backward  g = dL/dpred (the shape of pred).  Round is the identity here (BPDA, :48-55), so this is the exact
+ *                           Jacobian of the smooth sum of 127 * net at x.  gw / gb: 6 * M device pointers, [6 * m + l] = the gradient
+ *                           of conv(l+1)'s weight / bias of unit m; they are WRITTEN, and bit-identical from run to run.  gx, if not
+ *                           NULL, has the shape of x and is ADDED to (float atomics: zero it first; not bit-reproducible); NULL skips
+ *                           the tap gradient (a first stage).  ws: 256-byte aligned, of ws_bytes bytes; the passes run in chunks of
+ *                           as many sites as fit.  The units must come from mulut_net_unit_create_train and share nf.
+ * Refusals before any launch: as mulut_net_stage's, plus a unit without a backward stream, a NULL gradient pointer, a misaligned ws
+ * (MULUT_EINVAL), units of different nf (MULUT_ESHAPE), ws_bytes below mulut_net_backward_ws_bytes(nf, u, 128) (MULUT_EWORKSPACE). */
+int mulut_net_unit_create_train(int device, int nf, int u, mulut_net_unit **unit);
+int mulut_net_unit_load_dev(mulut_net_unit *unit, const float *const w_dev[6], const float *const b_dev[6], void *stream);
+long long mulut_net_pack_host(int nf, int u, const float *const w[6], const float *const b[6], int backward, float *out, long long cap);
+long long mulut_net_unit_read(const mulut_net_unit *unit, int backward, float *host, long long cap);
+int mulut_net_stage_sum(const mulut_net_unit *const units[], const char *modes, const float *x, int N, int C, int H, int W, float *pred,
+                        void *stream);
+long long mulut_net_backward_ws_bytes(int nf, int u, long long sites);
+int mulut_net_stage_backward(const mulut_net_unit *const units[], const char *modes, const float *x, const float *g, int N, int C, int H,
+                             int W, void *ws, long long ws_bytes, float *gx, float *const gw[], float *const gb[], void *stream);
+
 /* Tuning knobs (never change results).
  * "final_stage_kernel" (scale 4, <= 3 modes): 0 = auto (= 6), 1 = full-table gather kernel, 5 = tube kernel on every tile (the tube
  *   bands of all modes resident in LDS; samples with a pass outside the tube are recomputed from the full table through a device

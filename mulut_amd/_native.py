@@ -8,8 +8,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 _LIBDIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(_LIBDIR, "libmulut_hip.so")
-SOURCES = ["mulut_kernels.hip", "mulut_k1.hip", "mulut_detail.hip", "mulut_interval.hip", "mulut_capi.hip", "mulut_ft.hip", "mulut_ft_interval.hip", "mulut_ft_exact.hip", "mulut_ft_data.hip", "mulut_eval.hip", "mulut_resample.hip", "mulut_net.hip"]
-HEADERS = ["mulut_core.h", "mulut_interval.h", "mulut_ft.h", "mulut_ft_interval.h", "mulut_ft_exact.h", "mulut_kernels.h", "mulut_dev.h", "mulut_net.h", "mulut_tube2_asm.inc", os.path.join("..", "..", "include", "mulut.h")]
+SOURCES = ["mulut_kernels.hip", "mulut_k1.hip", "mulut_detail.hip", "mulut_interval.hip", "mulut_capi.hip", "mulut_ft.hip", "mulut_ft_interval.hip", "mulut_ft_exact.hip", "mulut_ft_data.hip", "mulut_eval.hip", "mulut_resample.hip", "mulut_net.hip", "mulut_net_train.hip"]
+HEADERS = ["mulut_core.h", "mulut_interval.h", "mulut_ft.h", "mulut_ft_interval.h", "mulut_ft_exact.h", "mulut_kernels.h", "mulut_dev.h", "mulut_net.h", "mulut_net_dev.h", "mulut_tube2_asm.inc", os.path.join("..", "..", "include", "mulut.h")]
 # -Wno-inline-asm: stage_tube2_kernel names registers ABOVE the register allocator's budget in its asm clobber lists on purpose
 # (tools/gen_tube2_asm.py); -Wno-pass-failed: its occupancy attribute is that budget, not an occupancy the kernel reaches
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-inline-asm", "-Wno-pass-failed"]
@@ -25,6 +25,8 @@ EXPORTS = [
     "mulut_eval_ws_doubles", "mulut_eval_y", "mulut_eval_plan_create", "mulut_eval_plan_run", "mulut_eval_plan_destroy", "mulut_eval_finish", "mulut_last_detail_counters", "mulut_debug_read",
     "mulut_resample_coeffs", "mulut_resample_plan_create", "mulut_resample_plan_destroy", "mulut_resample_run",
     "mulut_net_unit_create", "mulut_net_unit_destroy", "mulut_net_table", "mulut_net_pass", "mulut_net_stage",
+    "mulut_net_unit_create_train", "mulut_net_unit_load_dev", "mulut_net_unit_read", "mulut_net_pack_host", "mulut_net_stage_sum", "mulut_net_backward_ws_bytes",
+    "mulut_net_stage_backward",
 ]
 
 _libs = {}
@@ -235,5 +237,17 @@ def load(path=None):
                  "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward", "mulut_ft_wide_stage_forward",
                  "mulut_ft_wide_stage_backward", "mulut_ft_crop_batch"):
         getattr(L, name).restype = i
+    L.mulut_net_unit_create_train.argtypes = [i, i, i, ctypes.POINTER(p)]
+    L.mulut_net_unit_load_dev.argtypes = [p, ctypes.POINTER(p), ctypes.POINTER(p), p]
+    L.mulut_net_unit_read.argtypes = [p, i, p, ctypes.c_longlong]
+    L.mulut_net_stage_sum.argtypes = [ctypes.POINTER(p), c_char_p, p, i, i, i, i, p, p]
+    L.mulut_net_backward_ws_bytes.argtypes = [i, i, ctypes.c_longlong]
+    L.mulut_net_stage_backward.argtypes = [ctypes.POINTER(p), c_char_p, p, p, i, i, i, i, p, ctypes.c_longlong, p, ctypes.POINTER(p),
+                                           ctypes.POINTER(p), p]
+    for name in ("mulut_net_unit_create_train", "mulut_net_unit_load_dev", "mulut_net_stage_sum", "mulut_net_stage_backward"):
+        getattr(L, name).restype = i
+    L.mulut_net_pack_host.argtypes = [i, i, fpp, fpp, i, p, ctypes.c_longlong]
+    for name in ("mulut_net_unit_read", "mulut_net_backward_ws_bytes", "mulut_net_pack_host"):
+        getattr(L, name).restype = ctypes.c_longlong
     _libs[path] = L
     return L

@@ -20,14 +20,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/mulut.h"
-#include "mulut_net.h"
-
-struct mulut_net_unit {
-    int device, nf, u, mt;
-    long long floats;
-    float *w;      // device: the packed stream
-};
+#include "mulut_net_dev.h"
 
 namespace mulut {
 
@@ -64,140 +57,6 @@ void net_pack(int nf, int u, const float *const w[6], const float *const b[6], f
             }
         }
     }
-}
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int B, int E, class F>
-__device__ __forceinline__ void net_static_for(F &&f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        net_static_for<B + 1, E>(f);
-    }
-}
-
-// a workgroup's walk down weight streams: chunk 0 of `cur` is in LDS buffer `par` when a site body begins, and chunk 0 of `next`
-// is in buffer `par` (updated) when it ends
-struct NetStream {
-    const float4 *cur, *next;
-    float4 *lds;
-    float4 pf[4], wq;
-    int par, tid, lane;
-};
-
-__device__ __forceinline__ void net_fetch(NetStream &s, const float4 *chunk) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s.pf[j] = chunk[j * kNetNT + s.tid];
-}
-
-__device__ __forceinline__ void net_put(NetStream &s, int c) {
-    float4 *buf = s.lds + ((c & 1) ^ s.par) * kNetChunkVec4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) buf[j * kNetNT + s.tid] = s.pf[j];
-}
-
-// before the first body of a workgroup
-__device__ __forceinline__ void net_stream_begin(NetStream &s, const float4 *first, float4 *lds) {
-    s.lds = lds;
-    s.par = 0;
-    s.tid = (int)threadIdx.x;
-    s.lane = s.tid & 63;
-    net_fetch(s, first);
-    net_put(s, 0);
-    __syncthreads();
-}
-
-template <int MT, int G>
-__device__ __forceinline__ void net_step(NetStream &s, float b, f32x16 &acc) {
-    constexpr int NC = net_chunks(MT), c = G / kNetChunkSteps;
-    if constexpr (G % kNetChunkSteps == 0) {
-        if constexpr (c > 0) {
-            net_put(s, c);      // buffer c & 1 was last read in chunk c - 2: every wave has passed the barrier of chunk c - 1 since
-            __syncthreads();
-        }
-        net_fetch(s, c + 1 < NC ? s.cur + (c + 1) * kNetChunkVec4 : s.next);
-    }
-    if constexpr (G % 4 == 0) s.wq = s.lds[((c & 1) ^ s.par) * kNetChunkVec4 + ((G % kNetChunkSteps) / 4) * 64 + s.lane];
-    const float a = (G & 3) == 0 ? s.wq.x : (G & 3) == 1 ? s.wq.y : (G & 3) == 2 ? s.wq.z : s.wq.w;
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-}
-
-// t0, t1: this lane's tap values of steps 1 and 2 -- (a, c) in lane half 0, (b, d) in half 1.  y[r]: output 8 * h + r (valid below u*u).
-template <int MT, int U>
-__device__ __forceinline__ void net_site_body(NetStream &s, float t0, float t1, float (&y)[8]) {
-    const float one = s.lane < 32 ? 1.0f : 0.0f;
-    f32x16 x[5][MT];
-    net_static_for<1, 6>([&](auto Lc) __attribute__((always_inline)) {
-        constexpr int L = decltype(Lc)::value;
-        net_static_for<0, MT>([&](auto mc) __attribute__((always_inline)) {
-            constexpr int mt = decltype(mc)::value, base = net_step_base(MT, L, mt);
-            f32x16 acc;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
-            net_step<MT, base>(s, one, acc);
-            if constexpr (L == 1) {
-                net_step<MT, base + 1>(s, t0, acc);
-                net_step<MT, base + 2>(s, t1, acc);
-            } else {
-                net_static_for<0, (L - 1) * MT * 16>([&](auto kc) __attribute__((always_inline)) {
-                    constexpr int k = decltype(kc)::value;
-                    net_step<MT, base + 1 + k>(s, x[k / (MT * 16)][(k / 16) % MT][k % 16], acc);
-                });
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) x[L - 1][mt][q] = fmaxf(acc[q], 0.0f);
-        });
-    });
-    constexpr int base6 = net_step_base(MT, 6, 0);
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
-    net_step<MT, base6>(s, one, acc);
-    net_static_for<0, 5 * MT * 16>([&](auto kc) __attribute__((always_inline)) {
-        constexpr int k = decltype(kc)::value;
-        net_step<MT, base6 + 1 + k>(s, x[k / (MT * 16)][(k / 16) % MT][k % 16], acc);
-    });
-    constexpr int NC = net_chunks(MT);
-    net_put(s, NC);
-    __syncthreads();
-    s.par ^= NC & 1;
-    constexpr int RN = U * U < 8 ? U * U : 8;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) y[r] = r < RN ? tanhf(acc[r]) : 0.0f;
-}
-
-// round(127 * y) of sr/1_train_model.py:34-35 and round(clamp(y, -1, 1) * 127) of sr/2_transfer_to_lut.py:108-109: tanh stays inside
-// [-1, 1], the clamp only makes that explicit; torch.round is round-half-even
-__device__ __forceinline__ int net_q127(float y) { return (int)__builtin_rintf(fminf(fmaxf(y, -1.0f), 1.0f) * 127.0f); }
-
-// ---- rotations by index arithmetic.  rot90^r(x)[i][j] = x[net_unrot(r, i, j, H, W)] for an H x W image x (torch.rot90 over dims 2, 3)
-__device__ __forceinline__ void net_unrot(int r, int i, int j, int H, int W, int &y, int &x) {
-    y = r == 0 ? i : r == 1 ? j : r == 2 ? H - 1 - i : H - 1 - j;
-    x = r == 0 ? j : r == 1 ? W - 1 - i : r == 2 ? W - 1 - j : i;
-}
-__device__ __forceinline__ void net_rot(int r, int y, int x, int H, int W, int &i, int &j) {
-    i = r == 0 ? y : r == 1 ? W - 1 - x : r == 2 ? H - 1 - y : x;
-    j = r == 0 ? x : r == 1 ? y : r == 2 ? W - 1 - x : H - 1 - y;
-}
-
-// The two tap values of this lane half for the site that pixel (y, x) of the un-rotated plane is in rotation r: taps k = h and 2 + h
-// of the pattern (`taps`: di | dj << 4 in byte k), replicate-padded on the bottom and right of the ROTATED image (mode_pad_dict)
-__device__ __forceinline__ void net_taps(const unsigned char *plane, int H, int W, int r, int y, int x, unsigned taps, int h, float &t0, float &t1) {
-    int i, j;
-    net_rot(r, y, x, H, W, i, j);
-    const int Hr = (r & 1) ? W : H, Wr = (r & 1) ? H : W;
-    float t[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const unsigned tp = taps >> (8 * (2 * q + h));
-        int ii = i + (int)(tp & 15u), jj = j + (int)((tp >> 4) & 15u), yy, xx;
-        ii = ii < Hr ? ii : Hr - 1;
-        jj = jj < Wr ? jj : Wr - 1;
-        net_unrot(r, ii, jj, H, W, yy, xx);
-        t[q] = (float)plane[yy * W + xx] / 255.0f;
-    }
-    t0 = t[0];
-    t1 = t[1];
 }
 
 // ---- grid form: row i of the table is the site (a, b, c, d) = the base-L digits of i, a slowest
@@ -265,129 +124,13 @@ __global__ void __launch_bounds__(kNetNT) net_pass_kernel(const float4 *w, const
     }
 }
 
-// ---- stage form
-struct NetStageArgs {
-    const float4 *w[MULUT_MAX_MODES];
-    unsigned taps[MULUT_MAX_MODES];
-    const unsigned char *in;
-    unsigned char *out;
-    int M, is_last, H, W, total;
-};
-
-// Integer round-half-even of n / D (D > 0), clipped to a byte.  sr/1_train_model.py:36-43 computes pred / avg_factor + bias in
-// float32 and rounds that.  pred is an integer with |pred| <= 127 * 4 * M and avg_factor D is M or 4 * M <= 32, so the exact quotient
-// is either an integer, a tie (k + 1/2, exactly representable, and so is the sum with the bias 127), or at least 1 / (2 * D) >= 1 / 64
-// away from the nearest tie; float32 carries |pred / D + 127| < 2^10 with an error below 2^-13, which can reach neither.  Hence
-// round-half-even of the rational is the reference's float32 result, bit for bit.
-__device__ __forceinline__ int net_rhe_clip(int n, int D) {
-    int q = n / D, rem = n % D;
-    if (rem < 0) {
-        rem += D;
-        --q;
-    }
-    if (2 * rem > D || (2 * rem == D && (q & 1))) ++q;
-    return q < 0 ? 0 : q > 255 ? 255 : q;
-}
-
-// A lane pair owns pixel (y, x) of the un-rotated image and its U x U output block for the whole stage: in rotation r the site that
-// produces this block is the pixel's own position in the rotated frame, with the block's sub-pixels rotated along.  The integer sums
-// sit in a wave-private LDS tile, [output][site]: in a pass a lane adds the outputs it computed to where they land un-rotated (which
-// may be the other lane half's slot), and LDS operations of a wave execute in order, so no synchronisation beyond program order is
-// needed.
+// ---- stage form (the body is net_stage_body of mulut_net_dev.h)
 template <int MT, int U>
-__global__ void __launch_bounds__(kNetNT) net_stage_kernel(NetStageArgs a) {
+__global__ void __launch_bounds__(kNetNT) net_stage_kernel(NetStageArgs<unsigned char, unsigned char> a) {
     __shared__ float4 lds[2 * kNetChunkVec4];
     __shared__ int sums[kNetWaves][16][kNetTileSites];
-    NetStream s;
-    net_stream_begin(s, a.w[0], lds);
-    const int h = s.lane >> 5, sl = s.lane & 31, wave = s.tid >> 6;
-    const int site = (int)blockIdx.x * kNetSites + wave * kNetTileSites + sl;
-    const int px = site < a.total ? site : a.total - 1;
-    const int H = a.H, W = a.W;
-    const int plane = px / (H * W), y0 = (px % (H * W)) / W, x0 = px % W;
-    const unsigned char *pin = a.in + (long long)plane * H * W;
-    int(*acc)[kNetTileSites] = sums[wave];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) acc[8 * h + q][sl] = 0;
-    for (int m = 0; m < a.M; ++m) {
-        const unsigned taps = a.taps[m];
-        for (int r = 0; r < 4; ++r) {
-            s.cur = a.w[m];
-            s.next = r < 3 ? a.w[m] : a.w[m + 1 < a.M ? m + 1 : m];
-            float t0, t1, y[8];
-            net_taps(pin, H, W, r, y0, x0, taps, h, t0, t1);
-            net_site_body<MT, U>(s, t0, t1, y);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int o = 8 * h + q;
-                if (o < U * U) {
-                    const int si = o / U, sj = o % U;
-                    const int sy = r == 0 ? si : r == 1 ? sj : r == 2 ? U - 1 - si : U - 1 - sj;
-                    const int sx = r == 0 ? sj : r == 1 ? U - 1 - si : r == 2 ? U - 1 - sj : si;
-                    acc[sy * U + sx][sl] += net_q127(y[q]);
-                }
-            }
-        }
-    }
-    if (site >= a.total) return;
-    const int D = a.is_last ? a.M : 4 * a.M, bias = a.is_last ? 0 : 127 * D;
-    unsigned char *po = a.out + (long long)plane * (H * U) * (W * U);
-    if (U == 4 && (reinterpret_cast<uintptr_t>(a.out) & 3) == 0) {
-#pragma unroll
-        for (int row = 0; row < 2; ++row) {
-            unsigned v = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v |= (unsigned)net_rhe_clip(acc[8 * h + 4 * row + q][sl] + bias, D) << (8 * q);
-            *reinterpret_cast<unsigned *>(po + (y0 * 4 + 2 * h + row) * (W * 4) + x0 * 4) = v;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int o = 8 * h + q;
-            if (o < U * U) po[(y0 * U + o / U) * (W * U) + x0 * U + o % U] = (unsigned char)net_rhe_clip(acc[o][sl] + bias, D);
-        }
-    }
+    net_stage_body<MT, U>(a, lds, sums);
 }
-
-// di | dj << 4 per tap a, b, c, d (common/network.py:150-227), or 0xffffffff for an unknown letter
-static unsigned net_pattern(char mode) {
-    switch (mode) {
-        case 's': return 0x11011000u;
-        case 'd': return 0x22022000u;
-        case 'y': return 0x12211100u;
-        case 'e': return 0x33033000u;
-        case 'h': return 0x23322200u;
-        case 'o': return 0x13312200u;
-        default: return 0xffffffffu;
-    }
-}
-
-static int net_image_sites(int N, int C, int H, int W, int u, int *sites) {
-    if (N < 1 || C < 1 || H < 1 || W < 1) return MULUT_EINVAL;
-    const long long px = (long long)N * C;
-    if (px >= (1LL << 31) || (long long)H * W >= (1LL << 31) || px * H * W * u * u >= (1LL << 31)) return MULUT_EUNSUPPORTED;
-    *sites = (int)(px * H * W);
-    return MULUT_OK;
-}
-
-#define MULUT_NET_LAUNCH(kernel, mt, u, ...)                                                               \
-    do {                                                                                                   \
-        if ((mt) == 1) {                                                                                   \
-            switch (u) {                                                                                   \
-                case 1: hipLaunchKernelGGL((kernel<1, 1>), grid, block, 0, st, __VA_ARGS__); break;        \
-                case 2: hipLaunchKernelGGL((kernel<1, 2>), grid, block, 0, st, __VA_ARGS__); break;        \
-                case 3: hipLaunchKernelGGL((kernel<1, 3>), grid, block, 0, st, __VA_ARGS__); break;        \
-                default: hipLaunchKernelGGL((kernel<1, 4>), grid, block, 0, st, __VA_ARGS__); break;       \
-            }                                                                                              \
-        } else {                                                                                           \
-            switch (u) {                                                                                   \
-                case 1: hipLaunchKernelGGL((kernel<2, 1>), grid, block, 0, st, __VA_ARGS__); break;        \
-                case 2: hipLaunchKernelGGL((kernel<2, 2>), grid, block, 0, st, __VA_ARGS__); break;        \
-                case 3: hipLaunchKernelGGL((kernel<2, 3>), grid, block, 0, st, __VA_ARGS__); break;        \
-                default: hipLaunchKernelGGL((kernel<2, 4>), grid, block, 0, st, __VA_ARGS__); break;       \
-            }                                                                                              \
-        }                                                                                                  \
-    } while (0)
 
 }  // namespace mulut
 
@@ -410,7 +153,7 @@ extern "C" int mulut_net_unit_create(int device, int nf, int u, const float *con
     }
     net_pack(nf, u, w, b, host.data());
     if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    mulut_net_unit *p = new (std::nothrow) mulut_net_unit{device, nf, u, mt, floats, nullptr};
+    mulut_net_unit *p = new (std::nothrow) mulut_net_unit{device, nf, u, mt, floats, nullptr, nullptr};
     if (!p) return MULUT_EHIP;
     if (hipMalloc(reinterpret_cast<void **>(&p->w), (size_t)floats * sizeof(float)) != hipSuccess) {
         delete p;
@@ -474,7 +217,7 @@ extern "C" int mulut_net_stage(const mulut_net_unit *const units[], const char *
     const size_t M = strnlen(modes, MULUT_MAX_MODES + 1);
     if (M < 1) return MULUT_EINVAL;
     if (M > MULUT_MAX_MODES) return MULUT_EUNSUPPORTED;
-    NetStageArgs a;
+    NetStageArgs<unsigned char, unsigned char> a;
     memset(&a, 0, sizeof(a));
     for (size_t m = 0; m < M; ++m) {
         if (!units[m]) return MULUT_EINVAL;

@@ -24,9 +24,28 @@ def _dev(t, dtype, name):
     return t
 
 
+def unit_layers(unit):
+    """The six convolutions of a dense MuLUTUnit, conv1..conv6."""
+    if not isinstance(unit.conv2, network.DenseConv):
+        raise MuLUTError("mulut error -5: only dense=True units run on the fused forward")
+    return [unit.conv1.conv] + [c.conv1.conv for c in (unit.conv2, unit.conv3, unit.conv4, unit.conv5)] + [unit.conv6.conv]
+
+
+def unit_param_pointers(unit, device):
+    """(w[6], b[6]) as ctypes arrays of device pointers for mulut_net_unit_load_dev, and the tensors that must outlive the launch."""
+    keep, ws, bs = [], [], []
+    for c in unit_layers(unit):
+        w = c.weight.detach().to(device=device, dtype=torch.float32).contiguous()
+        b = (c.bias.detach() if c.bias is not None else torch.zeros(c.weight.shape[0])).to(device=device, dtype=torch.float32).contiguous()
+        keep += [w, b]
+        ws.append(w.data_ptr())
+        bs.append(b.data_ptr())
+    return (ctypes.c_void_p * 6)(*ws), (ctypes.c_void_p * 6)(*bs), keep
+
+
 class NetEngine:
     """Owns a `mulut_net_unit` per module of `model_G` (an `SRNets`, also one rebuilt by `network.load_checkpoint`).  The weights are
-    read once, here: a later change of the module's parameters is not seen.  Every method takes and returns device tensors and
+    read once, here: a later change of the module's parameters is not seen until `load_weights` packs them anew, on the device.  Every method takes and returns device tensors and
     queues its work on torch's current stream."""
 
     def __init__(self, model_G, device=0, lib_path=None):
@@ -82,6 +101,16 @@ class NetEngine:
         h = ctypes.c_void_p()
         self._check(self._lib.mulut_net_unit_create(self.device.index, nf, u, wp, bp, ctypes.byref(h)))
         return h, u
+
+    def load_weights(self, model_G):
+        """Refresh every unit from the current parameters of `model_G` (the module tree this engine was built from) through the
+        device pack, mulut_net_unit_load_dev: one small launch per unit on the current stream, no host round trip for parameters that
+        live on the device."""
+        for (s, mode), h in self._units.items():
+            wp, bp, keep = unit_param_pointers(getattr(model_G, "s{}_{}".format(s, mode)).model, self.device)
+            self._check(self._lib.mulut_net_unit_load_dev(h, wp, bp, self._stream()))
+            del keep      # (stream-ordered: torch's allocator does not hand the memory out to another stream)
+        return self
 
     def close(self):
         for h in getattr(self, "_units", {}).values():

@@ -87,3 +87,89 @@ class TestOptions:
                 add_baseline_line(test_lut.eltr)
         self.opt = opt
         return opt
+
+
+class TrainOptions:
+    """The reference's training command line (common/option.py:13-31,160-187), flag for flag with its defaults, for
+    ``mulut_amd.train_model``.  ``parse()`` makes ``expDir`` and ``{expDir}/val`` (``opt.valoutDir``), writes ``opt.txt`` as the
+    reference does, applies ``--debug``'s short schedule (:147-151) and, like ``TestOptions``, copies the code only with
+    ``--saveCode``.  Additions default to the reference's behaviour: ``--torchPath``, ``--hostData``, ``--seed``."""
+
+    def __init__(self, debug=False):
+        self.debug = debug
+        self.isTrain = True
+
+    def initialize(self, parser):
+        parser.add_argument('--model', type=str, default='SRNets')
+        parser.add_argument('--task', '-t', type=str, default='sr')
+        parser.add_argument('--scale', '-r', type=int, default=4, help="up scale factor")
+        parser.add_argument('--sigma', '-s', type=int, default=25, help="noise level")
+        parser.add_argument('--qf', '-q', type=int, default=20, help="deblocking quality factor")
+        parser.add_argument('--nf', type=int, default=64, help="number of filters of convolutional layers")
+        parser.add_argument('--stages', type=int, default=2, help="stages of MuLUT")
+        parser.add_argument('--modes', type=str, default='sdy', help="sampling modes to use in every stage")
+        parser.add_argument('--interval', type=int, default=4, help='N bit uniform sampling')
+        parser.add_argument('--modelRoot', type=str, default='../models')
+        parser.add_argument('--expDir', '-e', type=str, default='', help="experiment folder")
+        parser.add_argument('--load_from_opt_file', action='store_true', default=False)
+        parser.add_argument('--debug', default=False, action='store_true')
+        # data
+        parser.add_argument('--batchSize', type=int, default=32)
+        parser.add_argument('--cropSize', type=int, default=48, help='input LR training patch size')
+        parser.add_argument('--trainDir', type=str, default="../data/DIV2K")
+        parser.add_argument('--valDir', type=str, default='../data/SRBenchmark')
+        # training
+        parser.add_argument('--startIter', type=int, default=0,
+                            help='Set 0 for from scratch, else will load saved params and trains further')
+        parser.add_argument('--totalIter', type=int, default=200000, help='Total number of training iterations')
+        parser.add_argument('--displayStep', type=int, default=100, help='display info every N iteration')
+        parser.add_argument('--valStep', type=int, default=2000, help='validate every N iteration')
+        parser.add_argument('--saveStep', type=int, default=2000, help='save models every N iteration')
+        parser.add_argument('--lr0', type=float, default=1e-3)
+        parser.add_argument('--lr1', type=float, default=1e-4)
+        parser.add_argument('--weightDecay', type=float, default=0)
+        parser.add_argument('--gpuNum', '-g', type=int, default=1)
+        parser.add_argument('--workerNum', '-n', type=int, default=8)
+        # additions
+        parser.add_argument('--torchPath', action='store_true', default=False,
+                            help="run the network as torch operators (network.SRNets) instead of the fused HIP kernels: the baseline")
+        parser.add_argument('--hostData', action='store_true', default=False,
+                            help="cut the batches on the host (CropProvider, the reference's path) instead of on the device")
+        parser.add_argument('--seed', type=int, default=None, help="seed of the initial weights and of the crops")
+        parser.add_argument('--saveCode', action='store_true', default=False,
+                            help="copy *.py under cwd into <expDir>/code like the reference's parse()")
+        return parser
+
+    def parse(self, argv=None):
+        parser = self.initialize(argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter))
+        opt = parser.parse_args([] if self.debug else argv)
+        opt.isTrain = True
+        if opt.expDir == '':
+            opt.modelDir = os.path.join(opt.modelRoot, "debug")
+            os.makedirs(opt.modelDir, exist_ok=True)
+            count = 1
+            while os.path.isdir(os.path.join(opt.modelDir, 'expr_{}'.format(count))):
+                count += 1
+            opt.expDir = os.path.join(opt.modelDir, 'expr_{}'.format(count))
+            os.mkdir(opt.expDir)
+        elif not os.path.isdir(opt.expDir):
+            os.makedirs(opt.expDir)
+        opt.modelPath = os.path.join(opt.expDir, "Model.pth")
+        opt.valoutDir = os.path.join(opt.expDir, 'val')
+        os.makedirs(opt.valoutDir, exist_ok=True)
+        with open(os.path.join(opt.expDir, 'opt.txt'), 'wt') as opt_file:          # save_options, common/option.py:66-74
+            for k, v in sorted(vars(opt).items()):
+                default = parser.get_default(k)
+                comment = '\t[default: %s]' % str(default) if v != default else ''
+                opt_file.write('{:>25}: {:<30}{}\n'.format(str(k), str(v), comment))
+        if opt.debug:                                                               # :147-151
+            opt.displayStep, opt.saveStep, opt.valStep, opt.totalIter = 10, 100, 50, 200
+        if opt.saveCode and not opt.debug:
+            import shutil
+            from pathlib import Path
+            for f in Path("./").rglob("*.py"):
+                trg = os.path.join(opt.expDir, "code", f)
+                os.makedirs(os.path.dirname(trg), exist_ok=True)
+                shutil.copy(f, trg, follow_symlinks=False)
+        self.opt = opt
+        return opt
