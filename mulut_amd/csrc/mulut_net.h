@@ -25,6 +25,10 @@ namespace mulut {
 constexpr int kNetWaves = 4, kNetNT = 64 * kNetWaves, kNetTileSites = 32, kNetSites = kNetTileSites * kNetWaves;
 constexpr int kNetChunkSteps = 64, kNetChunkFloats = kNetChunkSteps * 64, kNetChunkVec4 = kNetChunkFloats / 4;
 constexpr int kNetMaxNf = 64, kNetMaxU = 4;
+__host__ __device__ constexpr bool net_unit_ok(int nf, int u) { return nf >= 1 && nf <= kNetMaxNf && u >= 1 && u <= kNetMaxU; }
+// input / output features of layer L (1..6): conv(L) is [net_layer_out][net_layer_in]
+__host__ __device__ constexpr int net_layer_in(int nf, int L) { return L == 1 ? 4 : (L - 1) * nf; }
+__host__ __device__ constexpr int net_layer_out(int nf, int u, int L) { return L == 6 ? u * u : nf; }
 
 __host__ __device__ constexpr int net_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 // steps of one M-tile of layer L (1..6), bias step included
@@ -40,9 +44,6 @@ __host__ __device__ constexpr int net_chunks(int mt_count) { return (net_steps(m
 __host__ __device__ constexpr int net_tiles(int nf) { return nf <= 32 ? 1 : 2; }
 __host__ __device__ constexpr long long net_stream_floats(int mt_count) { return (long long)net_chunks(mt_count) * kNetChunkFloats; }
 __host__ __device__ constexpr long long net_step_float(int g, int lane) { return ((long long)(g >> 2) * 64 + lane) * 4 + (g & 3); }
-
-// the host pack (mulut_net.hip): `out` has net_stream_floats(net_tiles(nf)) floats; w[l] / b[l] are conv(l+1) as [out][in] / [out]
-void net_pack(int nf, int u, const float *const w[6], const float *const b[6], float *out);
 
 // ---- the backward stream (mulut_net_train.hip): the transposed weights in the same step format, for G^T = W^T * D^T.
 //
@@ -68,11 +69,21 @@ __host__ __device__ constexpr int net_bwd_steps(int mt_count) { return net_bwd_s
 __host__ __device__ constexpr int net_bwd_chunks(int mt_count) { return (net_bwd_steps(mt_count) + kNetChunkSteps - 1) / kNetChunkSteps; }
 __host__ __device__ constexpr long long net_bwd_stream_floats(int mt_count) { return (long long)net_bwd_chunks(mt_count) * kNetChunkFloats; }
 
-// What both streams hold at (step g, lane), computed rather than scattered: the device pack runs one thread per float of a stream,
-// and the host pack of the backward stream is a loop over the same function.  w[l] / b[l] as for net_pack.
+// What both streams hold at (step g, lane), computed rather than scattered: these two functions ARE the streams' definition.  The device
+// pack runs one thread per float of a stream and the host packs, net_pack and net_pack_bwd below, are loops over them.  w[l] / b[l] are conv(l+1) as
+// [out][in] / [out]; the backward stream reads no bias.
 struct NetParams {
     const float *w[6], *b[6];
 };
+// false if a pointer is missing
+inline bool net_have_params(const float *const w[6], const float *const b[6]) {
+    if (!w || !b) return false;
+    for (int l = 0; l < 6; ++l)
+        if (!w[l] || !b[l]) return false;
+    return true;
+}
+// (Both spell a layer's input features out, 4 or (L - 1) * nf, and do not call net_layer_in: net_pack_kernel inlines them, and with
+// the call its instructions are no longer the ones that were measured.)
 __host__ __device__ inline float net_fwd_value(int nf, int u, int MT, int g, int lane, const NetParams &p) {
     const int i = lane & 31, h = lane >> 5;
     int base = 0;
@@ -120,7 +131,21 @@ __host__ __device__ inline float net_bwd_value(int nf, int u, int MT, int g, int
     }
     return 0.0f;
 }
-void net_pack_bwd(int nf, int u, const float *const w[6], float *out);
+// the host packs, each a loop over its stream's function: `out` has net_stream_floats / net_bwd_stream_floats(net_tiles(nf)) floats
+inline void net_pack(int nf, int u, const float *const w[6], const float *const b[6], float *out) {
+    const int MT = net_tiles(nf);
+    NetParams p;
+    for (int l = 0; l < 6; ++l) p.w[l] = w[l], p.b[l] = b[l];
+    for (int g = 0; g < net_chunks(MT) * kNetChunkSteps; ++g)
+        for (int lane = 0; lane < 64; ++lane) out[net_step_float(g, lane)] = net_fwd_value(nf, u, MT, g, lane, p);
+}
+inline void net_pack_bwd(int nf, int u, const float *const w[6], float *out) {
+    const int MT = net_tiles(nf);
+    NetParams p;
+    for (int l = 0; l < 6; ++l) p.w[l] = w[l], p.b[l] = nullptr;
+    for (int g = 0; g < net_bwd_chunks(MT) * kNetChunkSteps; ++g)
+        for (int lane = 0; lane < 64; ++lane) out[net_step_float(g, lane)] = net_bwd_value(nf, u, MT, g, lane, p);
+}
 
 // ---- the workspace of the backward (mulut_net_train.hip), one (mode, rotation) pass of a chunk of `cs` sites (a multiple of 128):
 // float [rows][cs], a row being one feature and the site the fast index, behind kNetGradSplits partial copies of the unit's gradient.
@@ -135,7 +160,11 @@ void net_pack_bwd(int nf, int u, const float *const w[6], float *out);
 constexpr int kNetGradSplits = 16;
 __host__ __device__ constexpr int net_ws_rows(int nf, int u) { return 4 + 10 * nf + u * u; }
 // floats of one copy of a unit's gradient: dW_1..dW_6 as [out][in], then db_1..db_6
-__host__ __device__ constexpr int net_param_floats(int nf, int u) { return nf * 4 + nf * nf * 10 + u * u * 5 * nf + 5 * nf + u * u; }
+__host__ __device__ constexpr int net_param_floats(int nf, int u) {
+    int n = 0;
+    for (int L = 1; L <= 6; ++L) n += net_layer_out(nf, u, L) * (net_layer_in(nf, L) + 1);
+    return n;
+}
 
 }  // namespace mulut
 #endif

@@ -24,41 +24,6 @@
 
 namespace mulut {
 
-void net_pack(int nf, int u, const float *const w[6], const float *const b[6], float *out) {
-    const int MT = net_tiles(nf);
-    memset(out, 0, (size_t)net_stream_floats(MT) * sizeof(float));
-    for (int L = 1; L <= 6; ++L) {
-        const int tiles = L == 6 ? 1 : MT, in_f = L == 1 ? 4 : (L - 1) * nf;
-        const float *W = w[L - 1], *B = b[L - 1];
-        for (int mt = 0; mt < tiles; ++mt) {
-            const int base = net_step_base(MT, L, mt);
-            for (int lane = 0; lane < 64; ++lane) {
-                const int i = lane & 31, h = lane >> 5;
-                int out_row;      // the logical output this lane's A row feeds, or -1: padding
-                if (L < 6) {
-                    out_row = mt * 32 + i < nf ? mt * 32 + i : -1;
-                } else {
-                    const int hh = (i >> 2) & 1, r = (i & 3) + 4 * (i >> 3);      // i = net_row(r, hh)
-                    out_row = r < 8 && 8 * hh + r < u * u ? 8 * hh + r : -1;
-                }
-                if (out_row < 0) continue;
-                if (h == 0) out[net_step_float(base, lane)] = B[out_row];
-                if (L == 1) {
-                    out[net_step_float(base + 1, lane)] = W[out_row * 4 + h];
-                    out[net_step_float(base + 2, lane)] = W[out_row * 4 + 2 + h];
-                    continue;
-                }
-                for (int s = 0; s < L - 1; ++s)
-                    for (int t = 0; t < MT; ++t)
-                        for (int reg = 0; reg < 16; ++reg) {
-                            const int f = t * 32 + net_row(reg, h);
-                            if (f < nf) out[net_step_float(base + 1 + (s * MT + t) * 16 + reg, lane)] = W[(size_t)out_row * in_f + s * nf + f];
-                        }
-            }
-        }
-    }
-}
-
 // ---- grid form: row i of the table is the site (a, b, c, d) = the base-L digits of i, a slowest
 template <int MT, int U>
 __global__ void __launch_bounds__(kNetNT) net_table_kernel(const float4 *w, signed char *rows, int L, int interval, int total) {
@@ -139,33 +104,16 @@ extern "C" int mulut_net_unit_create(int device, int nf, int u, const float *con
     using namespace mulut;
     if (!out) return MULUT_EINVAL;
     *out = nullptr;
-    if (!w || !b) return MULUT_EINVAL;
-    for (int l = 0; l < 6; ++l)
-        if (!w[l] || !b[l]) return MULUT_EINVAL;
-    if (nf < 1 || nf > kNetMaxNf || u < 1 || u > kNetMaxU) return MULUT_EUNSUPPORTED;
-    const int mt = net_tiles(nf);
-    const long long floats = net_stream_floats(mt);
+    if (!net_have_params(w, b)) return MULUT_EINVAL;
+    if (!net_unit_ok(nf, u)) return MULUT_EUNSUPPORTED;
     std::vector<float> host;
     try {
-        host.resize((size_t)floats);
+        host.resize((size_t)net_stream_floats(net_tiles(nf)));
     } catch (const std::bad_alloc &) {
         return MULUT_EUNSUPPORTED;
     }
     net_pack(nf, u, w, b, host.data());
-    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    mulut_net_unit *p = new (std::nothrow) mulut_net_unit{device, nf, u, mt, floats, nullptr, nullptr};
-    if (!p) return MULUT_EHIP;
-    if (hipMalloc(reinterpret_cast<void **>(&p->w), (size_t)floats * sizeof(float)) != hipSuccess) {
-        delete p;
-        return MULUT_EHIP;
-    }
-    if (hipMemcpy(p->w, host.data(), (size_t)floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(p->w);
-        delete p;
-        return MULUT_EHIP;
-    }
-    *out = p;
-    return MULUT_OK;
+    return net_unit_new(device, nf, u, host.data(), out);
 }
 
 extern "C" int mulut_net_unit_destroy(mulut_net_unit *unit) {
@@ -184,10 +132,8 @@ extern "C" int mulut_net_table(const mulut_net_unit *unit, int interval, int8_t 
     if (interval < 4 || interval > 6) return MULUT_EUNSUPPORTED;
     const int L = (256 >> interval) + 1, total = L * L * L * L;
     if (hipSetDevice(unit->device) != hipSuccess) return MULUT_ENODEVICE;
-    const dim3 grid((unsigned)((total + kNetSites - 1) / kNetSites)), block(kNetNT);
-    hipStream_t st = (hipStream_t)stream;
     const float4 *w = reinterpret_cast<const float4 *>(unit->w);
-    MULUT_NET_LAUNCH(net_table_kernel, unit->mt, unit->u, w, reinterpret_cast<signed char *>(rows_dev), L, interval, total);
+    MULUT_NET_LAUNCH(net_table_kernel, unit->mt, unit->u, total, stream, w, reinterpret_cast<signed char *>(rows_dev), L, interval, total);
     return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }
 
@@ -202,10 +148,8 @@ extern "C" int mulut_net_pass(const mulut_net_unit *unit, char mode, int r, cons
     const int rc = net_image_sites(N, C, H, W, unit->u, &total);
     if (rc != MULUT_OK) return rc;
     if (hipSetDevice(unit->device) != hipSuccess) return MULUT_ENODEVICE;
-    const dim3 grid((unsigned)(((long long)total + kNetSites - 1) / kNetSites)), block(kNetNT);
-    hipStream_t st = (hipStream_t)stream;
     const float4 *w = reinterpret_cast<const float4 *>(unit->w);
-    MULUT_NET_LAUNCH(net_pass_kernel, unit->mt, unit->u, w, in, reinterpret_cast<signed char *>(out), H, W, r, taps, total);
+    MULUT_NET_LAUNCH(net_pass_kernel, unit->mt, unit->u, total, stream, w, in, reinterpret_cast<signed char *>(out), H, W, r, taps, total);
     return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }
 
@@ -214,30 +158,19 @@ extern "C" int mulut_net_stage(const mulut_net_unit *const units[], const char *
                                int C, int H, int W, void *stream) {
     using namespace mulut;
     if (!units || !modes || !in || !out) return MULUT_EINVAL;
-    const size_t M = strnlen(modes, MULUT_MAX_MODES + 1);
-    if (M < 1) return MULUT_EINVAL;
-    if (M > MULUT_MAX_MODES) return MULUT_EUNSUPPORTED;
     NetStageArgs<unsigned char, unsigned char> a;
     memset(&a, 0, sizeof(a));
-    for (size_t m = 0; m < M; ++m) {
-        if (!units[m]) return MULUT_EINVAL;
-        a.taps[m] = net_pattern(modes[m]);
-        if (a.taps[m] == 0xffffffffu) return MULUT_EINVAL;
-        if (units[m]->u != units[0]->u || units[m]->mt != units[0]->mt || units[m]->device != units[0]->device) return MULUT_ESHAPE;
-        a.w[m] = reinterpret_cast<const float4 *>(units[m]->w);
-    }
+    int rc = net_stage_units(units, modes, 0, a.w, a.taps, &a.M);
+    if (rc != MULUT_OK) return rc;
     const int u = units[0]->u, mt = units[0]->mt;
-    const int rc = net_image_sites(N, C, H, W, u, &a.total);
+    rc = net_image_sites(N, C, H, W, u, &a.total);
     if (rc != MULUT_OK) return rc;
     a.in = in;
     a.out = out;
-    a.M = (int)M;
     a.is_last = is_last ? 1 : 0;
     a.H = H;
     a.W = W;
     if (hipSetDevice(units[0]->device) != hipSuccess) return MULUT_ENODEVICE;
-    const dim3 grid((unsigned)(((long long)a.total + kNetSites - 1) / kNetSites)), block(kNetNT);
-    hipStream_t st = (hipStream_t)stream;
-    MULUT_NET_LAUNCH(net_stage_kernel, mt, u, a);
+    MULUT_NET_LAUNCH(net_stage_kernel, mt, u, a.total, stream, a);
     return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }

@@ -1,11 +1,13 @@
-// mulut_net_dev.h -- the device half that mulut_net.hip (inference forms) and mulut_net_train.hip (training forms) share: the unit, the
-// walk down a weight stream, the site body, the rotations' index arithmetic, the taps and the stage loop.
+// mulut_net_dev.h -- what mulut_net.hip (inference forms) and mulut_net_train.hip (training forms) share: the unit and its allocation,
+// the walk down a weight stream, the site body, the rotations' index arithmetic, the taps, the stage loop, and the stage calls' argument
+// checks and launch.
 #ifndef MULUT_NET_DEV_H_
 #define MULUT_NET_DEV_H_
 
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <new>
 #include <type_traits>
 
 #include "../../include/mulut.h"
@@ -303,23 +305,44 @@ inline int net_stage_units(const mulut_net_unit *const units[], const char *mode
     return MULUT_OK;
 }
 
-#define MULUT_NET_LAUNCH(kernel, mt, u, ...)                                                               \
-    do {                                                                                                   \
-        if ((mt) == 1) {                                                                                   \
-            switch (u) {                                                                                   \
-                case 1: hipLaunchKernelGGL((kernel<1, 1>), grid, block, 0, st, __VA_ARGS__); break;        \
-                case 2: hipLaunchKernelGGL((kernel<1, 2>), grid, block, 0, st, __VA_ARGS__); break;        \
-                case 3: hipLaunchKernelGGL((kernel<1, 3>), grid, block, 0, st, __VA_ARGS__); break;        \
-                default: hipLaunchKernelGGL((kernel<1, 4>), grid, block, 0, st, __VA_ARGS__); break;       \
-            }                                                                                              \
-        } else {                                                                                           \
-            switch (u) {                                                                                   \
-                case 1: hipLaunchKernelGGL((kernel<2, 1>), grid, block, 0, st, __VA_ARGS__); break;        \
-                case 2: hipLaunchKernelGGL((kernel<2, 2>), grid, block, 0, st, __VA_ARGS__); break;        \
-                case 3: hipLaunchKernelGGL((kernel<2, 3>), grid, block, 0, st, __VA_ARGS__); break;        \
-                default: hipLaunchKernelGGL((kernel<2, 4>), grid, block, 0, st, __VA_ARGS__); break;       \
-            }                                                                                              \
-        }                                                                                                  \
+// One allocation per unit: the forward stream, uploaded from `host`, or (host NULL: a training unit) both streams, zeroed.
+// mulut_net_unit_destroy frees w.
+inline int net_unit_new(int device, int nf, int u, const float *host, mulut_net_unit **out) {
+    const int mt = net_tiles(nf);
+    const long long floats = net_stream_floats(mt);
+    const size_t bytes = (size_t)(floats + (host ? 0 : net_bwd_stream_floats(mt))) * sizeof(float);
+    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
+    mulut_net_unit *p = new (std::nothrow) mulut_net_unit{device, nf, u, mt, floats, nullptr, nullptr};
+    if (!p) return MULUT_EHIP;
+    if (hipMalloc(reinterpret_cast<void **>(&p->w), bytes) != hipSuccess) {
+        delete p;
+        return MULUT_EHIP;
+    }
+    if ((host ? hipMemcpy(p->w, host, bytes, hipMemcpyHostToDevice) : hipMemset(p->w, 0, bytes)) != hipSuccess) {
+        (void)hipFree(p->w);
+        delete p;
+        return MULUT_EHIP;
+    }
+    if (!host) p->wb = p->w + floats;
+    *out = p;
+    return MULUT_OK;
+}
+
+// kernel<MT, U> over `sites` sites, one workgroup per kNetSites of them, on `stream`
+#define MULUT_NET_LAUNCH_U(kernel, MT, U, sites, stream, ...)                                                           \
+    hipLaunchKernelGGL((kernel<MT, U>), dim3((unsigned)(((long long)(sites) + kNetSites - 1) / kNetSites)), dim3(kNetNT), 0, \
+                       (hipStream_t)(stream), __VA_ARGS__)
+#define MULUT_NET_LAUNCH_MT(kernel, MT, u, sites, stream, ...)                                   \
+    switch (u) {                                                                                 \
+        case 1: MULUT_NET_LAUNCH_U(kernel, MT, 1, sites, stream, __VA_ARGS__); break;            \
+        case 2: MULUT_NET_LAUNCH_U(kernel, MT, 2, sites, stream, __VA_ARGS__); break;            \
+        case 3: MULUT_NET_LAUNCH_U(kernel, MT, 3, sites, stream, __VA_ARGS__); break;            \
+        default: MULUT_NET_LAUNCH_U(kernel, MT, 4, sites, stream, __VA_ARGS__); break;           \
+    }
+#define MULUT_NET_LAUNCH(kernel, mt, u, sites, stream, ...)                                      \
+    do {                                                                                         \
+        if ((mt) == 1) MULUT_NET_LAUNCH_MT(kernel, 1, u, sites, stream, __VA_ARGS__)             \
+        else MULUT_NET_LAUNCH_MT(kernel, 2, u, sites, stream, __VA_ARGS__)                       \
     } while (0)
 
 }  // namespace mulut

@@ -16,20 +16,9 @@
 //                         in wave order and the result is added to the split's own copy of the gradient.  No atomics.
 // After the four rotations of a unit net_wgrad_reduce_kernel adds the kNetGradSplits copies in index order into gw / gb, so these are
 // bit-identical from run to run (gx is not: float atomics).
-#include <new>
-
 #include "mulut_net_dev.h"
 
 namespace mulut {
-
-void net_pack_bwd(int nf, int u, const float *const w[6], float *out) {
-    const int MT = net_tiles(nf);
-    NetParams p;
-    for (int l = 0; l < 6; ++l) p.w[l] = w[l], p.b[l] = nullptr;
-    const int steps = net_bwd_chunks(MT) * kNetChunkSteps;
-    for (int g = 0; g < steps; ++g)
-        for (int lane = 0; lane < 64; ++lane) out[net_step_float(g, lane)] = net_bwd_value(nf, u, MT, g, lane, p);
-}
 
 // one thread per float of either stream
 __global__ void __launch_bounds__(256) net_pack_kernel(NetParams p, int nf, int u, int MT, float *fwd, int fwd_floats, float *bwd, int bwd_floats) {
@@ -159,21 +148,18 @@ struct NetWgradArgs {
 // the (layer, out tile, in tile) pairs of a unit; the last in tile of a layer is the bias (B = 1)
 __host__ __device__ inline int net_wgrad_pairs(int nf, int u) {
     int n = 0;
-    for (int L = 1; L <= 6; ++L) {
-        const int out_f = L == 6 ? u * u : nf, in_f = L == 1 ? 4 : (L - 1) * nf;
-        n += ((out_f + 31) / 32) * ((in_f + 31) / 32 + 1);
-    }
+    for (int L = 1; L <= 6; ++L) n += ((net_layer_out(nf, u, L) + 31) / 32) * ((net_layer_in(nf, L) + 31) / 32 + 1);
     return n;
 }
 
 __global__ void __launch_bounds__(kNetNT) net_wgrad_kernel(NetWgradArgs a) {
     __shared__ float red[kNetWaves - 1][16][64];
-    const int nf = a.nf, uu = a.u * a.u;
+    const int nf = a.nf, u = a.u;
     int p = (int)blockIdx.x, L = 1, out_f = nf, in_f = 4, IT = 2, off_w = 0, off_b = 0;
-    for (int l = 1; l <= 6; ++l) off_b += (l == 6 ? uu : nf) * (l == 1 ? 4 : (l - 1) * nf);
+    for (int l = 1; l <= 6; ++l) off_b += net_layer_out(nf, u, l) * net_layer_in(nf, l);
     for (;; ++L) {
-        out_f = L == 6 ? uu : nf;
-        in_f = L == 1 ? 4 : (L - 1) * nf;
+        out_f = net_layer_out(nf, u, L);
+        in_f = net_layer_in(nf, L);
         IT = (in_f + 31) / 32 + 1;
         const int n = ((out_f + 31) / 32) * IT;
         if (p < n) break;
@@ -257,33 +243,15 @@ extern "C" int mulut_net_unit_create_train(int device, int nf, int u, mulut_net_
     using namespace mulut;
     if (!out) return MULUT_EINVAL;
     *out = nullptr;
-    if (nf < 1 || nf > kNetMaxNf || u < 1 || u > kNetMaxU) return MULUT_EUNSUPPORTED;
-    const int mt = net_tiles(nf);
-    const long long floats = net_stream_floats(mt), bfloats = net_bwd_stream_floats(mt);
-    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
-    mulut_net_unit *p = new (std::nothrow) mulut_net_unit{device, nf, u, mt, floats, nullptr, nullptr};
-    if (!p) return MULUT_EHIP;
-    if (hipMalloc(reinterpret_cast<void **>(&p->w), (size_t)(floats + bfloats) * sizeof(float)) != hipSuccess) {
-        delete p;
-        return MULUT_EHIP;
-    }
-    if (hipMemset(p->w, 0, (size_t)(floats + bfloats) * sizeof(float)) != hipSuccess) {
-        (void)hipFree(p->w);
-        delete p;
-        return MULUT_EHIP;
-    }
-    p->wb = p->w + floats;      // one allocation: mulut_net_unit_destroy frees w
-    *out = p;
-    return MULUT_OK;
+    if (!net_unit_ok(nf, u)) return MULUT_EUNSUPPORTED;
+    return net_unit_new(device, nf, u, nullptr, out);
 }
 
 /* the host packs, for tests of the device pack: the stream mulut_net_unit_create uploads (backward 0) or the backward stream (1) */
 extern "C" long long mulut_net_pack_host(int nf, int u, const float *const w[6], const float *const b[6], int backward, float *out, long long cap) {
     using namespace mulut;
-    if (!w || !b || !out || backward < 0 || backward > 1) return MULUT_EINVAL;
-    for (int l = 0; l < 6; ++l)
-        if (!w[l] || !b[l]) return MULUT_EINVAL;
-    if (nf < 1 || nf > kNetMaxNf || u < 1 || u > kNetMaxU) return MULUT_EUNSUPPORTED;
+    if (!net_have_params(w, b) || !out || backward < 0 || backward > 1) return MULUT_EINVAL;
+    if (!net_unit_ok(nf, u)) return MULUT_EUNSUPPORTED;
     const long long n = backward ? net_bwd_stream_floats(net_tiles(nf)) : net_stream_floats(net_tiles(nf));
     if (cap < n) return MULUT_EWORKSPACE;
     if (backward) net_pack_bwd(nf, u, w, out);
@@ -293,13 +261,9 @@ extern "C" long long mulut_net_pack_host(int nf, int u, const float *const w[6],
 
 extern "C" int mulut_net_unit_load_dev(mulut_net_unit *unit, const float *const w_dev[6], const float *const b_dev[6], void *stream) {
     using namespace mulut;
-    if (!unit || !w_dev || !b_dev) return MULUT_EINVAL;
+    if (!unit || !net_have_params(w_dev, b_dev)) return MULUT_EINVAL;
     NetParams p;
-    for (int l = 0; l < 6; ++l) {
-        if (!w_dev[l] || !b_dev[l]) return MULUT_EINVAL;
-        p.w[l] = w_dev[l];
-        p.b[l] = b_dev[l];
-    }
+    for (int l = 0; l < 6; ++l) p.w[l] = w_dev[l], p.b[l] = b_dev[l];
     if (hipSetDevice(unit->device) != hipSuccess) return MULUT_ENODEVICE;
     const int ff = (int)unit->floats, bf = unit->wb ? (int)net_bwd_stream_floats(unit->mt) : 0;
     hipLaunchKernelGGL(net_pack_kernel, dim3((unsigned)((ff + bf + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, unit->nf, unit->u, unit->mt,
@@ -336,16 +300,14 @@ extern "C" int mulut_net_stage_sum(const mulut_net_unit *const units[], const ch
     a.H = H;
     a.W = W;
     if (hipSetDevice(units[0]->device) != hipSuccess) return MULUT_ENODEVICE;
-    const dim3 grid((unsigned)(((long long)a.total + kNetSites - 1) / kNetSites)), block(kNetNT);
-    hipStream_t st = (hipStream_t)stream;
-    MULUT_NET_LAUNCH(net_stage_sum_kernel, mt, u, a);
+    MULUT_NET_LAUNCH(net_stage_sum_kernel, mt, u, a.total, stream, a);
     return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }
 
 extern "C" long long mulut_net_backward_ws_bytes(int nf, int u, long long sites) {
     using namespace mulut;
     if (sites < 1) return MULUT_EINVAL;
-    if (nf < 1 || nf > kNetMaxNf || u < 1 || u > kNetMaxU || sites >= (1LL << 31)) return MULUT_EUNSUPPORTED;
+    if (!net_unit_ok(nf, u) || sites >= (1LL << 31)) return MULUT_EUNSUPPORTED;
     const long long cs = (sites + kNetSites - 1) / kNetSites * kNetSites;
     return net_partial_bytes(nf, u) + cs * net_ws_rows(nf, u) * (long long)sizeof(float);
 }
@@ -391,15 +353,11 @@ extern "C" int mulut_net_stage_backward(const mulut_net_unit *const units[], con
             }
         NetGradOut o;
         int end = 0;
-        for (int l = 0; l < 6; ++l) {
-            end += (l == 5 ? u * u : nf) * (l == 0 ? 4 : l * nf);
-            o.p[l] = gw[6 * m + l];
-            o.end[l] = end;
-        }
-        for (int l = 0; l < 6; ++l) {
-            end += l == 5 ? u * u : nf;
-            o.p[6 + l] = gb[6 * m + l];
-            o.end[6 + l] = end;
+        for (int k = 0; k < 12; ++k) {      // dW_1..dW_6, then db_1..db_6
+            const int L = k % 6 + 1;
+            end += net_layer_out(nf, u, L) * (k < 6 ? net_layer_in(nf, L) : 1);
+            o.p[k] = (k < 6 ? gw : gb)[6 * m + k % 6];
+            o.end[k] = end;
         }
         hipLaunchKernelGGL(net_wgrad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, partial, P, o);
     }

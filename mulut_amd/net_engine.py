@@ -31,6 +31,41 @@ def unit_layers(unit):
     return [unit.conv1.conv] + [c.conv1.conv for c in (unit.conv2, unit.conv3, unit.conv4, unit.conv5)] + [unit.conv6.conv]
 
 
+def layer_shapes(nf, u):
+    """(out, in) of conv1..conv6 of a dense unit: net_layer_out / net_layer_in of csrc/mulut_net.h."""
+    return [(u * u if L == 6 else nf, 4 if L == 1 else (L - 1) * nf) for L in range(1, 7)]
+
+
+def discover(model_G, need_bias=False):
+    """The `s{stage}_{mode}` units of an `SRNets`, validated; needs no GPU and no library.  Returns (mods, stages, modes, shape):
+    mods[(stage, mode)] is the SRNet, modes the letters of stage 1 in the module's own order (the order they were added in), which
+    every stage must hold, and shape[(stage, mode)] = (nf, u) of a unit whose six layers are those of a dense unit.  A layer without a
+    bias is refused if `need_bias` (training) and otherwise read as zeros."""
+    mods = {}
+    for name, mod in model_G.named_children():
+        m = _MODULE.match(name)
+        if m and isinstance(getattr(mod, "model", None), network.MuLUTUnit):
+            mods[(int(m.group(1)), m.group(2))] = mod
+    if not mods:
+        raise MuLUTError("no s{stage}_{mode} module found: the network is to be an SRNets")
+    stages = max(s for s, _ in mods)
+    modes = "".join(m for s, m in mods if s == 1)
+    for s in range(1, stages + 1):
+        if "".join(m for t, m in mods if t == s) != modes:
+            raise MuLUTError("stage %d does not hold the modes %r of stage 1" % (s, modes))
+    shape = {}
+    for key, mod in mods.items():
+        layers = unit_layers(mod.model)
+        nf, u = int(layers[0].out_channels), int(mod.model.upscale)
+        got = [(c.weight.shape[0], c.weight[0].numel()) for c in layers]
+        if got != layer_shapes(nf, u):
+            raise MuLUTError("mulut error -4: layer shapes %r of %s are not those of a dense unit, %r" % (got, mod.mode, layer_shapes(nf, u)))
+        if need_bias and any(c.bias is None for c in layers):
+            raise MuLUTError("mulut error -4: a layer of %s has no bias: training wants a dense unit with biases" % mod.mode)
+        shape[key] = (nf, u)
+    return mods, stages, modes, shape
+
+
 def unit_param_pointers(unit, device):
     """(w[6], b[6]) as ctypes arrays of device pointers for mulut_net_unit_load_dev, and the tensors that must outlive the launch."""
     keep, ws, bs = [], [], []
@@ -43,79 +78,43 @@ def unit_param_pointers(unit, device):
     return (ctypes.c_void_p * 6)(*ws), (ctypes.c_void_p * 6)(*bs), keep
 
 
-class NetEngine:
-    """Owns a `mulut_net_unit` per module of `model_G` (an `SRNets`, also one rebuilt by `network.load_checkpoint`).  The weights are
-    read once, here: a later change of the module's parameters is not seen until `load_weights` packs them anew, on the device.  Every method takes and returns device tensors and
-    queues its work on torch's current stream."""
+class NetUnits:
+    """The `mulut_net_unit` handles of `discover(model_G)` on `device`, under NetEngine and NetTrainer.  train False: each unit is
+    created from the module's weights as they are now, packed on the host (mulut_net_unit_create); True: both streams, zeroed
+    (mulut_net_unit_create_train), to be filled by `load`."""
 
-    def __init__(self, model_G, device=0, lib_path=None):
-        self._lib = _native.load(lib_path)
-        self._units, self._u = {}, {}
-        if not torch.cuda.is_available():
-            raise MuLUTError("no GPU visible: mulut_amd has no CPU path")
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
-        found = {}
-        for name, mod in model_G.named_children():
-            m = _MODULE.match(name)
-            if m and isinstance(getattr(mod, "model", None), network.MuLUTUnit):
-                found[(int(m.group(1)), m.group(2))] = mod
-        if not found:
-            raise MuLUTError("no s{stage}_{mode} module found: NetEngine wants an SRNets")
-        self.stages = max(s for s, _ in found)
-        self.modes = "".join(m for s, m in found if s == 1)      # in the module's own order, which is the order they were added in
-        self.scale = None
-        for s in range(1, self.stages + 1):
-            if "".join(m for t, m in found if t == s) != self.modes:
-                raise MuLUTError("stage %d does not hold the modes %r of stage 1" % (s, self.modes))
+    def __init__(self, model_G, device, train=False, lib_path=None):
+        self._h = {}
+        self.mods, self.stages, self.modes, self.shape = discover(model_G, train)
+        self.lib, self.device = _native.load(lib_path), device
         try:
-            for (s, mode), mod in found.items():
-                self._units[(s, mode)], self._u[(s, mode)] = self._create(mod)
+            for key, mod in self.mods.items():
+                self._h[key] = self._create(mod.model, *self.shape[key], train)
         except Exception:
             self.close()
             raise
-        us = {s: {self._u[(s, m)] for m in self.modes} for s in range(1, self.stages + 1)}
-        if any(len(v) != 1 for v in us.values()):
-            self.close()
-            raise MuLUTError("mulut error -4: the units of a stage differ in upscale")
-        self.scale = int(np.prod([next(iter(v)) for v in us.values()]))
 
-    # -- plumbing ---------------------------------------------------------------------------
-    def _check(self, rc):
-        _native.check(rc, MuLUTError)
+    def check(self, rc):
+        return _native.check(rc, MuLUTError)
 
-    def _create(self, srnet):
-        unit = srnet.model
-        if not isinstance(unit.conv2, network.DenseConv):
-            raise MuLUTError("mulut error -5: only dense=True units run on the fused forward")
-        nf, u = int(unit.conv1.conv.out_channels), int(unit.upscale)
-        layers = [unit.conv1.conv] + [c.conv1.conv for c in (unit.conv2, unit.conv3, unit.conv4, unit.conv5)] + [unit.conv6.conv]
+    def _create(self, unit, nf, u, train):
+        h = ctypes.c_void_p()
+        if train:
+            self.check(self.lib.mulut_net_unit_create_train(self.device.index, nf, u, ctypes.byref(h)))
+            return h
+        layers, fp = unit_layers(unit), ctypes.POINTER(ctypes.c_float)
         ws = [np.ascontiguousarray(c.weight.detach().cpu().numpy().reshape(c.weight.shape[0], -1), dtype=np.float32) for c in layers]
         bs = [np.ascontiguousarray((c.bias.detach().cpu().numpy() if c.bias is not None else np.zeros(c.weight.shape[0])), dtype=np.float32)
               for c in layers]
-        want = [(nf, 4)] + [(nf, nf * k) for k in (1, 2, 3, 4)] + [(u * u, 5 * nf)]
-        if [w.shape for w in ws] != want:
-            raise MuLUTError("mulut error -4: layer shapes %r are not those of a dense unit, %r" % ([w.shape for w in ws], want))
-        fp = ctypes.POINTER(ctypes.c_float)
         wp = (fp * 6)(*[w.ctypes.data_as(fp) for w in ws])
         bp = (fp * 6)(*[b.ctypes.data_as(fp) for b in bs])
-        h = ctypes.c_void_p()
-        self._check(self._lib.mulut_net_unit_create(self.device.index, nf, u, wp, bp, ctypes.byref(h)))
-        return h, u
-
-    def load_weights(self, model_G):
-        """Refresh every unit from the current parameters of `model_G` (the module tree this engine was built from) through the
-        device pack, mulut_net_unit_load_dev: one small launch per unit on the current stream, no host round trip for parameters that
-        live on the device."""
-        for (s, mode), h in self._units.items():
-            wp, bp, keep = unit_param_pointers(getattr(model_G, "s{}_{}".format(s, mode)).model, self.device)
-            self._check(self._lib.mulut_net_unit_load_dev(h, wp, bp, self._stream()))
-            del keep      # (stream-ordered: torch's allocator does not hand the memory out to another stream)
-        return self
+        self.check(self.lib.mulut_net_unit_create(self.device.index, nf, u, wp, bp, ctypes.byref(h)))
+        return h
 
     def close(self):
-        for h in getattr(self, "_units", {}).values():
-            self._lib.mulut_net_unit_destroy(h)
-        self._units = {}
+        for h in self._h.values():
+            self.lib.mulut_net_unit_destroy(h)
+        self._h = {}
 
     def __del__(self):
         try:
@@ -123,17 +122,75 @@ class NetEngine:
         except Exception:
             pass
 
-    def _stream(self):
+    def stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _unit(self, stage, mode):
+    def nf(self, stage):
+        return self.shape[(stage, self.modes[0])][0]
+
+    def u(self, stage):
+        return self.shape[(stage, self.modes[0])][1]
+
+    def handle(self, stage, mode):
         try:
-            return self._units[(int(stage), mode)]
+            return self._h[(int(stage), mode)]
         except KeyError:
             raise ValueError("Mode {} not implemented.".format(mode)) from None
 
+    def handles(self, stage):
+        """The units of a stage in the order of `modes`, as the stage calls take them."""
+        return (ctypes.c_void_p * len(self.modes))(*[self.handle(stage, m).value for m in self.modes])
+
+    def load(self, stage, model_G=None):
+        """Pack the current parameters of a stage's modules -- those of `model_G`, a module tree like the one the units were made
+        from, if given -- into the units' streams through the device pack, mulut_net_unit_load_dev: one small launch per unit on the
+        current stream, no host round trip for parameters that live on the device."""
+        for m in self.modes:
+            mod = self.mods[(stage, m)] if model_G is None else getattr(model_G, "s{}_{}".format(stage, m))
+            wp, bp, keep = unit_param_pointers(mod.model, self.device)
+            self.check(self.lib.mulut_net_unit_load_dev(self.handle(stage, m), wp, bp, self.stream()))
+            del keep      # (stream-ordered: torch's allocator does not hand the memory out to another stream)
+
+
+def _no_gpu():
+    if not torch.cuda.is_available():
+        raise MuLUTError("no GPU visible: mulut_amd has no CPU path")
+
+
+class NetEngine:
+    """Owns a `mulut_net_unit` per module of `model_G` (an `SRNets`, also one rebuilt by `network.load_checkpoint`).  The weights are
+    read once, here: a later change of the module's parameters is not seen until `load_weights` packs them anew, on the device.  Every method takes and returns device tensors and
+    queues its work on torch's current stream."""
+
+    def __init__(self, model_G, device=0, lib_path=None):
+        _no_gpu()
+        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+        self._units = un = NetUnits(model_G, self.device, False, lib_path)
+        self._lib, self.stages, self.modes = un.lib, un.stages, un.modes
+        if any(un.shape[(s, m)][1] != un.u(s) for s, m in un.shape):
+            self.close()
+            raise MuLUTError("mulut error -4: the units of a stage differ in upscale")
+        self.scale = int(np.prod([un.u(s) for s in range(1, self.stages + 1)]))
+
+    # -- plumbing ---------------------------------------------------------------------------
+    def _check(self, rc):
+        self._units.check(rc)
+
+    def load_weights(self, model_G):
+        """Refresh every unit from the current parameters of `model_G` (the module tree this engine was built from), on the device."""
+        for s in range(1, self.stages + 1):
+            self._units.load(s, model_G)
+        return self
+
+    def close(self):
+        if hasattr(self, "_units"):
+            self._units.close()
+
+    def _stream(self):
+        return self._units.stream()
+
     def upscale(self, stage):
-        return self._u[(int(stage), self.modes[0])]
+        return self._units.u(int(stage))
 
     def _u8(self, x, name="x_u8"):
         _dev(x, torch.uint8, name)
@@ -146,7 +203,7 @@ class NetEngine:
     # -- compute ------------------------------------------------------------------------------
     def table(self, stage, mode, interval=4):
         """int8 [L^4, 1, u, u] on the device: the table sr/2_transfer_to_lut.py:86-109 makes of this module."""
-        h, u = self._unit(stage, mode), self._u[(int(stage), mode)]
+        h, u = self._units.handle(stage, mode), self.upscale(stage)
         if interval not in (4, 5, 6):
             self._check(-5)
         out = torch.empty((lut_rows(interval), 1, u, u), dtype=torch.int8, device=self.device)
@@ -155,7 +212,7 @@ class NetEngine:
 
     def pass_(self, stage, mode, r, x_u8):
         """int8 [N, C, H*u, W*u]: one (mode, rotation) term of sr/1_train_model.py:33-35, round(127 * net(...)) rotated back."""
-        h, u = self._unit(stage, mode), self._u[(int(stage), mode)]
+        h, u = self._units.handle(stage, mode), self.upscale(stage)
         x = self._u8(x_u8)
         N, C, H, W = x.shape
         out = torch.empty((N, C, H * u, W * u), dtype=torch.int8, device=self.device)
@@ -165,8 +222,7 @@ class NetEngine:
     def stage(self, stage, x_u8, out=None):
         """uint8 [N, C, H*u, W*u]: one stage of mulut_predict in the 'valid' phase (sr/1_train_model.py:29-43)."""
         stage = int(stage)
-        handles = (ctypes.c_void_p * len(self.modes))(*[self._unit(stage, m).value for m in self.modes])
-        u = self.upscale(stage)
+        handles, u = self._units.handles(stage), self.upscale(stage)
         x = self._u8(x_u8)
         N, C, H, W = x.shape
         if out is None:

@@ -11,10 +11,9 @@ import ctypes
 
 import torch
 
-from . import _native
-from .engine import MuLUTError
-from .net_engine import _MODULE, unit_layers, unit_param_pointers
 from . import network
+from .engine import MuLUTError
+from .net_engine import NetUnits, _no_gpu, unit_layers
 
 DEFAULT_WS_SITES = 65536      # 173 MB of workspace at nf 64: inside the 256 MB Infinity Cache
 
@@ -24,6 +23,17 @@ def round_func(x):
     out = x.clone()
     out.data = torch.round(x).data
     return out
+
+
+def stage_epilogue(pred, M, last, phase="train"):
+    """sr/1_train_model.py:36-43: what follows the sum `pred` of the 4 M passes of a stage."""
+    if last:
+        x = round_func((pred / M) + 0)
+        if phase == "train":
+            x = x / 255.0
+    else:
+        x = round_func(torch.clamp((pred / (M * 4)) + 127, 0, 255)) / 255.0
+    return x
 
 
 class _StageSum(torch.autograd.Function):
@@ -50,71 +60,39 @@ class NetTrainer:
     which is allocated on first use and kept."""
 
     def __init__(self, model_G, ws_sites=DEFAULT_WS_SITES, lib_path=None):
-        self._lib = _native.load(lib_path)
-        self._units = {}
-        if not torch.cuda.is_available():
-            raise MuLUTError("no GPU visible: mulut_amd has no CPU path")
+        _no_gpu()
         self.model = model_G
-        found = {}
-        for name, mod in model_G.named_children():
-            m = _MODULE.match(name)
-            if m and isinstance(getattr(mod, "model", None), network.MuLUTUnit):
-                found[(int(m.group(1)), m.group(2))] = mod
-        if not found:
-            raise MuLUTError("no s{stage}_{mode} module found: NetTrainer wants an SRNets")
-        p0 = next(model_G.parameters())
-        if not p0.is_cuda:
-            raise MuLUTError("NetTrainer wants the module on the device (model_G.cuda())")
+        p0 = next(model_G.parameters(), None)
+        if p0 is None or not p0.is_cuda:
+            raise MuLUTError("NetTrainer wants an SRNets on the device (model_G.cuda())")
         self.device = p0.device
-        self.stages = max(s for s, _ in found)
-        self.modes = "".join(m for s, m in found if s == 1)
-        for s in range(1, self.stages + 1):
-            if "".join(m for t, m in found if t == s) != self.modes:
-                raise MuLUTError("stage %d does not hold the modes %r of stage 1" % (s, self.modes))
-        self._mods = found
+        self._units = un = NetUnits(model_G, self.device, True, lib_path)
+        self._lib, self.stages, self.modes = un.lib, un.stages, un.modes
         self.ws_sites = int(ws_sites)
         self._ws = None
         self.keep_sums = False   # True: last_sums[stage] holds pred of the last stage_sum (tests, logs); off, nothing outlives a step
         self.last_sums = {}
-        self._nf, self._u = {}, {}
-        try:
-            for (s, mode), mod in found.items():
-                layers = unit_layers(mod.model)
-                nf, u = int(layers[0].out_channels), int(mod.model.upscale)
-                want = [(nf, 4)] + [(nf, nf * k) for k in (1, 2, 3, 4)] + [(u * u, 5 * nf)]
-                if [(c.weight.shape[0], c.weight[0].numel()) for c in layers] != want or any(c.bias is None for c in layers):
-                    raise MuLUTError("mulut error -4: the layers of %s are not those of a dense unit with biases" % mod.mode)
-                h = ctypes.c_void_p()
-                _native.check(self._lib.mulut_net_unit_create_train(self.device.index, nf, u, ctypes.byref(h)), MuLUTError)
-                self._units[(s, mode)] = h
-                self._nf[s], self._u[s] = nf, u
-        except Exception:
-            self.close()
-            raise
 
     def close(self):
-        for h in getattr(self, "_units", {}).values():
-            self._lib.mulut_net_unit_destroy(h)
-        self._units = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if hasattr(self, "_units"):
+            self._units.close()
 
     # -- plumbing ---------------------------------------------------------------------------
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return self._units.stream()
 
     def _handles(self, stage):
-        return (ctypes.c_void_p * len(self.modes))(*[self._units[(stage, m)].value for m in self.modes])
+        return self._units.handles(stage)
+
+    def load(self, stage):
+        """Pack the current parameters of a stage's units into their streams (stream-ordered, on the device)."""
+        self._units.load(stage)
 
     def stage_params(self, stage):
         """The 12 M parameter tensors of a stage: per mode the six weights, then the six biases."""
         out = []
         for m in self.modes:
-            layers = unit_layers(self._mods[(stage, m)].model)
+            layers = unit_layers(self._units.mods[(stage, m)].model)
             out += [c.weight for c in layers] + [c.bias for c in layers]
         return out
 
@@ -125,17 +103,10 @@ class NetTrainer:
             raise ValueError("%s lives on %s, the module on %s" % (name, x.device, self.device))
         return x.contiguous()
 
-    def load(self, stage):
-        """Pack the current parameters of a stage's units into their streams (stream-ordered, on the device)."""
-        for m in self.modes:
-            wp, bp, keep = unit_param_pointers(self._mods[(stage, m)].model, self.device)
-            _native.check(self._lib.mulut_net_unit_load_dev(self._units[(stage, m)], wp, bp, self._stream()), MuLUTError)
-            del keep
-
     def workspace(self, stage, sites, min_sites=None):
         """The backward's workspace for chunks of min(sites, ws_sites) sites: kept and grown, never shrunk."""
-        want = int(self._lib.mulut_net_backward_ws_bytes(self._nf[stage], self._u[stage], min(sites, self.ws_sites if min_sites is None else min_sites)))
-        _native.check(min(want, 0), MuLUTError)
+        want = int(self._lib.mulut_net_backward_ws_bytes(self._units.nf(stage), self._units.u(stage), min(sites, self.ws_sites if min_sites is None else min_sites)))
+        self._units.check(min(want, 0))
         if min_sites is not None:
             return torch.empty(want, dtype=torch.uint8, device=self.device)
         if self._ws is None or self._ws.numel() < want:
@@ -146,10 +117,10 @@ class NetTrainer:
         x = self._x(x)
         self.load(stage)
         N, C, H, W = x.shape
-        u = self._u[stage]
+        u = self._units.u(stage)
         pred = torch.empty((N, C, H * u, W * u), dtype=torch.float32, device=self.device)
-        _native.check(self._lib.mulut_net_stage_sum(self._handles(stage), self.modes.encode(), x.data_ptr(), N, C, H, W, pred.data_ptr(),
-                                                    self._stream()), MuLUTError)
+        self._units.check(self._lib.mulut_net_stage_sum(self._handles(stage), self.modes.encode(), x.data_ptr(), N, C, H, W, pred.data_ptr(),
+                                                        self._stream()))
         if self.keep_sums:
             self.last_sums[stage] = pred.detach()
         return pred
@@ -159,7 +130,7 @@ class NetTrainer:
         forward ran on: `_StageSum.backward` raises if a parameter was written since; a direct caller runs `load(stage)` first."""
         x, g = self._x(x), self._x(g, "g")
         N, C, H, W = x.shape
-        u = self._u[stage]
+        u = self._units.u(stage)
         if g.shape != (N, C, H * u, W * u):
             raise ValueError("g has the wrong shape")
         ws = self.workspace(stage, N * C * H * W) if ws is None else ws
@@ -169,9 +140,9 @@ class NetTrainer:
         M = len(self.modes)
         gw = (ctypes.c_void_p * (6 * M))(*[grads[12 * m + l].data_ptr() for m in range(M) for l in range(6)])
         gb = (ctypes.c_void_p * (6 * M))(*[grads[12 * m + 6 + l].data_ptr() for m in range(M) for l in range(6)])
-        _native.check(self._lib.mulut_net_stage_backward(self._handles(stage), self.modes.encode(), x.data_ptr(), g.data_ptr(), N, C, H, W,
-                                                         ws.data_ptr(), ws.numel(), gx.data_ptr() if want_gx else None, gw, gb,
-                                                         self._stream()), MuLUTError)
+        self._units.check(self._lib.mulut_net_stage_backward(self._handles(stage), self.modes.encode(), x.data_ptr(), g.data_ptr(), N, C, H, W,
+                                                             ws.data_ptr(), ws.numel(), gx.data_ptr() if want_gx else None, gw, gb,
+                                                             self._stream()))
         return gx, grads
 
     # -- compute ------------------------------------------------------------------------------
@@ -182,15 +153,8 @@ class NetTrainer:
 
     def predict(self, x, phase="train"):
         """`mulut_predict(model_G, x, phase, opt)` of sr/1_train_model.py:26-45."""
-        M = len(self.modes)
         for s in range(1, self.stages + 1):
-            pred = self.stage_sum(s, x)
-            if s == self.stages:
-                x = round_func(pred / M + 0)
-                if phase == "train":
-                    x = x / 255.0
-            else:
-                x = round_func(torch.clamp(pred / (M * 4) + 127, 0, 255)) / 255.0
+            x = stage_epilogue(self.stage_sum(s, x), len(self.modes), s == self.stages, phase)
         return x
 
 
@@ -204,12 +168,7 @@ def torch_predict(model_G, x, modes, stages, phase="train"):
             for r in [0, 1, 2, 3]:
                 pred = pred + round_func(torch.rot90(model_G(F.pad(torch.rot90(x, r, [2, 3]), (0, pad, 0, pad), mode='replicate'),
                                                              stage=s + 1, mode=mode), (4 - r) % 4, [2, 3]) * 127)
-        if s + 1 == stages:
-            x = round_func((pred / len(modes)) + 0)
-            if phase == "train":
-                x = x / 255.0
-        else:
-            x = round_func(torch.clamp((pred / (len(modes) * 4)) + 127, 0, 255)) / 255.0
+        x = stage_epilogue(pred, len(modes), s + 1 == stages, phase)
     return x
 
 

@@ -4,63 +4,10 @@
 // frees; and the launch configurations of the three forms.  tests/test_net_cpu.py builds it under AddressSanitizer and
 // UndefinedBehaviorSanitizer and runs it as a program; it prints one line per check and exits with the number of lines that are not
 // what this file expects.  No kernel runs, so the image pointers are made-up addresses that nothing follows.
-#include <cmath>
-#include <cstdio>
-#include <string>
-#include <vector>
-
-#include "../../include/mulut.h"
-#include "../../mulut_amd/csrc/mulut_net.h"
-
-std::vector<std::string> &fake_hip_events();
-void fake_hip_flush();
+#include "net_host_common.h"
 
 static const uint8_t *const kIn = (const uint8_t *)0x10000000;
 static uint8_t *const kOut = (uint8_t *)0x50000000;
-static int g_wrong = 0;
-
-static void expect(const char *what, int rc, int want_rc, const std::string &want_event) {
-    fake_hip_flush();
-    std::vector<std::string> &ev = fake_hip_events();
-    std::string got;
-    for (auto &s : ev) got += (got.empty() ? "" : " | ") + s;
-    ev.clear();
-    const bool ok = rc == want_rc && got == want_event;
-    printf("%s -> %d [%s]%s\n", what, rc, got.c_str(), ok ? "" : "   UNEXPECTED");
-    g_wrong += !ok;
-}
-
-static void check(const char *what, bool ok) {
-    printf("%s%s\n", what, ok ? " ok" : "   UNEXPECTED");
-    g_wrong += !ok;
-}
-
-struct Weights {
-    int nf, u;
-    std::vector<float> w[6], b[6];
-    const float *wp[6], *bp[6];
-};
-
-static unsigned g_seed = 12345u;
-static float rnd() {      // in [-1, 1)
-    g_seed = g_seed * 1664525u + 1013904223u;
-    return (float)((g_seed >> 8) & 0xffff) / 32768.0f - 1.0f;
-}
-
-static void make(Weights &m, int nf, int u) {
-    m.nf = nf;
-    m.u = u;
-    for (int l = 0; l < 6; ++l) {
-        const int in = l == 0 ? 4 : l * nf, out = l == 5 ? u * u : nf;
-        m.w[l].resize((size_t)in * out);
-        m.b[l].resize((size_t)out);
-        const float s = 1.5f / std::sqrt((float)in);
-        for (auto &v : m.w[l]) v = rnd() * s;
-        for (auto &v : m.b[l]) v = rnd() * 0.2f;
-        m.wp[l] = m.w[l].data();
-        m.bp[l] = m.b[l].data();
-    }
-}
 
 // common/network.py:62-105 as plain loops, in double
 static void plain(const Weights &m, const float t[4], double *y) {
@@ -116,7 +63,7 @@ static void walk(const std::vector<float> &st, int MT, int u, const float t[4], 
 static void pack_case(int nf, int u) {
     using namespace mulut;
     Weights m;
-    make(m, nf, u);
+    make(m, nf, u, true);
     const int MT = net_tiles(nf);
     std::vector<float> st((size_t)net_stream_floats(MT));
     net_pack(nf, u, m.wp, m.bp, st.data());
@@ -144,13 +91,14 @@ static void pack_case(int nf, int u) {
 
 int main() {
     using namespace mulut;
+    g_seed = 12345u;
     check("steps at one tile 248, at two 815", net_steps(1) == 248 && net_steps(2) == 815 && net_chunks(1) == 4 && net_chunks(2) == 13);
     for (int nf : {1, 8, 24, 32, 33, 64})
         for (int u : {1, 2, 3, 4}) pack_case(nf, u);
     Weights m8, m64, m64u1;
-    make(m8, 8, 2);
-    make(m64, 64, 4);
-    make(m64u1, 64, 1);
+    make(m8, 8, 2, true);
+    make(m64, 64, 4, true);
+    make(m64u1, 64, 1, true);
     mulut_net_unit *unit = (mulut_net_unit *)0x1, *u8 = nullptr, *u64 = nullptr, *u64b = nullptr, *u64u1 = nullptr;
     // ---- mulut_net_unit_create: refusals before the device is touched; *unit is NULL afterwards
     expect("create null out", mulut_net_unit_create(0, 8, 2, m8.wp, m8.bp, nullptr), MULUT_EINVAL, "");

@@ -1,87 +1,25 @@
 // net_train_host.cpp -- the host half of the training entry points (mulut_amd/csrc/mulut_net_train.hip) on the CPU against fake_hip.cpp:
-// what the device pack computes per float (net_fwd_value / net_bwd_value of mulut_net.h) against the host pack of the forward stream,
-// bit for bit; the backward stream walked as net_bwd_site_kernel's MFMA sequence walks it against plain transposed matrices; every
+// the backward stream (net_bwd_value of mulut_net.h, through the host pack) walked as net_bwd_site_kernel's MFMA sequence walks it
+// against plain transposed matrices -- the forward stream has the same single definition, net_fwd_value, and net_host.cpp walks what
+// it produces against a plain-loop MLP over nf {1, 8, 24, 32, 33, 64} x u 1..4, so no forward comparison is made here; every
 // refusal of the six calls, each decided without touching the device; what a training unit allocates and frees; and the launch
 // sequence of a backward over a workspace of two chunks.  tests/test_net_train_cpu.py builds it under AddressSanitizer and
 // UndefinedBehaviorSanitizer and runs it as a program; it prints one line per check and exits with the number of lines that are not
 // what this file expects.  No kernel runs, so the device pointers are made-up addresses that nothing follows.
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/mulut.h"
-#include "../../mulut_amd/csrc/mulut_net.h"
-
-std::vector<std::string> &fake_hip_events();
-void fake_hip_flush();
+#include "net_host_common.h"
 
 static const float *const kX = (const float *)0x10000000;
 static float *const kOut = (float *)0x50000000;
 static void *const kWs = (void *)0x70000000;
-static int g_wrong = 0;
-
-static void expect(const char *what, long long rc, long long want_rc, const std::string &want_event) {
-    fake_hip_flush();
-    std::vector<std::string> &ev = fake_hip_events();
-    std::string got;
-    for (auto &s : ev) got += (got.empty() ? "" : " | ") + s;
-    ev.clear();
-    const bool ok = rc == want_rc && got == want_event;
-    printf("%s -> %lld [%s]%s\n", what, rc, got.c_str(), ok ? "" : "   UNEXPECTED");
-    g_wrong += !ok;
-}
-
-static void check(const char *what, bool ok) {
-    printf("%s%s\n", what, ok ? " ok" : "   UNEXPECTED");
-    g_wrong += !ok;
-}
-
-struct Weights {
-    int nf, u;
-    std::vector<float> w[6], b[6];
-    const float *wp[6], *bp[6];
-};
-
-static unsigned g_seed = 4321u;
-static float rnd() {      // in [-1, 1)
-    g_seed = g_seed * 1664525u + 1013904223u;
-    return (float)((g_seed >> 8) & 0xffff) / 32768.0f - 1.0f;
-}
-
-static void make(Weights &m, int nf, int u) {
-    m.nf = nf;
-    m.u = u;
-    for (int l = 0; l < 6; ++l) {
-        const int in = l == 0 ? 4 : l * nf, out = l == 5 ? u * u : nf;
-        m.w[l].resize((size_t)in * out);
-        m.b[l].resize((size_t)out);
-        for (auto &v : m.w[l]) v = rnd();
-        for (auto &v : m.b[l]) v = rnd();
-        m.wp[l] = m.w[l].data();
-        m.bp[l] = m.b[l].data();
-    }
-}
 
 static void pack_case(int nf, int u) {
     using namespace mulut;
     Weights m;
-    make(m, nf, u);
+    make(m, nf, u, false);
     const int MT = net_tiles(nf);
-    NetParams p;
-    for (int l = 0; l < 6; ++l) p.w[l] = m.wp[l], p.b[l] = m.bp[l];
-    // ---- forward: the per-float function of the device pack against the host pack's scatter
-    std::vector<float> st((size_t)net_stream_floats(MT));
-    net_pack(nf, u, m.wp, m.bp, st.data());
-    size_t differ = 0;
-    for (int g = 0; g < net_chunks(MT) * kNetChunkSteps; ++g)
-        for (int lane = 0; lane < 64; ++lane) {
-            const float a = net_fwd_value(nf, u, MT, g, lane, p), b = st[(size_t)net_step_float(g, lane)];
-            differ += memcmp(&a, &b, sizeof(float)) != 0;
-        }
-    // ---- backward: the stream walked step by step against plain transposed matrices, for one vector of deltas
+    // ---- the stream walked step by step against plain transposed matrices, for one vector of deltas
     std::vector<float> bw((size_t)net_bwd_stream_floats(MT));
     net_pack_bwd(nf, u, m.wp, bw.data());
     std::vector<double> delta[6];
@@ -134,21 +72,21 @@ static void pack_case(int nf, int u) {
         for (float v : m.w[l]) want_nonzero += v != 0.0f;
     // (every weight appears exactly once: W_1 in the tap steps, W_L (L >= 2) once per source block; biases nowhere)
     char what[128];
-    snprintf(what, sizeof(what), "pack nf %d u %d: forward differs on %zu floats; backward %d steps in %d chunks, worst |walk - plain| %.2e", nf, u, differ,
-             net_bwd_steps(MT), net_bwd_chunks(MT), worst);
+    snprintf(what, sizeof(what), "pack nf %d u %d: backward %d steps in %d chunks, worst |walk - plain| %.2e", nf, u, net_bwd_steps(MT), net_bwd_chunks(MT), worst);
     // double sums of at most 330 products of float values below 1: 330 * 2^-53
-    check(what, differ == 0 && worst < 1e-12 && nonzero == want_nonzero);
+    check(what, worst < 1e-12 && nonzero == want_nonzero);
 }
 
 int main() {
     using namespace mulut;
+    g_seed = 4321u;
     check("backward steps at one tile 216, at two 752", net_bwd_steps(1) == 216 && net_bwd_steps(2) == 752 && net_bwd_chunks(1) == 4 && net_bwd_chunks(2) == 12);
     check("workspace rows and gradient floats at nf 64 u 4", net_ws_rows(64, 4) == 660 && net_param_floats(64, 4) == 46672);
     for (int nf : {1, 8, 24, 32, 33, 64})
         for (int u : {1, 2, 3, 4}) pack_case(nf, u);
     Weights m8, m64;
-    make(m8, 8, 2);
-    make(m64, 64, 4);
+    make(m8, 8, 2, false);
+    make(m64, 64, 4, false);
     mulut_net_unit *unit = (mulut_net_unit *)0x1, *t8 = nullptr, *t64 = nullptr, *t64b = nullptr, *t24 = nullptr, *plain64 = nullptr;
     // ---- mulut_net_unit_create_train
     expect("create_train null out", mulut_net_unit_create_train(0, 8, 2, nullptr), MULUT_EINVAL, "");
