@@ -466,6 +466,41 @@ long long mulut_net_backward_ws_bytes(int nf, int u, long long sites);
 int mulut_net_stage_backward(const mulut_net_unit *const units[], const char *modes, const float *x, const float *g, int N, int C, int H,
                              int W, void *ws, long long ws_bytes, float *gx, float *const gw[], float *const gb[], void *stream);
 
+/* ---- The same backward with a bit-reproducible gx (mulut_net_train.hip).  No atomics and no fixed point: the site kernel STORES a
+ * site's tap gradient W_1^T delta_1 into a tap buffer t = float [4][ts], the site the fast index (row k: tap a, b, c, d of the
+ * pattern), and a second kernel, one thread per input pixel p of plane (n, c), gathers it.  The gather's definition:
+ *
+ *     acc = accumulate ? gx[p] : +0.0f
+ *     for k in 0..3                                   (taps a, b, c, d of the pattern)
+ *       for every site s = y0 * W + x0 of the same plane, ascending, with net_tap_index(H, W, r, y0, x0, taps, k) == p:
+ *         acc = acc + t[k][plane * H * W + s]         (a plain float32 add)
+ *     gx[p] = acc
+ *
+ * net_tap_index (mulut_net_dev.h) is where tap k of the site anchored at pixel (y0, x0) lies in rotation r: replicate-padded on the
+ * bottom and right of the ROTATED image, so a pixel receives from 0, 1 or, on the last row / column of the rotated frame, up to
+ * (di + 1)(dj + 1) <= 16 sites per tap.  A stage is its passes in the order the backward runs them (mode in the order of `modes`, then
+ * r = 0..3), the first with accumulate = 0, the others with 1.  gx is therefore WRITTEN (callers do not zero it) and is a function
+ * of the inputs alone: the same bits from run to run and for every workspace size.
+ *   mulut_net_backward_exact_ws_bytes  mulut_net_backward_ws_bytes(nf, u, chunk_sites) plus the tap region of a whole pass,
+ *                           16 bytes x total_sites rounded up to 128: the gather needs all sites of a pass, the weight-gradient
+ *                           rows still run in chunks.  Layout: the 16 partial copies of a unit's gradient (rounded up to 256
+ *                           bytes), the tap region float [4][ts], then the rows [4 + 10 nf + u*u][chunk].  total_sites < 1:
+ *                           MULUT_EINVAL; >= 2^31: MULUT_EUNSUPPORTED; else as mulut_net_backward_ws_bytes.
+ *   mulut_net_stage_backward_exact  the arguments of mulut_net_stage_backward.  gw / gb are the bits mulut_net_stage_backward
+ *                           writes; gx, if not NULL, is written by the definition above, whatever number of chunks the workspace
+ *                           allows.  The same refusals, and MULUT_EWORKSPACE when ws_bytes is below
+ *                           mulut_net_backward_exact_ws_bytes(nf, u, 128, N*C*H*W).
+ *   mulut_net_gx_gather     the gather of one pass on its own: t = device float [4][ts], rows beyond the N*C*H*W sites never read;
+ *                           gx = device float [N][C][H][W].  Refusals before any launch: a NULL pointer, r outside 0..3, an
+ *                           unknown pattern letter, a size < 1, ts < N*C*H*W (MULUT_EINVAL); sizes beyond the limits of
+ *                           mulut_net_stage (MULUT_EUNSUPPORTED).
+ * All three are stream-ordered, wait for nothing and allocate nothing. */
+long long mulut_net_backward_exact_ws_bytes(int nf, int u, long long chunk_sites, long long total_sites);
+int mulut_net_stage_backward_exact(const mulut_net_unit *const units[], const char *modes, const float *x, const float *g, int N, int C,
+                                   int H, int W, void *ws, long long ws_bytes, float *gx, float *const gw[], float *const gb[], void *stream);
+int mulut_net_gx_gather(int device, char mode, int r, const float *t, long long ts, int N, int C, int H, int W, float *gx, int accumulate,
+                        void *stream);
+
 /* Tuning knobs (never change results).
  * "final_stage_kernel" (scale 4, <= 3 modes): 0 = auto (= 6), 1 = full-table gather kernel, 5 = tube kernel on every tile (the tube
  *   bands of all modes resident in LDS; samples with a pass outside the tube are recomputed from the full table through a device

@@ -26,7 +26,7 @@ EXPORTS = [
     "mulut_resample_coeffs", "mulut_resample_plan_create", "mulut_resample_plan_destroy", "mulut_resample_run",
     "mulut_net_unit_create", "mulut_net_unit_destroy", "mulut_net_table", "mulut_net_pass", "mulut_net_stage",
     "mulut_net_unit_create_train", "mulut_net_unit_load_dev", "mulut_net_unit_read", "mulut_net_pack_host", "mulut_net_stage_sum", "mulut_net_backward_ws_bytes",
-    "mulut_net_stage_backward",
+    "mulut_net_stage_backward", "mulut_net_backward_exact_ws_bytes", "mulut_net_stage_backward_exact", "mulut_net_gx_gather",
 ]
 
 _libs = {}
@@ -244,10 +244,14 @@ def load(path=None):
     L.mulut_net_backward_ws_bytes.argtypes = [i, i, ctypes.c_longlong]
     L.mulut_net_stage_backward.argtypes = [ctypes.POINTER(p), c_char_p, p, p, i, i, i, i, p, ctypes.c_longlong, p, ctypes.POINTER(p),
                                            ctypes.POINTER(p), p]
-    for name in ("mulut_net_unit_create_train", "mulut_net_unit_load_dev", "mulut_net_stage_sum", "mulut_net_stage_backward"):
+    L.mulut_net_backward_exact_ws_bytes.argtypes = [i, i, ctypes.c_longlong, ctypes.c_longlong]
+    L.mulut_net_stage_backward_exact.argtypes = L.mulut_net_stage_backward.argtypes
+    L.mulut_net_gx_gather.argtypes = [i, ctypes.c_char, i, p, ctypes.c_longlong, i, i, i, i, p, i, p]
+    for name in ("mulut_net_unit_create_train", "mulut_net_unit_load_dev", "mulut_net_stage_sum", "mulut_net_stage_backward",
+                 "mulut_net_stage_backward_exact", "mulut_net_gx_gather"):
         getattr(L, name).restype = i
     L.mulut_net_pack_host.argtypes = [i, i, fpp, fpp, i, p, ctypes.c_longlong]
-    for name in ("mulut_net_unit_read", "mulut_net_backward_ws_bytes", "mulut_net_pack_host"):
+    for name in ("mulut_net_unit_read", "mulut_net_backward_ws_bytes", "mulut_net_backward_exact_ws_bytes", "mulut_net_pack_host"):
         getattr(L, name).restype = ctypes.c_longlong
     _libs[path] = L
     return L

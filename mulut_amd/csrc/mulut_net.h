@@ -157,6 +157,8 @@ inline void net_pack_bwd(int nf, int u, const float *const w[6], float *out) {
 // wave reads 32 consecutive sites of 32 rows per operand and step group: a lane takes 16 sites of its row (64 bytes, lane half h the
 // sites 16 * h ..) as four 16-byte loads, and MFMA v * 4 + c of the group contracts sites 4 * v + c and 16 + 4 * v + c -- the order of a
 // sum's terms is free as long as both operands agree on it.
+// (mulut_net_stage_backward_exact puts the tap buffer of a whole pass, float [4][sites rounded up to 128], between the partial copies
+// and the rows: include/mulut.h.)
 constexpr int kNetGradSplits = 16;
 __host__ __device__ constexpr int net_ws_rows(int nf, int u) { return 4 + 10 * nf + u * u; }
 // floats of one copy of a unit's gradient: dW_1..dW_6 as [out][in], then db_1..db_6

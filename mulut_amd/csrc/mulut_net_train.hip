@@ -16,6 +16,11 @@
 //                         in wave order and the result is added to the split's own copy of the gradient.  No atomics.
 // After the four rotations of a unit net_wgrad_reduce_kernel adds the kNetGradSplits copies in index order into gw / gb, so these are
 // bit-identical from run to run (gx is not: float atomics).
+//
+// mulut_net_stage_backward_exact makes gx a function of its inputs too, without atomics and without fixed point.  Its site kernel,
+// net_bwd_site_taps_kernel (the same body, the other compile-time form), STORES the four tap gradients of a site into a tap buffer
+// [4][ts] of the workspace, and after the last chunk of a pass net_gx_gather_kernel, one thread per input pixel, adds the terms that
+// land on its pixel in the fixed order include/mulut.h defines, found by index arithmetic.  gw / gb are the bits of the other backward.
 #include "mulut_net_dev.h"
 
 namespace mulut {
@@ -46,9 +51,11 @@ struct NetBwdArgs {
     int r, u, nf, H, W, total, site0;
 };
 
-template <int MT>
-__global__ void __launch_bounds__(kNetNT) net_bwd_site_kernel(NetBwdArgs a) {
-    __shared__ float4 lds[2 * kNetChunkVec4];
+// The site body in its two forms.  TAPS false: the tap gradient is added into a.gx with float atomics.  TAPS true: a.gx is the pass's
+// tap buffer t, float [4][ts] with the site as the fast index, and row k of the site's column is STORED -- 32 consecutive floats per
+// wave and tap; net_gx_gather_kernel sums them per pixel in a fixed order.
+template <int MT, bool TAPS>
+__device__ __forceinline__ void net_bwd_site_body(const NetBwdArgs &a, long long ts, float4 *lds) {
     NetStream s;
     s.cur = a.wf;
     s.next = a.wb;
@@ -132,10 +139,70 @@ __global__ void __launch_bounds__(kNetNT) net_bwd_site_kernel(NetBwdArgs a) {
         net_step_of<NCB, tap_base + k, false>(s, d[0][k / 16][k % 16], gacc);
     });
     if (valid && h == 0) {
-        float *pgx = a.gx + (long long)plane * H * W;
+        if constexpr (TAPS) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) atomicAdd(pgx + net_tap_index(H, W, a.r, y0, x0, a.taps, q), gacc[q]);
+            for (int q = 0; q < 4; ++q) a.gx[q * ts + site] = gacc[q];
+        } else {
+            float *pgx = a.gx + (long long)plane * H * W;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) atomicAdd(pgx + net_tap_index(H, W, a.r, y0, x0, a.taps, q), gacc[q]);
+        }
     }
+}
+
+template <int MT>
+__global__ void __launch_bounds__(kNetNT) net_bwd_site_kernel(NetBwdArgs a) {
+    __shared__ float4 lds[2 * kNetChunkVec4];
+    net_bwd_site_body<MT, false>(a, 0, lds);
+}
+
+template <int MT>
+__global__ void __launch_bounds__(kNetNT) net_bwd_site_taps_kernel(NetBwdArgs a, long long ts) {
+    __shared__ float4 lds[2 * kNetChunkVec4];
+    net_bwd_site_body<MT, true>(a, ts, lds);
+}
+
+// gx of one (pattern, rotation) pass from its tap buffer: the definition of mulut_net_gx_gather (include/mulut.h), one thread per
+// input pixel.  Tap k = (di, dj) of the site at (i, j) of the ROTATED frame reads (min(i + di, Hr - 1), min(j + dj, Wr - 1)), so row i'
+// receives from i' - di below the last row and from every i in [max(0, Hr - 1 - di), Hr - 1] on it, and columns likewise: a rectangle
+// of sites, which is a rectangle of the un-rotated plane too, walked there row by row -- ascending in the index the site kernel
+// numbers sites with.
+struct NetGatherArgs {
+    const float *t;
+    float *gx;
+    long long ts;
+    unsigned taps;
+    int r, H, W, total, accumulate;
+};
+
+__global__ void __launch_bounds__(256) net_gx_gather_kernel(NetGatherArgs a) {
+    const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (idx >= a.total) return;
+    const int H = a.H, W = a.W, r = a.r;
+    const int plane = idx / (H * W), p = idx % (H * W), y = p / W, x = p % W;
+    const int Hr = (r & 1) ? W : H, Wr = (r & 1) ? H : W;
+    int ip, jp;
+    net_rot(r, y, x, H, W, ip, jp);
+    const float *tp = a.t + (long long)plane * H * W;
+    float acc = a.accumulate ? a.gx[idx] : 0.0f;
+    for (int k = 0; k < 4; ++k) {
+        const unsigned tpn = a.taps >> (8 * k);
+        const int di = (int)(tpn & 15u), dj = (int)((tpn >> 4) & 15u);
+        int i_lo = ip - di, i_hi = ip - di, j_lo = jp - dj, j_hi = jp - dj;
+        if (ip == Hr - 1) i_hi = ip;
+        if (jp == Wr - 1) j_hi = jp;
+        i_lo = i_lo > 0 ? i_lo : 0;
+        j_lo = j_lo > 0 ? j_lo : 0;
+        if (i_lo > i_hi || j_lo > j_hi) continue;
+        int ya, xa, yb, xb;
+        net_unrot(r, i_lo, j_lo, H, W, ya, xa);
+        net_unrot(r, i_hi, j_hi, H, W, yb, xb);
+        const int y_lo = ya < yb ? ya : yb, y_hi = ya < yb ? yb : ya, x_lo = xa < xb ? xa : xb, x_hi = xa < xb ? xb : xa;
+        const float *tk = tp + k * a.ts;
+        for (int y0 = y_lo; y0 <= y_hi; ++y0)
+            for (int x0 = x_lo; x0 <= x_hi; ++x0) acc = acc + tk[y0 * W + x0];
+    }
+    a.gx[idx] = acc;
 }
 
 struct NetWgradArgs {
@@ -236,6 +303,14 @@ static long long net_partial_bytes(int nf, int u) {
     return (b + 255) / 256 * 256;
 }
 
+// the tap buffer of a pass: float [4][ts], ts the pass's sites rounded up to 128
+static long long net_tap_bytes(long long ts) { return 4 * ts * (long long)sizeof(float); }
+
+static void net_gx_gather_launch(unsigned taps, int r, const float *t, long long ts, int total, int H, int W, float *gx, bool accumulate, hipStream_t st) {
+    NetGatherArgs a{t, gx, ts, taps, r, H, W, total, accumulate ? 1 : 0};
+    hipLaunchKernelGGL(net_gx_gather_kernel, dim3((unsigned)(((long long)total + 255) / 256)), dim3(256), 0, st, a);
+}
+
 }  // namespace mulut
 
 /* a unit for training: both streams allocated and zeroed, to be filled by mulut_net_unit_load_dev */
@@ -312,8 +387,11 @@ extern "C" long long mulut_net_backward_ws_bytes(int nf, int u, long long sites)
     return net_partial_bytes(nf, u) + cs * net_ws_rows(nf, u) * (long long)sizeof(float);
 }
 
-extern "C" int mulut_net_stage_backward(const mulut_net_unit *const units[], const char *modes, const float *x, const float *g, int N, int C, int H,
-                                        int W, void *ws, long long ws_bytes, float *gx, float *const gw[], float *const gb[], void *stream) {
+// Both backwards.  exact: the workspace holds the pass's tap buffer, float [4][ts], between the partial copies and the rows; the site
+// kernel stores a site's tap gradient there and, after the last chunk of a pass, net_gx_gather_kernel writes (first pass of the stage)
+// or adds to gx.
+static int net_backward(const mulut_net_unit *const units[], const char *modes, const float *x, const float *g, int N, int C, int H, int W, void *ws,
+                        long long ws_bytes, float *gx, float *const gw[], float *const gb[], void *stream, bool exact) {
     using namespace mulut;
     if (!units || !modes || !x || !g || !ws || !gw || !gb) return MULUT_EINVAL;
     const float4 *wf[MULUT_MAX_MODES], *wb[MULUT_MAX_MODES];
@@ -330,27 +408,36 @@ extern "C" int mulut_net_stage_backward(const mulut_net_unit *const units[], con
     rc = net_image_sites(N, C, H, W, u, &total);
     if (rc != MULUT_OK) return rc;
     if (reinterpret_cast<uintptr_t>(ws) & 255) return MULUT_EINVAL;
-    const long long pbytes = net_partial_bytes(nf, u), row_bytes = net_ws_rows(nf, u) * (long long)sizeof(float);
-    if (ws_bytes < pbytes + kNetSites * row_bytes) return MULUT_EWORKSPACE;
-    long long cs = (ws_bytes - pbytes) / row_bytes / kNetSites * kNetSites;
     const long long need = ((long long)total + kNetSites - 1) / kNetSites * kNetSites;
+    const long long pbytes = net_partial_bytes(nf, u), row_bytes = net_ws_rows(nf, u) * (long long)sizeof(float);
+    const long long tbytes = exact ? net_tap_bytes(need) : 0;
+    if (ws_bytes < pbytes + tbytes + kNetSites * row_bytes) return MULUT_EWORKSPACE;
+    long long cs = (ws_bytes - pbytes - tbytes) / row_bytes / kNetSites * kNetSites;
     if (cs > need) cs = need;
     if (hipSetDevice(units[0]->device) != hipSuccess) return MULUT_ENODEVICE;
     hipStream_t st = (hipStream_t)stream;
-    float *partial = static_cast<float *>(ws), *rows = reinterpret_cast<float *>(static_cast<char *>(ws) + pbytes);
+    float *partial = static_cast<float *>(ws), *t = reinterpret_cast<float *>(static_cast<char *>(ws) + pbytes);
+    float *rows = reinterpret_cast<float *>(static_cast<char *>(ws) + pbytes + tbytes);
     const int P = net_param_floats(nf, u), pairs = net_wgrad_pairs(nf, u);
     for (int m = 0; m < M; ++m) {
         if (hipMemsetAsync(partial, 0, (size_t)kNetGradSplits * P * sizeof(float), st) != hipSuccess) return MULUT_EHIP;
-        for (int r = 0; r < 4; ++r)
+        for (int r = 0; r < 4; ++r) {
             for (long long site0 = 0; site0 < total; site0 += cs) {
                 const long long n = total - site0 < cs ? total - site0 : cs;
                 const int blocks = (int)((n + kNetSites - 1) / kNetSites);
-                NetBwdArgs a{wf[m], wb[m], x, g, gx, rows, cs, taps[m], r, u, nf, H, W, total, (int)site0};
-                if (mt == 1) hipLaunchKernelGGL(net_bwd_site_kernel<1>, dim3((unsigned)blocks), dim3(kNetNT), 0, st, a);
-                else hipLaunchKernelGGL(net_bwd_site_kernel<2>, dim3((unsigned)blocks), dim3(kNetNT), 0, st, a);
+                NetBwdArgs a{wf[m], wb[m], x, g, exact && gx ? t : gx, rows, cs, taps[m], r, u, nf, H, W, total, (int)site0};
+                if (exact) {
+                    if (mt == 1) hipLaunchKernelGGL(net_bwd_site_taps_kernel<1>, dim3((unsigned)blocks), dim3(kNetNT), 0, st, a, need);
+                    else hipLaunchKernelGGL(net_bwd_site_taps_kernel<2>, dim3((unsigned)blocks), dim3(kNetNT), 0, st, a, need);
+                } else {
+                    if (mt == 1) hipLaunchKernelGGL(net_bwd_site_kernel<1>, dim3((unsigned)blocks), dim3(kNetNT), 0, st, a);
+                    else hipLaunchKernelGGL(net_bwd_site_kernel<2>, dim3((unsigned)blocks), dim3(kNetNT), 0, st, a);
+                }
                 NetWgradArgs wa{rows, partial, cs, nf, u, blocks * kNetWaves, P};
                 hipLaunchKernelGGL(net_wgrad_kernel, dim3((unsigned)pairs, kNetGradSplits), dim3(kNetNT), 0, st, wa);
             }
+            if (exact && gx) net_gx_gather_launch(taps[m], r, t, need, total, H, W, gx, m > 0 || r > 0, st);
+        }
         NetGradOut o;
         int end = 0;
         for (int k = 0; k < 12; ++k) {      // dW_1..dW_6, then db_1..db_6
@@ -361,5 +448,40 @@ extern "C" int mulut_net_stage_backward(const mulut_net_unit *const units[], con
         }
         hipLaunchKernelGGL(net_wgrad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, partial, P, o);
     }
+    return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
+}
+
+extern "C" int mulut_net_stage_backward(const mulut_net_unit *const units[], const char *modes, const float *x, const float *g, int N, int C, int H,
+                                        int W, void *ws, long long ws_bytes, float *gx, float *const gw[], float *const gb[], void *stream) {
+    return net_backward(units, modes, x, g, N, C, H, W, ws, ws_bytes, gx, gw, gb, stream, false);
+}
+
+extern "C" long long mulut_net_backward_exact_ws_bytes(int nf, int u, long long chunk_sites, long long total_sites) {
+    using namespace mulut;
+    if (total_sites < 1) return MULUT_EINVAL;
+    const long long base = mulut_net_backward_ws_bytes(nf, u, chunk_sites);
+    if (base < 0) return base;
+    if (total_sites >= (1LL << 31)) return MULUT_EUNSUPPORTED;
+    return base + net_tap_bytes((total_sites + kNetSites - 1) / kNetSites * kNetSites);
+}
+
+extern "C" int mulut_net_stage_backward_exact(const mulut_net_unit *const units[], const char *modes, const float *x, const float *g, int N, int C,
+                                              int H, int W, void *ws, long long ws_bytes, float *gx, float *const gw[], float *const gb[],
+                                              void *stream) {
+    return net_backward(units, modes, x, g, N, C, H, W, ws, ws_bytes, gx, gw, gb, stream, true);
+}
+
+extern "C" int mulut_net_gx_gather(int device, char mode, int r, const float *t, long long ts, int N, int C, int H, int W, float *gx, int accumulate,
+                                   void *stream) {
+    using namespace mulut;
+    if (!t || !gx || r < 0 || r > 3) return MULUT_EINVAL;
+    const unsigned taps = net_pattern(mode);
+    if (taps == 0xffffffffu) return MULUT_EINVAL;
+    int total = 0;
+    const int rc = net_image_sites(N, C, H, W, 1, &total);
+    if (rc != MULUT_OK) return rc;
+    if (ts < total) return MULUT_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return MULUT_ENODEVICE;
+    net_gx_gather_launch(taps, r, t, ts, total, H, W, gx, accumulate != 0, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? MULUT_OK : MULUT_EHIP;
 }

@@ -1,5 +1,7 @@
 """Training the SR network on the fused HIP forward and backward (mulut_net_stage_sum / mulut_net_stage_backward of include/mulut.h,
-mulut_amd/csrc/mulut_net_train.hip): one NetTrainer per `SRNets` whose parameters live on the device.
+mulut_amd/csrc/mulut_net_train.hip): one NetTrainer per `SRNets` whose parameters live on the device.  With `deterministic=True` the
+backward is mulut_net_stage_backward_exact: the input gradient is gathered per pixel in a fixed order instead of added with float
+atomics, so every gradient of every stage is a function of the inputs alone, bit for bit.
 
 `stage_sum(stage, x)` is the sum of the 4 M rounded rotation passes of one stage (sr/1_train_model.py:30-35) as one autograd node: the
 forward packs the current parameters into the units' weight streams on the device and runs one kernel; the backward runs the
@@ -57,9 +59,10 @@ class _StageSum(torch.autograd.Function):
 class NetTrainer:
     """Owns a training unit (both weight streams) per `s{stage}_{mode}` module of `model_G`, an `SRNets` on the device.  The units
     follow the parameters: every `stage_sum` packs them anew, on the device.  `ws_sites`: sites per chunk of the backward's workspace,
-    which is allocated on first use and kept."""
+    which is allocated on first use and kept.  `deterministic`: the backward with the gather-form input gradient (the workspace then
+    also holds the tap buffer of a whole pass)."""
 
-    def __init__(self, model_G, ws_sites=DEFAULT_WS_SITES, lib_path=None):
+    def __init__(self, model_G, ws_sites=DEFAULT_WS_SITES, lib_path=None, deterministic=False):
         _no_gpu()
         self.model = model_G
         p0 = next(model_G.parameters(), None)
@@ -69,6 +72,7 @@ class NetTrainer:
         self._units = un = NetUnits(model_G, self.device, True, lib_path)
         self._lib, self.stages, self.modes = un.lib, un.stages, un.modes
         self.ws_sites = int(ws_sites)
+        self.deterministic = bool(deterministic)
         self._ws = None
         self.keep_sums = False   # True: last_sums[stage] holds pred of the last stage_sum (tests, logs); off, nothing outlives a step
         self.last_sums = {}
@@ -105,7 +109,11 @@ class NetTrainer:
 
     def workspace(self, stage, sites, min_sites=None):
         """The backward's workspace for chunks of min(sites, ws_sites) sites: kept and grown, never shrunk."""
-        want = int(self._lib.mulut_net_backward_ws_bytes(self._units.nf(stage), self._units.u(stage), min(sites, self.ws_sites if min_sites is None else min_sites)))
+        chunk = min(sites, self.ws_sites if min_sites is None else min_sites)
+        if self.deterministic:      # `sites` is the pass's site count: the tap buffer holds all of them, whatever the chunk
+            want = int(self._lib.mulut_net_backward_exact_ws_bytes(self._units.nf(stage), self._units.u(stage), chunk, sites))
+        else:
+            want = int(self._lib.mulut_net_backward_ws_bytes(self._units.nf(stage), self._units.u(stage), chunk))
         self._units.check(min(want, 0))
         if min_sites is not None:
             return torch.empty(want, dtype=torch.uint8, device=self.device)
@@ -134,16 +142,34 @@ class NetTrainer:
         if g.shape != (N, C, H * u, W * u):
             raise ValueError("g has the wrong shape")
         ws = self.workspace(stage, N * C * H * W) if ws is None else ws
-        gx = torch.zeros_like(x) if want_gx else None
+        if self.deterministic:      # written, not added to
+            gx = torch.empty_like(x) if want_gx else None
+        else:
+            gx = torch.zeros_like(x) if want_gx else None
         params = self.stage_params(stage)
         grads = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in params]
         M = len(self.modes)
         gw = (ctypes.c_void_p * (6 * M))(*[grads[12 * m + l].data_ptr() for m in range(M) for l in range(6)])
         gb = (ctypes.c_void_p * (6 * M))(*[grads[12 * m + 6 + l].data_ptr() for m in range(M) for l in range(6)])
-        self._units.check(self._lib.mulut_net_stage_backward(self._handles(stage), self.modes.encode(), x.data_ptr(), g.data_ptr(), N, C, H, W,
-                                                             ws.data_ptr(), ws.numel(), gx.data_ptr() if want_gx else None, gw, gb,
-                                                             self._stream()))
+        entry = self._lib.mulut_net_stage_backward_exact if self.deterministic else self._lib.mulut_net_stage_backward
+        self._units.check(entry(self._handles(stage), self.modes.encode(), x.data_ptr(), g.data_ptr(), N, C, H, W, ws.data_ptr(), ws.numel(),
+                                gx.data_ptr() if want_gx else None, gw, gb, self._stream()))
         return gx, grads
+
+    def gx_gather(self, mode, r, t, shape, gx=None):
+        """mulut_net_gx_gather for tests: the input gradient of one (pattern, rotation) pass from its tap buffer `t`, float32 [4, ts] on
+        the device.  gx None: a new tensor of `shape` = (N, C, H, W) is written; else `gx` is added to, in the order of the definition."""
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and t.shape[0] == 4 and t.is_contiguous()):
+            raise TypeError("t must be a contiguous float32 CUDA tensor [4, ts]")
+        N, C, H, W = shape
+        accumulate = gx is not None
+        if gx is None:
+            gx = torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
+        elif self._x(gx, "gx").data_ptr() != gx.data_ptr() or tuple(gx.shape) != tuple(shape):      # (_x copies what is not contiguous)
+            raise ValueError("gx must be contiguous and of `shape`")
+        self._units.check(self._lib.mulut_net_gx_gather(self.device.index, mode.encode(), r, t.data_ptr(), t.shape[1], N, C, H, W, gx.data_ptr(),
+                                                        int(accumulate), self._stream()))
+        return gx
 
     # -- compute ------------------------------------------------------------------------------
     def stage_sum(self, stage, x):

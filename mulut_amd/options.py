@@ -93,7 +93,7 @@ class TrainOptions:
     """The reference's training command line (common/option.py:13-31,160-187), flag for flag with its defaults, for
     ``mulut_amd.train_model``.  ``parse()`` makes ``expDir`` and ``{expDir}/val`` (``opt.valoutDir``), writes ``opt.txt`` as the
     reference does, applies ``--debug``'s short schedule (:147-151) and, like ``TestOptions``, copies the code only with
-    ``--saveCode``.  Additions default to the reference's behaviour: ``--torchPath``, ``--hostData``, ``--seed``."""
+    ``--saveCode``.  Additions default to the reference's behaviour: ``--torchPath``, ``--hostData``, ``--seed``, ``--deterministic``, ``--saveOpt``."""
 
     def __init__(self, debug=False):
         self.debug = debug
@@ -136,6 +136,12 @@ class TrainOptions:
         parser.add_argument('--hostData', action='store_true', default=False,
                             help="cut the batches on the host (CropProvider, the reference's path) instead of on the device")
         parser.add_argument('--seed', type=int, default=None, help="seed of the initial weights and of the crops")
+        parser.add_argument('--deterministic', action='store_true', default=False,
+                            help="bit-reproducible gradients: the input gradient of every stage is gathered per pixel in a fixed "
+                                 "order (mulut_net_stage_backward_exact) instead of added with float atomics")
+        parser.add_argument('--saveOpt', action='store_true', default=False,
+                            help="beside every Model_{i:06d}.pth also write Opt_{i:06d}.pth (the optimiser's state and the crop "
+                                 "draws' generator state), which --startIter loads when it exists: an exact resume")
         parser.add_argument('--saveCode', action='store_true', default=False,
                             help="copy *.py under cwd into <expDir>/code like the reference's parse()")
         return parser

@@ -9,7 +9,12 @@ the tests.  Batches come from `ft_data.DeviceCropProvider` (`--hostData`: `CropP
 `net_val.net_valid_steps`, and `Model_{:06d}.pth` is `torch.save(model_G)`, which `network.load_checkpoint` and so
 `transfer_to_lut` (with `--fused` too) read.  The log lines are the reference's.  TensorBoard scalars are written only if
 `torch.utils.tensorboard` imports.  `--startIter N` loads `Model_{N:06d}.pth` as the reference intends (its own call is broken) and
-advances the schedule to N; the optimiser state starts fresh, because the reference never saved it.  `--gpuNum > 1` is refused.
+advances the schedule to N; the optimiser state starts fresh, because the reference never saved it -- unless the run that wrote
+the checkpoint had `--saveOpt`: then `Opt_{N:06d}.pth` (the name the reference's own resume asks for, :163) lies beside it with
+`opt_G.state_dict()` and the state of the crop draws' generator, both are loaded, and the run goes on exactly where the other stood.
+`--deterministic` trains on `mulut_net_stage_backward_exact`: the input gradient of a stage is gathered in a fixed order, so with
+`--seed` two runs write the same `Model_*.pth`, tensor for tensor (it has no meaning for `--torchPath` and is refused with it).
+`--gpuNum > 1` is refused.
 """
 import math
 import os
@@ -27,15 +32,20 @@ from .net_val import net_valid_steps
 from .options import TrainOptions
 
 
-def save_checkpoint(model_G, opt, i, log):
-    """sr/1_train_model.py:58-67"""
+def save_checkpoint(model_G, opt, i, log, opt_G=None, train_iter=None):
+    """sr/1_train_model.py:58-67; with --saveOpt also what an exact resume needs: the optimiser's state and the state of the crop
+    draws' generator as it stands before the draw of iteration i + 1."""
     torch.save(model_G, os.path.join(opt.expDir, 'Model_{:06d}{}.pth'.format(i, '')))
+    if opt.saveOpt:
+        torch.save({"opt_G": opt_G.state_dict(), "rng": train_iter.rng.getstate()}, os.path.join(opt.expDir, 'Opt_{:06d}.pth'.format(i)))
     log("Checkpoint saved {}".format(str(i)))
 
 
 def train(opt, log=print):
     if opt.gpuNum > 1:
         raise SystemExit("--gpuNum {}: this driver trains on one GPU (DataParallel is out of scope)".format(opt.gpuNum))
+    if opt.deterministic and opt.torchPath:
+        raise SystemExit("--deterministic selects a backward of the fused HIP kernels and cannot be combined with --torchPath")
     try:
         from torch.utils.tensorboard import SummaryWriter
         writer = SummaryWriter(log_dir=opt.expDir)
@@ -54,12 +64,21 @@ def train(opt, log=print):
         lr_b = opt.lr1 / opt.lr0
         lr_a = 1 - lr_b
         lf = lambda x: (((1 + math.cos(x * math.pi / opt.totalIter)) / 2) ** 1.0) * lr_a + lr_b   # noqa: E731
+    resume = None
     if opt.startIter > 0:      # :158-164 as intended: the module's parameters; the schedule goes on from startIter
         lm = network.load_checkpoint(os.path.join(opt.expDir, 'Model_{:06d}.pth'.format(opt.startIter)))
         model_G.load_state_dict(lm.state_dict(), strict=True)
+        opt_path = os.path.join(opt.expDir, 'Opt_{:06d}.pth'.format(opt.startIter))
+        if os.path.exists(opt_path):      # --saveOpt wrote it: the optimiser goes on where it stood, and below the crop draws do
+            resume = torch.load(opt_path, map_location=next(model_G.parameters()).device, weights_only=False)
+            opt_G.load_state_dict(resume["opt_G"])
+            log("{} | optimiser state loaded from {}".format(opt.expDir, opt_path))
     start = opt.startIter
     scheduler = optim.lr_scheduler.LambdaLR(opt_G, lr_lambda=lambda x: lf(x + start))
-    trainer = None if opt.torchPath else NetTrainer(model_G)
+    trainer = None if opt.torchPath else NetTrainer(model_G, deterministic=opt.deterministic)
+    if opt.deterministic:
+        log("{} | deterministic backward: the input gradient of every stage is gathered per pixel in a fixed order{}".format(
+            opt.expDir, "" if opt.seed is not None else " (no --seed: the weights and the draws are not fixed)"))
     if opt.hostData:
         train_iter = CropProvider(opt.trainDir, opt.scale, opt.cropSize, opt.batchSize, opt.seed, log=log)
     else:
@@ -69,6 +88,8 @@ def train(opt, log=print):
         except TrainingSetTooLarge as e:
             log("{} | training set of {} bytes exceeds half the free device memory ({}): batches are cut on the host".format(opt.expDir, e.nbytes, e.limit))
             train_iter = e.host
+    if resume is not None:
+        train_iter.rng.setstate(resume["rng"])
     engine = None
     if not os.path.isdir(opt.valDir):      # (the reference's SRBenchmark would fail here; a run without validation sets is allowed, and said)
         log("{} | valDir {} is not a directory: validation is skipped".format(opt.expDir, opt.valDir))
@@ -106,7 +127,7 @@ def train(opt, log=print):
             dT = 0.
             rT = 0.
         if i % opt.saveStep == 0:
-            save_checkpoint(model_G, opt, i, log)
+            save_checkpoint(model_G, opt, i, log, opt_G, train_iter)
         if i % opt.valStep == 0 and os.path.isdir(opt.valDir):
             if engine is None:
                 engine = NetEngine(model_G, device=next(model_G.parameters()).device.index)
