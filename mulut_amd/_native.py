@@ -14,20 +14,88 @@ HEADERS = ["mulut_core.h", "mulut_interval.h", "mulut_ft.h", "mulut_ft_interval.
 # (tools/gen_tube2_asm.py); -Wno-pass-failed: its occupancy attribute is that budget, not an occupancy the kernel reaches
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-inline-asm", "-Wno-pass-failed"]
 
-# every symbol include/mulut.h declares
-EXPORTS = [
-    "mulut_version", "mulut_strerror", "mulut_last_hip_error", "mulut_create", "mulut_destroy",
-    "mulut_configure", "mulut_set_lut", "mulut_read_table_image", "mulut_pass", "mulut_stage", "mulut_pipeline",
-    "mulut_pipeline_rows", "mulut_halo", "mulut_reserve", "mulut_set_stage_timing", "mulut_last_stage_ms", "mulut_last_kernel_ms",
-    "mulut_set_tuning", "mulut_kernel_name", "mulut_ft_stage_forward", "mulut_ft_stage_backward", "mulut_ft_quantize", "mulut_ft_quantize_backward", "mulut_ft_adam",
-    "mulut_ft_stage_forward_mask", "mulut_ft_stage_backward_mask", "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward",
-    "mulut_ft_wide_stage_forward", "mulut_ft_wide_stage_backward", "mulut_ft_exact_ws_bytes", "mulut_ft_exact_stage_backward", "mulut_ft_crop_batch", "mulut_ft_val_pack",
-    "mulut_eval_ws_doubles", "mulut_eval_y", "mulut_eval_plan_create", "mulut_eval_plan_run", "mulut_eval_plan_destroy", "mulut_eval_finish", "mulut_last_detail_counters", "mulut_debug_read",
-    "mulut_resample_coeffs", "mulut_resample_plan_create", "mulut_resample_plan_destroy", "mulut_resample_run",
-    "mulut_net_unit_create", "mulut_net_unit_destroy", "mulut_net_table", "mulut_net_pass", "mulut_net_stage",
-    "mulut_net_unit_create_train", "mulut_net_unit_load_dev", "mulut_net_unit_read", "mulut_net_pack_host", "mulut_net_stage_sum", "mulut_net_backward_ws_bytes",
-    "mulut_net_stage_backward", "mulut_net_backward_exact_ws_bytes", "mulut_net_stage_backward_exact", "mulut_net_gx_gather",
-]
+
+def _prototypes():
+    """One entry per function of include/mulut.h, in the header's order: name -> (restype, argtypes).  The typed pointers are what
+    call sites hand byref() objects and ctypes arrays to; device and opaque pointers are plain c_void_p (callers pass data_ptr())."""
+    i, p, s, c, ll, d = ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char, ctypes.c_longlong, ctypes.c_double
+    pp, fp, dp, i32p = ctypes.POINTER(p), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(d), ctypes.POINTER(ctypes.c_int32)
+    fpp = ctypes.POINTER(fp)
+    return {
+        # the context and the inference cascade
+        "mulut_version": (i, []),
+        "mulut_strerror": (s, [i]),
+        "mulut_last_hip_error": (s, [p]),
+        "mulut_create": (i, [i, pp]),
+        "mulut_destroy": (i, [p]),
+        "mulut_configure": (i, [p, i, s, i, i]),
+        "mulut_set_lut": (i, [p, i, c, p, ll, i]),
+        "mulut_read_table_image": (ll, [p, i, c, i, p, ll, p]),
+        "mulut_pass": (i, [p, i, c, i, p, i, i, i, p, p]),
+        "mulut_stage": (i, [p, i, p, i, p, i, i, i, i, i, p]),
+        "mulut_pipeline": (i, [p, p, p, i, i, i, i, i, p]),
+        "mulut_pipeline_rows": (i, [p, p, i, i, p, i, i, i, i, i, i, i, p]),
+        "mulut_halo": (i, [p]),
+        "mulut_reserve": (i, [p, i, i, i, i]),
+        "mulut_set_stage_timing": (i, [p, i]),
+        "mulut_last_stage_ms": (i, [p, fp, i]),
+        "mulut_last_kernel_ms": (i, [p, fp, i]),
+        "mulut_last_detail_counters": (i, [p, ctypes.POINTER(ctypes.c_uint32), i, p]),
+        "mulut_debug_read": (i, [p, ctypes.POINTER(ctypes.c_uint64), i, i, p]),
+        # LUT-aware fine-tuning
+        "mulut_ft_quantize": (i, [i, p, p, i, ll, p]),
+        "mulut_ft_quantize_backward": (i, [i, p, p, i, ll, p]),
+        "mulut_ft_adam": (i, [i, p, p, p, p, p, i, ll, d, d, d, d, d, p]),
+        "mulut_ft_stage_forward": (i, [i, p, s, i, i, p, i, i, i, i, p, p]),
+        "mulut_ft_stage_backward": (i, [i, p, s, i, i, p, p, i, i, i, i, p, p, p]),
+        "mulut_ft_stage_forward_mask": (i, [i, p, s, i, i, p, i, i, i, i, p, p, p]),
+        "mulut_ft_stage_backward_mask": (i, [i, p, s, i, i, p, p, p, i, i, i, i, p, p, p]),
+        "mulut_ft_interval_stage_forward": (i, [i, i, p, s, i, i, p, i, i, i, i, p, p, p]),
+        "mulut_ft_interval_stage_backward": (i, [i, i, p, s, i, i, p, p, p, i, i, i, i, p, p, p]),
+        "mulut_ft_wide_stage_forward": (i, [i, i, p, s, i, i, p, i, i, i, i, p, p, p]),
+        "mulut_ft_wide_stage_backward": (i, [i, i, p, s, i, i, p, p, p, i, i, i, i, p, p, p]),
+        "mulut_ft_exact_ws_bytes": (ll, [i, s, i, i, i, i, i]),
+        "mulut_ft_exact_stage_backward": (i, [i, i, p, s, i, i, p, p, p, i, i, i, i, p, p, p, ll, p]),
+        "mulut_ft_crop_batch": (i, [i, p, ll, p, i, p, i, i, i, p, p, p, p]),
+        "mulut_ft_val_pack": (i, [i, p, i, i, p, p]),
+        # device-side evaluation
+        "mulut_eval_ws_doubles": (ll, [i, i]),
+        "mulut_eval_y": (i, [i, p, p, i, i, i, p, ll, dp, dp, p]),
+        "mulut_eval_plan_create": (i, [i, p, i, i, pp]),
+        "mulut_eval_plan_run": (i, [p, p, p, p, p]),
+        "mulut_eval_plan_destroy": (i, [p]),
+        "mulut_eval_finish": (i, [d, d, i, i, i, dp, dp]),
+        # LR images made on the device
+        "mulut_resample_coeffs": (i, [i, i, i32p, i32p, i32p, ll]),
+        "mulut_resample_plan_create": (i, [i, i, i, i, i, pp]),
+        "mulut_resample_plan_destroy": (i, [p]),
+        "mulut_resample_run": (i, [p, p, i, p, i, i, i, p]),
+        # the trained network, fused
+        "mulut_net_unit_create": (i, [i, i, i, fpp, fpp, pp]),
+        "mulut_net_unit_destroy": (i, [p]),
+        "mulut_net_table": (i, [p, i, p, p]),
+        "mulut_net_pass": (i, [p, c, i, p, i, i, i, i, p, p]),
+        "mulut_net_stage": (i, [pp, s, i, p, p, i, i, i, i, p]),
+        # training the network
+        "mulut_net_unit_create_train": (i, [i, i, i, pp]),
+        "mulut_net_unit_load_dev": (i, [p, pp, pp, p]),
+        "mulut_net_pack_host": (ll, [i, i, fpp, fpp, i, p, ll]),
+        "mulut_net_unit_read": (ll, [p, i, p, ll]),
+        "mulut_net_stage_sum": (i, [pp, s, p, i, i, i, i, p, p]),
+        "mulut_net_backward_ws_bytes": (ll, [i, i, ll]),
+        "mulut_net_stage_backward": (i, [pp, s, p, p, i, i, i, i, p, ll, p, pp, pp, p]),
+        # the same backward with a bit-reproducible gx
+        "mulut_net_backward_exact_ws_bytes": (ll, [i, i, ll, ll]),
+        "mulut_net_stage_backward_exact": (i, [pp, s, p, p, i, i, i, i, p, ll, p, pp, pp, p]),
+        "mulut_net_gx_gather": (i, [i, c, i, p, ll, i, i, i, i, p, i, p]),
+        # tuning knobs and kernel names
+        "mulut_set_tuning": (i, [p, s, i]),
+        "mulut_kernel_name": (s, [p, i]),
+    }
+
+
+PROTOTYPES = _prototypes()
+EXPORTS = list(PROTOTYPES)       # every symbol include/mulut.h declares
 
 _libs = {}
 
@@ -157,101 +225,19 @@ def load(path=None):
             raise RuntimeError("libmulut_hip.so is missing and hipcc is unavailable; "
                                "run `python -c 'import __graft_entry__ as g; g.build()'`")
     L = ctypes.CDLL(path)
-    i, p, c_char_p, i64 = ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64
-    L.mulut_version.restype = i
-    L.mulut_strerror.argtypes = [i]
-    L.mulut_strerror.restype = c_char_p
-    L.mulut_last_hip_error.argtypes = [p]
-    L.mulut_last_hip_error.restype = c_char_p
-    L.mulut_create.argtypes = [i, ctypes.POINTER(p)]
-    L.mulut_destroy.argtypes = [p]
-    L.mulut_configure.argtypes = [p, i, c_char_p, i, i]
-    L.mulut_set_lut.argtypes = [p, i, ctypes.c_char, p, i64, i]
-    L.mulut_read_table_image.argtypes = [p, i, ctypes.c_char, i, p, ctypes.c_longlong, p]
-    L.mulut_read_table_image.restype = ctypes.c_longlong
-    L.mulut_pass.argtypes = [p, i, ctypes.c_char, i, p, i, i, i, p, p]
-    L.mulut_stage.argtypes = [p, i, p, i, p, i, i, i, i, i, p]
-    L.mulut_pipeline.argtypes = [p, p, p, i, i, i, i, i, p]
-    L.mulut_pipeline_rows.argtypes = [p, p, i, i, p, i, i, i, i, i, i, i, p]
-    L.mulut_halo.argtypes = [p]
-    L.mulut_reserve.argtypes = [p, i, i, i, i]
-    L.mulut_set_stage_timing.argtypes = [p, i]
-    L.mulut_last_stage_ms.argtypes = [p, ctypes.POINTER(ctypes.c_float), i]
-    L.mulut_last_kernel_ms.argtypes = [p, ctypes.POINTER(ctypes.c_float), i]
-    L.mulut_last_detail_counters.argtypes = [p, ctypes.POINTER(ctypes.c_uint32), i, p]
-    L.mulut_last_detail_counters.restype = i
-    L.mulut_debug_read.argtypes = [p, ctypes.POINTER(ctypes.c_uint64), i, i, p]
-    L.mulut_debug_read.restype = i
-    L.mulut_set_tuning.argtypes = [p, c_char_p, i]
-    L.mulut_kernel_name.argtypes = [p, i]
-    L.mulut_ft_stage_forward.argtypes = [i, p, c_char_p, i, i, p, i, i, i, i, p, p]
-    L.mulut_ft_stage_backward.argtypes = [i, p, c_char_p, i, i, p, p, i, i, i, i, p, p, p]
-    L.mulut_ft_stage_forward_mask.argtypes = [i, p, c_char_p, i, i, p, i, i, i, i, p, p, p]
-    L.mulut_ft_stage_backward_mask.argtypes = [i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p]
-    L.mulut_ft_interval_stage_forward.argtypes = [i, i, p, c_char_p, i, i, p, i, i, i, i, p, p, p]
-    L.mulut_ft_interval_stage_backward.argtypes = [i, i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p]
-    L.mulut_ft_wide_stage_forward.argtypes = [i, i, p, c_char_p, i, i, p, i, i, i, i, p, p, p]
-    L.mulut_ft_wide_stage_backward.argtypes = [i, i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p]
-    L.mulut_ft_exact_ws_bytes.argtypes = [i, c_char_p, i, i, i, i, i]
-    L.mulut_ft_exact_ws_bytes.restype = ctypes.c_longlong
-    L.mulut_ft_exact_stage_backward.argtypes = [i, i, p, c_char_p, i, i, p, p, p, i, i, i, i, p, p, p, ctypes.c_longlong, p]
-    L.mulut_ft_exact_stage_backward.restype = i
-    L.mulut_ft_crop_batch.argtypes = [i, p, ctypes.c_longlong, p, i, p, i, i, i, p, p, p, p]
-    L.mulut_kernel_name.restype = c_char_p
-    L.mulut_ft_quantize.argtypes = [i, p, p, i, ctypes.c_longlong, p]
-    L.mulut_ft_quantize_backward.argtypes = [i, p, p, i, ctypes.c_longlong, p]
-    d = ctypes.c_double
-    L.mulut_ft_adam.argtypes = [i, p, p, p, p, p, i, ctypes.c_longlong, d, d, d, d, d, p]
-    L.mulut_ft_adam.restype = i
-    L.mulut_eval_ws_doubles.argtypes = [i, i]
-    L.mulut_eval_ws_doubles.restype = ctypes.c_longlong
-    L.mulut_eval_y.argtypes = [i, p, p, i, i, i, p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double),
-                               ctypes.POINTER(ctypes.c_double), p]
-    L.mulut_eval_y.restype = i
-    L.mulut_eval_plan_create.argtypes = [i, p, i, i, ctypes.POINTER(p)]
-    L.mulut_eval_plan_run.argtypes = [p, p, p, p, p]
-    L.mulut_eval_plan_destroy.argtypes = [p]
-    L.mulut_eval_finish.argtypes = [d, d, i, i, i, ctypes.POINTER(d), ctypes.POINTER(d)]
-    L.mulut_ft_val_pack.argtypes = [i, p, i, i, p, p]
-    for name in ("mulut_eval_plan_create", "mulut_eval_plan_run", "mulut_eval_plan_destroy", "mulut_eval_finish", "mulut_ft_val_pack"):
-        getattr(L, name).restype = i
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    L.mulut_resample_coeffs.argtypes = [i, i, i32p, i32p, i32p, ctypes.c_longlong]
-    L.mulut_resample_plan_create.argtypes = [i, i, i, i, i, ctypes.POINTER(p)]
-    L.mulut_resample_plan_destroy.argtypes = [p]
-    L.mulut_resample_run.argtypes = [p, p, i, p, i, i, i, p]
-    for name in ("mulut_resample_coeffs", "mulut_resample_plan_create", "mulut_resample_plan_destroy", "mulut_resample_run"):
-        getattr(L, name).restype = i
-    fpp = ctypes.POINTER(ctypes.POINTER(ctypes.c_float))
-    L.mulut_net_unit_create.argtypes = [i, i, i, fpp, fpp, ctypes.POINTER(p)]
-    L.mulut_net_unit_destroy.argtypes = [p]
-    L.mulut_net_table.argtypes = [p, i, p, p]
-    L.mulut_net_pass.argtypes = [p, ctypes.c_char, i, p, i, i, i, i, p, p]
-    L.mulut_net_stage.argtypes = [ctypes.POINTER(p), c_char_p, i, p, p, i, i, i, i, p]
-    for name in ("mulut_net_unit_create", "mulut_net_unit_destroy", "mulut_net_table", "mulut_net_pass", "mulut_net_stage"):
-        getattr(L, name).restype = i
-    for name in ("mulut_create", "mulut_destroy", "mulut_configure", "mulut_set_lut", "mulut_pass", "mulut_stage",
-                 "mulut_pipeline", "mulut_pipeline_rows", "mulut_halo", "mulut_reserve", "mulut_set_stage_timing",
-                 "mulut_last_stage_ms", "mulut_last_kernel_ms", "mulut_set_tuning", "mulut_ft_stage_forward", "mulut_ft_stage_backward",
-                 "mulut_ft_quantize", "mulut_ft_quantize_backward", "mulut_ft_stage_forward_mask", "mulut_ft_stage_backward_mask",
-                 "mulut_ft_interval_stage_forward", "mulut_ft_interval_stage_backward", "mulut_ft_wide_stage_forward",
-                 "mulut_ft_wide_stage_backward", "mulut_ft_crop_batch"):
-        getattr(L, name).restype = i
-    L.mulut_net_unit_create_train.argtypes = [i, i, i, ctypes.POINTER(p)]
-    L.mulut_net_unit_load_dev.argtypes = [p, ctypes.POINTER(p), ctypes.POINTER(p), p]
-    L.mulut_net_unit_read.argtypes = [p, i, p, ctypes.c_longlong]
-    L.mulut_net_stage_sum.argtypes = [ctypes.POINTER(p), c_char_p, p, i, i, i, i, p, p]
-    L.mulut_net_backward_ws_bytes.argtypes = [i, i, ctypes.c_longlong]
-    L.mulut_net_stage_backward.argtypes = [ctypes.POINTER(p), c_char_p, p, p, i, i, i, i, p, ctypes.c_longlong, p, ctypes.POINTER(p),
-                                           ctypes.POINTER(p), p]
-    L.mulut_net_backward_exact_ws_bytes.argtypes = [i, i, ctypes.c_longlong, ctypes.c_longlong]
-    L.mulut_net_stage_backward_exact.argtypes = L.mulut_net_stage_backward.argtypes
-    L.mulut_net_gx_gather.argtypes = [i, ctypes.c_char, i, p, ctypes.c_longlong, i, i, i, i, p, i, p]
-    for name in ("mulut_net_unit_create_train", "mulut_net_unit_load_dev", "mulut_net_stage_sum", "mulut_net_stage_backward",
-                 "mulut_net_stage_backward_exact", "mulut_net_gx_gather"):
-        getattr(L, name).restype = i
-    L.mulut_net_pack_host.argtypes = [i, i, fpp, fpp, i, p, ctypes.c_longlong]
-    for name in ("mulut_net_unit_read", "mulut_net_backward_ws_bytes", "mulut_net_backward_exact_ws_bytes", "mulut_net_pack_host"):
-        getattr(L, name).restype = ctypes.c_longlong
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _libs[path] = L
     return L
+
+
+def stream_ptr(device=None):
+    """The current torch stream of `device` as the void* every `stream` parameter of the ABI takes."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr_array(tensors):
+    """The data pointers of `tensors` as a void*[]: what the `const float *const *` parameters take."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])

@@ -37,8 +37,7 @@ def eval_y(gt_hwc, out_hwc, shave, lib=None):
     ws = torch.empty(n, dtype=torch.float64, device=gt.device)
     psnr, ssim = ctypes.c_double(), ctypes.c_double()
     _native.check(lib.mulut_eval_y(gt.device.index, gt.data_ptr(), out.data_ptr(), H, W, int(shave), ws.data_ptr(), n,
-                                   ctypes.byref(psnr), ctypes.byref(ssim), ctypes.c_void_p(torch.cuda.current_stream(gt.device).cuda_stream)),
-                  MuLUTError)
+                                   ctypes.byref(psnr), ctypes.byref(ssim), _native.stream_ptr(gt.device)), MuLUTError)
     return psnr.value, ssim.value
 
 
@@ -79,7 +78,7 @@ class MuLUTEngine:
             pass
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _native.stream_ptr(self.device)
 
     def _need_config(self):
         if self.stages is None:

@@ -16,10 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _native
-
-
-def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+from ._native import ptr_array, stream_ptr
 
 
 class _StageFn(torch.autograd.Function):
@@ -37,7 +34,7 @@ class _StageFn(torch.autograd.Function):
                 raise ValueError("a table lives on {}, x on {}".format(w.device, x.device))
         lib = _native.load()
         x = x.contiguous()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = stream_ptr(x.device)
         # weight = clamp(round_func(weight * 127), -127, 127)       sr/model.py:74-76, the stage's tables in one launch
         ws = [w.detach().contiguous() for w in weights]
         n = ws[0].numel()
@@ -45,13 +42,13 @@ class _StageFn(torch.autograd.Function):
             raise ValueError("the tables of a stage must be float32 of one shape")
         wq_all = torch.empty((len(ws), n), dtype=torch.float32, device=x.device)
         wq = [wq_all[m].view(w.shape) for m, w in enumerate(ws)]
-        _native.check(lib.mulut_ft_quantize(x.device.index, _ptr_array(ws), _ptr_array(wq), len(ws), n, stream))
+        _native.check(lib.mulut_ft_quantize(x.device.index, ptr_array(ws), ptr_array(wq), len(ws), n, stream))
         B, C, H, W = x.shape
         out = torch.empty((B, C, H * u, W * u), dtype=torch.float32, device=x.device)
         # where the stage's clamp passes gradient, 16 bits per site: saves the backward a recomputation of the stage forward
         inside = torch.empty((B, C, H, W), dtype=torch.int16, device=x.device)
         # any list over s, d, y, e, h, o at interval 4, 5 or 6: for a list of s, d, y the launches of the narrow entry points
-        rc = lib.mulut_ft_wide_stage_forward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
+        rc = lib.mulut_ft_wide_stage_forward(x.device.index, int(interval), ptr_array(wq), modes.encode(), int(is_last), int(u),
                                              x.data_ptr(), B, C, H, W, out.data_ptr(), inside.data_ptr(), stream)
         if rc == -2:      # MULUT_EMODE: the reference's ValueError("Mode {} not implemented.")
             raise ValueError(lib.mulut_strerror(rc).decode())
@@ -71,21 +68,21 @@ class _StageFn(torch.autograd.Function):
         g_all = torch.zeros_like(wq_all)
         gwq = [g_all[m].view(w.shape) for m, w in enumerate(ws)]
         gx = torch.zeros_like(x)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = stream_ptr(x.device)
         if getattr(ctx, "exact", False):
             # fixed-point sums (mulut_ft_exact_stage_backward): the same bits whatever order the hardware runs the waves in.  The
             # workspace comes from torch's allocator on the current stream, so its reuse is ordered behind this call.
             need = _native.check(lib.mulut_ft_exact_ws_bytes(int(interval), modes.encode(), int(u), B, C, H, W))
             work = torch.empty(need // 8, dtype=torch.int64, device=x.device)
-            _native.check(lib.mulut_ft_exact_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
-                                                            x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
+            _native.check(lib.mulut_ft_exact_stage_backward(x.device.index, int(interval), ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                                            x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, ptr_array(gwq),
                                                             gx.data_ptr(), work.data_ptr(), need, stream))
         else:
-            _native.check(lib.mulut_ft_wide_stage_backward(x.device.index, int(interval), _ptr_array(wq), modes.encode(), int(is_last), int(u),
-                                                           x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, _ptr_array(gwq),
+            _native.check(lib.mulut_ft_wide_stage_backward(x.device.index, int(interval), ptr_array(wq), modes.encode(), int(is_last), int(u),
+                                                           x.data_ptr(), gout.data_ptr(), inside.data_ptr(), B, C, H, W, ptr_array(gwq),
                                                            gx.data_ptr(), stream))
         # backward of clamp(round_func(w*127)): round is identity (BPDA), clamp passes inside [-127,127], x127 -- in place, one launch
-        _native.check(lib.mulut_ft_quantize_backward(x.device.index, _ptr_array(ws), _ptr_array(gwq), len(ws), ws[0].numel(), stream))
+        _native.check(lib.mulut_ft_quantize_backward(x.device.index, ptr_array(ws), ptr_array(gwq), len(ws), ws[0].numel(), stream))
         return (gx, None, None, None, None) + tuple(gwq)
 
 
@@ -229,8 +226,8 @@ class Adam(torch.optim.Optimizer):
             for (device, step), ps in by_step.items():
                 grads = [p.grad.contiguous() for p in ps]
                 n = (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps])
-                _native.check(lib.mulut_ft_adam(device.index, _ptr_array(ps), _ptr_array(grads), _ptr_array([self.state[p]["exp_avg"] for p in ps]),
-                                                _ptr_array([self.state[p]["exp_avg_sq"] for p in ps]), n, len(ps), step, float(group["lr"]),
+                _native.check(lib.mulut_ft_adam(device.index, ptr_array(ps), ptr_array(grads), ptr_array([self.state[p]["exp_avg"] for p in ps]),
+                                                ptr_array([self.state[p]["exp_avg_sq"] for p in ps]), n, len(ps), step, float(group["lr"]),
                                                 group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"],
-                                                ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+                                                stream_ptr(device)))
         return loss

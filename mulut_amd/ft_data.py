@@ -2,7 +2,6 @@
 providers that cut batches from them -- ``CropProvider`` on the host (the reference's path, sr/data.py:96-124) and
 ``DeviceCropProvider`` on the device (``mulut_ft_crop_batch``).  Both take their pairs from ``scan_pairs`` and their draws from
 ``draw_sample``, so the same ``--seed`` gives the same batches, bit for bit, by construction."""
-import ctypes
 import os
 import random
 
@@ -180,5 +179,5 @@ class DeviceCropProvider:
         lb = torch.empty((self.batch, 1, self.sz * self.scale, self.sz * self.scale), dtype=torch.float32, device=self.device)
         _native.check(self._lib.mulut_ft_crop_batch(self.device.index, self.pool.data_ptr(), self.pool_bytes, self.table.data_ptr(), len(self.shapes),
                                                     draws.data_ptr(), self.batch, self.sz, self.scale, im.data_ptr(), lb.data_ptr(),
-                                                    self.bad.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+                                                    self.bad.data_ptr(), _native.stream_ptr(self.device)))
         return im, lb

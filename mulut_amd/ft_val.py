@@ -222,12 +222,12 @@ class DeviceValSet:
     def score(self):
         """One mulut_eval_plan_run per dataset on the current stream, then the point's only wait: the sums of all datasets read back
         once.  Returns {dataset: float64 array [images, 2]} of (PSNR, SSIM), mulut_eval_finish applied per image."""
-        stream = torch.cuda.current_stream(self.device)
+        stream = _native.stream_ptr(self.device)
         for s in self.sets:
             _native.check(self.lib.mulut_eval_plan_run(s["plan"], self.gt_pool.data_ptr(), self.out_pool.data_ptr(),
-                                                       self.sums[s["first"]:].data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+                                                       self.sums[s["first"]:].data_ptr(), stream))
         self.sums_host.copy_(self.sums, non_blocking=True)
-        stream.synchronize()
+        torch.cuda.current_stream(self.device).synchronize()
         sums, out = self.sums_host.numpy(), {}
         ps, ss = ctypes.c_double(), ctypes.c_double()
         for s in self.sets:
@@ -290,7 +290,7 @@ def resident_valid_steps(net, vset, opt, it, log=print):
     lib, was_training = vset.lib, net.training
     net.eval()
     vset.before_write()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(vset.device).cuda_stream)
+    stream = _native.stream_ptr(vset.device)
     with torch.no_grad():
         for n, (_, H, W, _, _, _) in enumerate(vset.shapes):
             pred = net(vset.lr_tensor(n)).contiguous()

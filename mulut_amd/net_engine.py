@@ -68,14 +68,11 @@ def discover(model_G, need_bias=False):
 
 def unit_param_pointers(unit, device):
     """(w[6], b[6]) as ctypes arrays of device pointers for mulut_net_unit_load_dev, and the tensors that must outlive the launch."""
-    keep, ws, bs = [], [], []
+    ws, bs = [], []
     for c in unit_layers(unit):
-        w = c.weight.detach().to(device=device, dtype=torch.float32).contiguous()
-        b = (c.bias.detach() if c.bias is not None else torch.zeros(c.weight.shape[0])).to(device=device, dtype=torch.float32).contiguous()
-        keep += [w, b]
-        ws.append(w.data_ptr())
-        bs.append(b.data_ptr())
-    return (ctypes.c_void_p * 6)(*ws), (ctypes.c_void_p * 6)(*bs), keep
+        ws.append(c.weight.detach().to(device=device, dtype=torch.float32).contiguous())
+        bs.append((c.bias.detach() if c.bias is not None else torch.zeros(c.weight.shape[0])).to(device=device, dtype=torch.float32).contiguous())
+    return _native.ptr_array(ws), _native.ptr_array(bs), ws + bs
 
 
 class NetUnits:
@@ -123,7 +120,7 @@ class NetUnits:
             pass
 
     def stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _native.stream_ptr(self.device)
 
     def nf(self, stage):
         return self.shape[(stage, self.modes[0])][0]

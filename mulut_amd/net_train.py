@@ -9,11 +9,9 @@ site and weight-gradient kernels per (mode, rotation) pass and hands autograd th
 tensors, so `p.grad`, `torch.optim.Adam` and `LambdaLR` work as they do on the torch operators.  `predict` restates `mulut_predict`
 (:26-45) over it; the stage's own arithmetic (average, bias, clamp, BPDA round, / 255) stays a few torch element-wise operators.
 """
-import ctypes
-
 import torch
 
-from . import network
+from . import _native, network
 from .engine import MuLUTError
 from .net_engine import NetUnits, _no_gpu, unit_layers
 
@@ -149,8 +147,8 @@ class NetTrainer:
         params = self.stage_params(stage)
         grads = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in params]
         M = len(self.modes)
-        gw = (ctypes.c_void_p * (6 * M))(*[grads[12 * m + l].data_ptr() for m in range(M) for l in range(6)])
-        gb = (ctypes.c_void_p * (6 * M))(*[grads[12 * m + 6 + l].data_ptr() for m in range(M) for l in range(6)])
+        gw = _native.ptr_array([grads[12 * m + l] for m in range(M) for l in range(6)])
+        gb = _native.ptr_array([grads[12 * m + 6 + l] for m in range(M) for l in range(6)])
         entry = self._lib.mulut_net_stage_backward_exact if self.deterministic else self._lib.mulut_net_stage_backward
         self._units.check(entry(self._handles(stage), self.modes.encode(), x.data_ptr(), g.data_ptr(), N, C, H, W, ws.data_ptr(), ws.numel(),
                                 gx.data_ptr() if want_gx else None, gw, gb, self._stream()))

@@ -119,8 +119,8 @@ def bicubic(x, size, out=None):
             raise ValueError("out must be a contiguous uint8 tensor of %d elements on %s" % (N * C * out_h * out_w, t.device))
     plan = _plan(t.device.index, int(in_h), int(in_w), out_h, out_w)
     with torch.cuda.device(t.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-        _native.check(lib.mulut_resample_run(plan._h, t.data_ptr(), layout, res.data_ptr(), layout, int(N), int(C), stream), MuLUTError)
+        _native.check(lib.mulut_resample_run(plan._h, t.data_ptr(), layout, res.data_ptr(), layout, int(N), int(C), _native.stream_ptr(t.device)),
+                      MuLUTError)
     if out is not None:
         return out
     if as_numpy:

@@ -13,6 +13,7 @@ import os
 import shutil
 import struct
 import subprocess
+import sys
 import tempfile
 import zlib
 
@@ -20,10 +21,12 @@ import numpy as np
 
 from conftest import ROOT
 
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from host_abi import SAN      # noqa: E402  (the sanitizer flags of every stand-alone host program)
+
 MAGIC = 0x46584331
 HOST_SRC = os.path.join(ROOT, "tests", "host_emul", "ft_exact_host.cpp")
-HOST_FLAGS = ["-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-              "-fno-omit-frame-pointer"]
+HOST_FLAGS = ["-O2", "-std=c++17", "-Wall", "-ffp-contract=off"] + SAN
 ORDERS = {"ascending": 0, "descending": 1, "shuffled": 2}
 
 

@@ -19,6 +19,77 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(mulut_[a-z_]+)\s*\(", txt)))
 
 
+C_SCALARS = {"int": "int", "char": "char", "long long": "i64", "int64_t": "i64", "double": "double"}
+
+
+def c_kind(decl):
+    """The kind of a C return type or parameter declaration: a scalar of C_SCALARS, "str" (const char *) or "ptr" (every other pointer,
+    arrays included: `const float *const w[6]` is a pointer)."""
+    words = [w for w in re.findall(r"\w+", decl.split("*")[0].split("[")[0]) if w != "const"]
+    if "*" in decl or "[" in decl:
+        return "str" if words == ["char"] and decl.count("*") == 1 and "[" not in decl else "ptr"
+    for ws in (words, words[:-1]):      # with or without a parameter name behind the type
+        if " ".join(ws) in C_SCALARS:
+            return C_SCALARS[" ".join(ws)]
+    return "?" + decl.strip()
+
+
+def header_prototypes():
+    """{name: (return kind, [parameter kinds])} of every function include/mulut.h declares, in its order."""
+    txt = open(os.path.join(ROOT, "include", "mulut.h")).read()
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*", " ", txt, flags=re.S)
+    txt = re.sub(r"^[ \t]*#.*$", "", txt, flags=re.M)
+    out = {}
+    for stmt in txt.split(";"):      # (a prototype may span several lines)
+        m = re.match(r"^(.*?)\b(mulut_\w+)\s*\((.*)\)\s*$", stmt.strip(), flags=re.S)
+        if m:
+            params = m.group(3).strip()
+            out[m.group(2)] = (c_kind(m.group(1)), [] if params == "void" else [c_kind(a) for a in params.split(",")])
+    return out
+
+
+def ctypes_kind(t):
+    scalars = {ctypes.c_int: "int", ctypes.c_char: "char", ctypes.c_longlong: "i64", ctypes.c_double: "double", ctypes.c_char_p: "str"}
+    if t in scalars:
+        return scalars[t]
+    return "ptr" if t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)) else "?%r" % (t,)
+
+
+def signature_mismatches(prototypes):
+    """Every disagreement between a {name: (restype, argtypes)} table and the header, as "name: what": a name on one side only, the
+    argument count, a parameter, the return type."""
+    declared, bad = header_prototypes(), []
+    for name in sorted(set(declared) | set(prototypes)):
+        if name not in declared or name not in prototypes:
+            bad.append("%s: %s" % (name, "not declared in the header" if name in prototypes else "declared, but not in the table"))
+            continue
+        (ret, params), (restype, argtypes) = declared[name], prototypes[name]
+        if ctypes_kind(restype) != ret:
+            bad.append("%s: returns %s, restype %r" % (name, ret, restype))
+        if len(argtypes) != len(params):
+            bad.append("%s: %d parameters, %d argtypes" % (name, len(params), len(argtypes)))
+        bad += ["%s: parameter %d is %s, argtype %r" % (name, k, c, t) for k, (c, t) in enumerate(zip(params, argtypes)) if ctypes_kind(t) != c]
+    return bad
+
+
+def test_prototype_table_matches_the_header():
+    assert signature_mismatches(_native.PROTOTYPES) == []
+    assert len(header_prototypes()) == len(_native.PROTOTYPES) and list(header_prototypes()) == list(_native.PROTOTYPES)
+
+
+def test_signature_check_is_alive():
+    def mutated(name, change):
+        table = {k: (r, list(a)) for k, (r, a) in _native.PROTOTYPES.items()}
+        change(table)
+        bad = signature_mismatches(table)
+        assert bad and all(m.startswith(name + ": ") for m in bad), (name, bad)
+    mutated("mulut_pipeline", lambda t: t["mulut_pipeline"][1].pop())
+    mutated("mulut_ft_quantize", lambda t: t["mulut_ft_quantize"][1].__setitem__(4, ctypes.c_int))      # long long n
+    mutated("mulut_read_table_image", lambda t: t.__setitem__("mulut_read_table_image", (ctypes.c_int, t["mulut_read_table_image"][1])))
+    mutated("mulut_set_lut", lambda t: t["mulut_set_lut"][1].__setitem__(2, ctypes.c_char_p))      # char mode
+    mutated("mulut_net_gx_gather", lambda t: t.pop("mulut_net_gx_gather"))
+
+
 def test_library_exports_every_declared_symbol():
     lib = _native.load()
     names = declared_functions()
@@ -111,8 +182,7 @@ def test_tube2_private_registers_stay_private(tmp_path):
     """stage_tube2_kernel keeps the rows of the pass in flight in v88..v127 across asm statements (tools/gen_tube2_asm.py): the
     compiler must never allocate them.  _native.build() refuses to install a library whose assembly fails this audit; here the
     audit runs on the current sources, and on a doctored listing to show that it bites."""
-    import shutil
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
+    if _native._hipcc() is None:
         pytest.skip("no hipcc")
     assert _native.audit_tube2_isa() == 3
     bad = tmp_path / "bad.s"

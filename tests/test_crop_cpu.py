@@ -2,7 +2,6 @@
 order in which the draws consume random.Random(seed)) against CropProvider, and mulut_ft_crop_batch's host half (refusals, launch
 configuration) as a stand-alone program under AddressSanitizer / UndefinedBehaviorSanitizer against tests/host_emul/fake_hip.cpp."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -84,22 +83,10 @@ def test_host_half_refusals_and_launch_configuration_under_sanitizers(tmp_path):
     """mulut_ft_data.hip's host half + fake_hip.cpp + crop_host.cpp (its own main), -fsanitize=address,undefined, run as a program."""
     from mulut_amd import _native
     import host_abi as tool
-    hipcc = _native._hipcc()
-    if hipcc is None:
+    if _native._hipcc() is None:
         pytest.skip("no hipcc")
     assert "mulut_ft_data.hip" in _native.SOURCES and "mulut_ft_crop_batch" in _native.EXPORTS
-    warn = [f for f in _native.HIPCC_FLAGS if f.startswith("-W") or f.startswith("-std")]
-    host = [hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g"] + warn + [x for f in tool.SAN for x in ("-Xarch_host", f)]
-    out = str(tmp_path)
-    jobs = [subprocess.Popen(host + ["-c", "-o", os.path.join(out, "mulut_ft_data.o"), os.path.join(ROOT, "mulut_amd", "csrc", "mulut_ft_data.hip")])]
-    for s in ("fake_hip", "crop_host"):
-        jobs.append(subprocess.Popen(host + ["-x", "hip", "-c", "-o", os.path.join(out, s + ".o"), os.path.join(tool.EMUL, s + ".cpp")]))
-    assert [p.wait() for p in jobs] == [0, 0, 0]
-    clang = os.path.join(subprocess.check_output([os.path.join(os.path.dirname(hipcc), "hipconfig"), "-l"], text=True).strip(), "clang++")
-    exe = os.path.join(out, "crop_host")
-    subprocess.check_call([clang] + tool.SAN + ["-Wl,--unresolved-symbols=ignore-all", "-o", exe] +
-                          [os.path.join(out, s + ".o") for s in ("mulut_ft_data", "fake_hip", "crop_host")])
-    r = tool.run(exe)
+    r = tool.run(tool.build(str(tmp_path), tool.CSRC, "crop_host", ["mulut_ft_data.hip"]))
     print(r.stdout)
     assert r.stderr == "", r.stderr[-4000:]
     assert r.returncode == 0 and "UNEXPECTED" not in r.stdout and r.stdout.endswith("\n0 unexpected\n")

@@ -6,8 +6,6 @@ tests/golden/host_abi_trace.txt is what that program printed for the sources BEF
 the fine-tune entry points their one dispatcher (`tools/host_abi.py trace OUT --csrc <that checkout>/mulut_amd/csrc`): every call's
 return code, allocations, frees, copies, waits, events and launch configurations.  The host layer must keep printing it."""
 import os
-import shutil
-import subprocess
 import sys
 
 import pytest
@@ -19,10 +17,11 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 @pytest.fixture(scope="module")
 def host_abi(tmp_path_factory):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("no hipcc")
+    from mulut_amd import _native
     import host_abi as tool
-    exe = tool.build(str(tmp_path_factory.mktemp("host_abi")), os.path.join(ROOT, "mulut_amd", "csrc"))
+    if _native._hipcc() is None:
+        pytest.skip("no hipcc")
+    exe = tool.build(str(tmp_path_factory.mktemp("host_abi")), tool.CSRC)
     return tool, exe
 
 

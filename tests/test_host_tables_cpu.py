@@ -7,7 +7,6 @@ tests/golden/host_tables_trace.txt is what the program printed when the accessor
 the header's contract is asserted on the trace itself, so that a regenerated golden file cannot hide a broken promise."""
 import os
 import re
-import shutil
 import sys
 
 import pytest
@@ -19,10 +18,11 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 @pytest.fixture(scope="module")
 def trace(tmp_path_factory):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("no hipcc")
+    from mulut_amd import _native
     import host_abi as tool
-    exe = tool.build(str(tmp_path_factory.mktemp("host_tables")), os.path.join(ROOT, "mulut_amd", "csrc"), driver="abi_tables_host")
+    if _native._hipcc() is None:
+        pytest.skip("no hipcc")
+    exe = tool.build(str(tmp_path_factory.mktemp("host_tables")), tool.CSRC, driver="abi_tables_host")
     r = tool.run(exe)
     assert r.stderr == "", r.stderr[-4000:]       # no sanitizer report, the leak check at exit included
     assert r.returncode == 0

@@ -3,7 +3,6 @@
 those entry points as a program of its own under sanitizers; the command line."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -80,22 +79,9 @@ def test_host_half_as_a_program_under_sanitizers(tmp_path):
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import host_abi as tool
-    hipcc = _native._hipcc()
-    if hipcc is None:
+    if _native._hipcc() is None:
         pytest.skip("no hipcc")
-    warn = [f for f in _native.HIPCC_FLAGS if f.startswith("-W") or f.startswith("-std")]
-    host = [hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-ffp-contract=off"] + warn + [x for f in tool.SAN for x in ("-Xarch_host", f)]
-    out = str(tmp_path)
-    jobs = [subprocess.Popen(host + ["-c", "-o", os.path.join(out, s + ".o"), os.path.join(ROOT, "mulut_amd", "csrc", s + ".hip")])
-            for s in ("mulut_net", "mulut_net_train")]
-    for s in ("fake_hip", "net_gx_host"):
-        jobs.append(subprocess.Popen(host + ["-x", "hip", "-c", "-o", os.path.join(out, s + ".o"), os.path.join(tool.EMUL, s + ".cpp")]))
-    assert [p.wait() for p in jobs] == [0, 0, 0, 0]
-    clang = os.path.join(subprocess.check_output([os.path.join(os.path.dirname(hipcc), "hipconfig"), "-l"], text=True).strip(), "clang++")
-    exe = os.path.join(out, "net_gx_host")
-    subprocess.check_call([clang] + tool.SAN + ["-Wl,--unresolved-symbols=ignore-all", "-o", exe] +
-                          [os.path.join(out, s + ".o") for s in ("mulut_net", "mulut_net_train", "fake_hip", "net_gx_host")])
-    r = tool.run(exe)
+    r = tool.run(tool.build(str(tmp_path), tool.CSRC, "net_gx_host", ["mulut_net.hip", "mulut_net_train.hip"], flags=["-ffp-contract=off"]))
     print(r.stdout)
     assert r.stderr == "", r.stderr[-4000:]
     assert r.returncode == 0 and "UNEXPECTED" not in r.stdout and r.stdout.endswith("\n0 unexpected\n")

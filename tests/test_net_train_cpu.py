@@ -6,7 +6,6 @@ import copy
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -171,23 +170,10 @@ def test_host_half_as_a_program_under_sanitizers(tmp_path):
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import host_abi as tool
-    hipcc = _native._hipcc()
-    if hipcc is None:
+    if _native._hipcc() is None:
         pytest.skip("no hipcc")
     assert "mulut_net_train.hip" in _native.SOURCES and "mulut_net_dev.h" in _native.HEADERS
-    warn = [f for f in _native.HIPCC_FLAGS if f.startswith("-W") or f.startswith("-std")]
-    host = [hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g"] + warn + [x for f in tool.SAN for x in ("-Xarch_host", f)]
-    out = str(tmp_path)
-    jobs = [subprocess.Popen(host + ["-c", "-o", os.path.join(out, s + ".o"), os.path.join(ROOT, "mulut_amd", "csrc", s + ".hip")])
-            for s in ("mulut_net", "mulut_net_train")]
-    for s in ("fake_hip", "net_train_host"):
-        jobs.append(subprocess.Popen(host + ["-x", "hip", "-c", "-o", os.path.join(out, s + ".o"), os.path.join(tool.EMUL, s + ".cpp")]))
-    assert [p.wait() for p in jobs] == [0, 0, 0, 0]
-    clang = os.path.join(subprocess.check_output([os.path.join(os.path.dirname(hipcc), "hipconfig"), "-l"], text=True).strip(), "clang++")
-    exe = os.path.join(out, "net_train_host")
-    subprocess.check_call([clang] + tool.SAN + ["-Wl,--unresolved-symbols=ignore-all", "-o", exe] +
-                          [os.path.join(out, s + ".o") for s in ("mulut_net", "mulut_net_train", "fake_hip", "net_train_host")])
-    r = tool.run(exe)
+    r = tool.run(tool.build(str(tmp_path), tool.CSRC, "net_train_host", ["mulut_net.hip", "mulut_net_train.hip"]))
     print(r.stdout)
     assert r.stderr == "", r.stderr[-4000:]
     assert r.returncode == 0 and "UNEXPECTED" not in r.stdout and r.stdout.endswith("\n0 unexpected\n")

@@ -4,7 +4,6 @@ through the loaded library, and their host half as a stand-alone program under A
 tests/host_emul/fake_hip.cpp."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -106,23 +105,11 @@ def test_host_half_as_a_program_under_sanitizers(tmp_path):
     program: plan create / run / destroy with their allocations, copies and launch configurations, the refusals, the sweep."""
     from mulut_amd import _native
     import host_abi as tool
-    hipcc = _native._hipcc()
-    if hipcc is None:
+    if _native._hipcc() is None:
         pytest.skip("no hipcc")
     assert "mulut_resample.hip" in _native.SOURCES
     assert {"mulut_resample_coeffs", "mulut_resample_plan_create", "mulut_resample_plan_destroy", "mulut_resample_run"} <= set(_native.EXPORTS)
-    warn = [f for f in _native.HIPCC_FLAGS if f.startswith("-W") or f.startswith("-std")]
-    host = [hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g"] + warn + [x for f in tool.SAN for x in ("-Xarch_host", f)]
-    out = str(tmp_path)
-    jobs = [subprocess.Popen(host + ["-c", "-o", os.path.join(out, "mulut_resample.o"), os.path.join(ROOT, "mulut_amd", "csrc", "mulut_resample.hip")])]
-    for s in ("fake_hip", "resample_host"):
-        jobs.append(subprocess.Popen(host + ["-x", "hip", "-c", "-o", os.path.join(out, s + ".o"), os.path.join(tool.EMUL, s + ".cpp")]))
-    assert [p.wait() for p in jobs] == [0, 0, 0]
-    clang = os.path.join(subprocess.check_output([os.path.join(os.path.dirname(hipcc), "hipconfig"), "-l"], text=True).strip(), "clang++")
-    exe = os.path.join(out, "resample_host")
-    subprocess.check_call([clang] + tool.SAN + ["-Wl,--unresolved-symbols=ignore-all", "-o", exe] +
-                          [os.path.join(out, s + ".o") for s in ("mulut_resample", "fake_hip", "resample_host")])
-    r = tool.run(exe)
+    r = tool.run(tool.build(str(tmp_path), tool.CSRC, "resample_host", ["mulut_resample.hip"]))
     print(r.stdout)
     assert r.stderr == "", r.stderr[-4000:]
     assert r.returncode == 0 and "UNEXPECTED" not in r.stdout and r.stdout.endswith("\n0 unexpected\n")

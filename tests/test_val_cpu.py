@@ -2,7 +2,6 @@
 sanitizers (a stand-alone program), mulut_eval_finish against mulut_amd/metrics.py, the PNG writer behind the loop, the parser."""
 import ctypes
 import os
-import subprocess
 import sys
 import threading
 import time
@@ -24,24 +23,11 @@ def test_host_half_refusals_and_launch_configuration_under_sanitizers(tmp_path):
     1-item, a 2-item and a 328-item plan, no leak after create / destroy."""
     from mulut_amd import _native
     import host_abi as tool
-    hipcc = _native._hipcc()
-    if hipcc is None:
+    if _native._hipcc() is None:
         pytest.skip("no hipcc")
     new = {"mulut_eval_plan_create", "mulut_eval_plan_run", "mulut_eval_plan_destroy", "mulut_eval_finish", "mulut_ft_val_pack"}
     assert {"mulut_eval.hip", "mulut_ft_data.hip"} <= set(_native.SOURCES) and new <= set(_native.EXPORTS)
-    warn = [f for f in _native.HIPCC_FLAGS if f.startswith("-W") or f.startswith("-std")]
-    host = [hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g"] + warn + [x for f in tool.SAN for x in ("-Xarch_host", f)]
-    out = str(tmp_path)
-    jobs = [subprocess.Popen(host + ["-c", "-o", os.path.join(out, s + ".o"), os.path.join(ROOT, "mulut_amd", "csrc", s + ".hip")])
-            for s in ("mulut_eval", "mulut_ft_data")]
-    for s in ("fake_hip", "eval_list_host"):
-        jobs.append(subprocess.Popen(host + ["-x", "hip", "-c", "-o", os.path.join(out, s + ".o"), os.path.join(tool.EMUL, s + ".cpp")]))
-    assert [p.wait() for p in jobs] == [0, 0, 0, 0]
-    clang = os.path.join(subprocess.check_output([os.path.join(os.path.dirname(hipcc), "hipconfig"), "-l"], text=True).strip(), "clang++")
-    exe = os.path.join(out, "eval_list_host")
-    subprocess.check_call([clang] + tool.SAN + ["-Wl,--unresolved-symbols=ignore-all", "-o", exe] +
-                          [os.path.join(out, s + ".o") for s in ("mulut_eval", "mulut_ft_data", "fake_hip", "eval_list_host")])
-    r = tool.run(exe)
+    r = tool.run(tool.build(str(tmp_path), tool.CSRC, "eval_list_host", ["mulut_eval.hip", "mulut_ft_data.hip"]))
     print(r.stdout)
     assert r.stderr == "", r.stderr[-4000:]
     assert r.returncode == 0 and "UNEXPECTED" not in r.stdout and r.stdout.endswith("\n0 unexpected\n")

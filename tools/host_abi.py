@@ -22,18 +22,21 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 EMUL = os.path.join(ROOT, "tests", "host_emul")
+CSRC = os.path.join(ROOT, "mulut_amd", "csrc")
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
 
 
-def build(outdir, csrc, driver="abi_host"):
+def build(outdir, csrc, driver="abi_host", sources=None, flags=()):
+    """`sources`: the files of _native.SOURCES to compile (None: all of them); `flags`: more compile flags for every file of the program."""
     from mulut_amd import _native
     hipcc = _native._hipcc()
+    sources = _native.SOURCES if sources is None else list(sources)
     outdir = os.path.abspath(outdir)
     os.makedirs(outdir, exist_ok=True)
     warn = [f for f in _native.HIPCC_FLAGS if f.startswith("-W") or f.startswith("-std")]
-    host = [hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g"] + warn + ["-Xarch_host " + f for f in SAN]
+    host = [hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g"] + list(flags) + warn + ["-Xarch_host " + f for f in SAN]
     host = [x for f in host for x in f.split(" ")]
-    jobs = [(s, subprocess.Popen(host + ["-c", "-o", os.path.join(outdir, s[:-4] + ".o"), s], cwd=csrc)) for s in _native.SOURCES]
+    jobs = [(s, subprocess.Popen(host + ["-c", "-o", os.path.join(outdir, s[:-4] + ".o"), s], cwd=csrc)) for s in sources]
     # (the two files of the harness always compile against THIS tree's include/mulut.h, whatever --csrc names: comparing two trees
     # this way presumes that the ABI header did not change between them)
     for s in ("fake_hip.cpp", driver + ".cpp"):
@@ -58,8 +61,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("cmd", choices=["build", "trace"])
     ap.add_argument("outdir")
-    ap.add_argument("--csrc", default=os.path.join(ROOT, "mulut_amd", "csrc"))
-    ap.add_argument("--driver", default="abi_host", choices=["abi_host", "abi_tables_host"])
+    ap.add_argument("--csrc", default=CSRC)
+    ap.add_argument("--driver", default="abi_host", help="a driver of tests/host_emul, without its .cpp")
     args = ap.parse_args()
     exe = build(args.outdir, args.csrc, args.driver)
     if args.cmd == "trace":
