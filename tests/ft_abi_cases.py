@@ -83,14 +83,15 @@ LARGEST = 16 * 1 * 48 * 48
 
 @functools.lru_cache(maxsize=None)
 def _built(name):
-    case = next(c for c in CASES + EXTRA if c.name == name)
-    case.build()
+    case = copy.copy(next(c for c in CASES + EXTRA if c.name == name)).build()
     ref = (fw.reference if is_wide(case) else fx.reference)(case)
     return case, ref
 
 
 def built(case):
-    """(the case with tables, x and gout in place, its integer reference): computed once per process and shared -- read only"""
+    """(a copy of the case with tables, x and gout in place, its integer reference): computed once per process and shared -- read only.
+    A copy, because the objects of CASES are those of ft_exact_cases.CASES / ft_wide_cases.CASES, which the tests that own those lists
+    build and release (`case.tables = case.x = case.gout = None`) per test: in one process with them the cache must not hold theirs."""
     return _built(case.name)
 
 

@@ -141,12 +141,13 @@ int main() {
     Weights m8, m64;
     make(m8, 8, 2, false);
     make(m64, 64, 4, false);
-    mulut_net_unit *t8 = nullptr, *t24 = nullptr, *t64 = nullptr, *plain64 = nullptr;
+    mulut_net_unit *t8 = nullptr, *t24 = nullptr, *t24u2 = nullptr, *t64 = nullptr, *plain64 = nullptr;
     expect("create_train nf 8 u 2", mulut_net_unit_create_train(0, 8, 2, &t8), MULUT_OK, "malloc 131072 | memset 131072");
     expect("create_train nf 24 u 4", mulut_net_unit_create_train(0, 24, 4, &t24), MULUT_OK, "malloc 131072 | memset 131072");
+    expect("create_train nf 24 u 2", mulut_net_unit_create_train(0, 24, 2, &t24u2), MULUT_OK, "malloc 131072 | memset 131072");
     expect("create_train nf 64 u 4", mulut_net_unit_create_train(0, 64, 4, &t64), MULUT_OK, "malloc 409600 | memset 409600");
     expect("create nf 64 u 4", mulut_net_unit_create(0, 64, 4, m64.wp, m64.bp, &plain64), MULUT_OK, "malloc 212992 | memcpy 212992");
-    g_wrong += !t8 || !t24 || !t64 || !plain64;
+    g_wrong += !t8 || !t24 || !t24u2 || !t64 || !plain64;
     const mulut_net_unit *list[9] = {t64, t64, t64, t64, t64, t64, t64, t64, t64};
     // ---- mulut_net_backward_exact_ws_bytes: the old figure plus 16 bytes per site of the whole pass, rounded up to 128 sites
     const long long p64 = 16LL * 46672 * 4, row64 = 660LL * 4;
@@ -201,6 +202,9 @@ int main() {
                MULUT_EINVAL, "");
         const mulut_net_unit *two_nf[2] = {t8, t24};
         expect("exact units of two nf", mulut_net_stage_backward_exact(two_nf, "sd", kX, kX, 1, 3, 8, 8, kWs, big, kOut, gw, gb, nullptr), MULUT_ESHAPE, "");
+        const mulut_net_unit *one_width[2] = {t8, t24u2};      // (those differ in u as well; these only in nf)
+        expect("exact units of two nf, one u and one padded width", mulut_net_stage_backward_exact(one_width, "sy", kX, kX, 2, 3, 5, 7, kWs, big, kOut, gw, gb, nullptr),
+               MULUT_ESHAPE, "");
         float *hole[12];
         for (int k = 0; k < 12; ++k) hole[k] = gw[k];
         hole[7] = nullptr;
@@ -265,6 +269,7 @@ int main() {
     }
     expect("destroy nf 8", mulut_net_unit_destroy(t8), MULUT_OK, "free 131072");
     expect("destroy nf 24", mulut_net_unit_destroy(t24), MULUT_OK, "free 131072");
+    expect("destroy nf 24 u 2", mulut_net_unit_destroy(t24u2), MULUT_OK, "free 131072");
     expect("destroy nf 64", mulut_net_unit_destroy(t64), MULUT_OK, "free 409600");
     expect("destroy plain", mulut_net_unit_destroy(plain64), MULUT_OK, "free 212992");
     printf("%d unexpected\n", g_wrong);

@@ -87,7 +87,7 @@ int main() {
     Weights m8, m64;
     make(m8, 8, 2, false);
     make(m64, 64, 4, false);
-    mulut_net_unit *unit = (mulut_net_unit *)0x1, *t8 = nullptr, *t64 = nullptr, *t64b = nullptr, *t24 = nullptr, *plain64 = nullptr;
+    mulut_net_unit *unit = (mulut_net_unit *)0x1, *t8 = nullptr, *t64 = nullptr, *t64b = nullptr, *t24 = nullptr, *t24u2 = nullptr, *plain64 = nullptr;
     // ---- mulut_net_unit_create_train
     expect("create_train null out", mulut_net_unit_create_train(0, 8, 2, nullptr), MULUT_EINVAL, "");
     expect("create_train nf 0", mulut_net_unit_create_train(0, 0, 2, &unit), MULUT_EUNSUPPORTED, "");
@@ -101,8 +101,9 @@ int main() {
     expect("create_train nf 64 u 4", mulut_net_unit_create_train(0, 64, 4, &t64), MULUT_OK, "malloc 409600 | memset 409600");
     expect("create_train nf 64 u 4 again", mulut_net_unit_create_train(0, 64, 4, &t64b), MULUT_OK, "malloc 409600 | memset 409600");
     expect("create_train nf 24 u 4", mulut_net_unit_create_train(0, 24, 4, &t24), MULUT_OK, "malloc 131072 | memset 131072");
+    expect("create_train nf 24 u 2", mulut_net_unit_create_train(0, 24, 2, &t24u2), MULUT_OK, "malloc 131072 | memset 131072");
     expect("create nf 64 u 4", mulut_net_unit_create(0, 64, 4, m64.wp, m64.bp, &plain64), MULUT_OK, "malloc 212992 | memcpy 212992");
-    g_wrong += !t8 || !t64 || !t64b || !t24 || !plain64;
+    g_wrong += !t8 || !t64 || !t64b || !t24 || !t24u2 || !plain64;
     // ---- mulut_net_unit_load_dev (the pointers are device pointers: nothing follows them here)
     expect("load_dev null unit", mulut_net_unit_load_dev(nullptr, m8.wp, m8.bp, nullptr), MULUT_EINVAL, "");
     expect("load_dev null w", mulut_net_unit_load_dev(t8, nullptr, m8.bp, nullptr), MULUT_EINVAL, "");
@@ -149,6 +150,11 @@ int main() {
         expect("sum null unit in the list", mulut_net_stage_sum(hole, "sd", kX, 1, 3, 8, 8, kOut, nullptr), MULUT_EINVAL, "");
         const mulut_net_unit *mixed_w[2] = {t64, t8};
         expect("sum units of two widths", mulut_net_stage_sum(mixed_w, "sd", kX, 1, 3, 8, 8, kOut, nullptr), MULUT_ESHAPE, "");
+        const mulut_net_unit *mixed_u[2] = {t24u2, t24};
+        expect("sum units of two u", mulut_net_stage_sum(mixed_u, "sd", kX, 1, 3, 8, 8, kOut, nullptr), MULUT_ESHAPE, "");
+        const mulut_net_unit *one_width[2] = {t8, t24u2};      // nf 8 and nf 24: one u, one padded width -- the forward takes them
+        expect("sum units of two nf under one padded width", mulut_net_stage_sum(one_width, "sy", kX, 2, 3, 5, 7, kOut, nullptr), MULUT_OK,
+               "launch net_stage_sum_kernel<1, 2> grid 2,1,1 block 256,1,1 lds 0");
     }
     for (int v = 0; v >= -1; --v) {
         expect("sum N < 1", mulut_net_stage_sum(list, "sd", kX, v, 3, 8, 8, kOut, nullptr), MULUT_EINVAL, "");
@@ -193,6 +199,9 @@ int main() {
                MULUT_EINVAL, "");
         const mulut_net_unit *two_nf[2] = {t8, t24};      // one feature tile each, yet different rows in the workspace
         expect("backward units of two nf", mulut_net_stage_backward(two_nf, "sd", kX, kX, 1, 3, 8, 8, kWs, big, kOut, gw, gb, nullptr), MULUT_ESHAPE, "");
+        const mulut_net_unit *one_width[2] = {t8, t24u2};      // (those differ in u as well; these only in nf)
+        expect("backward units of two nf, one u and one padded width", mulut_net_stage_backward(one_width, "sy", kX, kX, 2, 3, 5, 7, kWs, big, kOut, gw, gb, nullptr),
+               MULUT_ESHAPE, "");
         float *hole[12];
         for (int k = 0; k < 12; ++k) hole[k] = gw[k];
         hole[7] = nullptr;
@@ -224,6 +233,7 @@ int main() {
     expect("destroy nf 64", mulut_net_unit_destroy(t64), MULUT_OK, "free 409600");
     expect("destroy nf 64", mulut_net_unit_destroy(t64b), MULUT_OK, "free 409600");
     expect("destroy nf 24", mulut_net_unit_destroy(t24), MULUT_OK, "free 131072");
+    expect("destroy nf 24 u 2", mulut_net_unit_destroy(t24u2), MULUT_OK, "free 131072");
     expect("destroy plain", mulut_net_unit_destroy(plain64), MULUT_OK, "free 212992");
     printf("%d unexpected\n", g_wrong);
     return g_wrong;

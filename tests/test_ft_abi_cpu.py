@@ -234,3 +234,26 @@ def test_stage_function_refuses_a_host_tensor_before_the_library_is_loaded(monke
     w = torch.zeros((83521, 1), dtype=torch.float32)
     with pytest.raises(TypeError):
         _StageFn.apply(torch.zeros((1, 1, 4, 4), dtype=torch.float32), "s", False, 1, 4, w)
+
+
+# ------------------------------------------------------------------------------------------------------------ the shared case objects
+def test_built_cases_outlive_the_tests_that_release_the_shared_objects():
+    """The objects of fa.CASES are those of ft_exact_cases.CASES / ft_wide_cases.CASES (_pick returns them).  The tests that own those
+    lists (test_ft_exact_cpu.py, test_ft_wide_cpu.py, test_gpu_ft_exact.py, test_gpu_ft_wide.py) build a case and release its arrays
+    per test, and tests/test_gpu_abi_streams.py ran the same path on them.  In one process with them, before or after, built() must
+    still hand out a case with its arrays: it holds a copy, and the stream test builds on a copy of its own."""
+    import test_gpu_abi_streams as streams      # (importing it needs no GPU: every collection does)
+    shared = [c for c in streams.FT_CASES if any(c is d for d in fa.CASES)]
+    assert len(shared) >= 6 and {c.interval for c in shared} == {4, 5, 6}
+    for k, case in enumerate(shared):
+        if k % 2:
+            fa.built(case)
+        before = dict(vars(case))
+        ref, tables, x, gout = streams._reference_and_inputs(case, lambda a: a)
+        assert vars(case) == before      # the stream test's path leaves the object it was given alone
+        assert len(tables) == case.M and x.shape == case.shape and gout.dtype == np.float32 and ref.out is not None
+        case.build()                     # what an owner's test does with it
+        case.tables = case.x = case.gout = None
+        got, _ = fa.built(case)
+        assert got is not case and got.name == case.name and got.tables is not None and got.x is not None and got.gout is not None
+        assert np.array_equal(got.x, x) and np.array_equal(got.gout, gout) and all(np.array_equal(a, b) for a, b in zip(got.tables, tables))

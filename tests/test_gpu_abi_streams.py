@@ -4,6 +4,7 @@ to the host", set-up calls wait for work in flight, "contexts may be created and
 torch's side streams are non-blocking: the legacy null stream does not wait for them, nor they for it.  So an entry point that
 launched on another stream than the one it was given would read input that a torch kernel queued on that stream has not written
 yet -- every input below is produced that way (Late), behind a delay, while the default stream runs unrelated pipeline calls."""
+import copy
 import ctypes
 import threading
 
@@ -153,18 +154,23 @@ FT_CASES = [c for c in fx.CASES if c.modes == "sdy" and c.content == "noise" and
 assert {(c.interval, c.u, c.last) for c in FT_CASES} >= {(iv, u, last) for iv in (4, 5, 6) for u, last in ((4, 1), (1, 0))}
 
 
+def _reference_and_inputs(case, late):
+    """(reference, tables, x, gout as `late` makes them) of a case.  The case objects are those of ft_exact_cases.CASES, which
+    ft_abi_cases.built() caches, built, for the whole process: the arrays are built on a copy, and only the copy's are released."""
+    own = copy.copy(case).build()
+    try:
+        return fx.reference(own), [late(t.astype(np.float32)) for t in own.tables], late(own.x), late(own.gout)
+    finally:
+        own.tables = own.x = own.gout = None
+
+
 @pytest.mark.parametrize("case", FT_CASES, ids=lambda c: c.name)
 def test_fine_tune_stage_entry_points_on_a_side_stream(busy, side, case):
     """mulut_ft_stage_forward(_mask) / backward(_mask) at interval 4, mulut_ft_interval_stage_forward / backward at 5 and 6, on the
     integer cases of tests/ft_exact_cases.py: exact, so np.array_equal applies."""
     from mulut_amd import _native
     lib = _native.load()
-    case.build()
-    try:
-        ref = fx.reference(case)
-        lw, lx, lg = [Late(t.astype(np.float32)) for t in case.tables], Late(case.x), Late(case.gout)
-    finally:
-        case.tables = case.x = case.gout = None
+    ref, lw, lx, lg = _reference_and_inputs(case, Late)
     torch.cuda.synchronize()
     busy()
     bad = []
