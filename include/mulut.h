@@ -428,6 +428,41 @@ int mulut_net_table(const mulut_net_unit *unit, int interval, int8_t *rows_dev, 
 int mulut_net_pass(const mulut_net_unit *unit, char mode, int r, const uint8_t *in, int N, int C, int H, int W, int8_t *out, void *stream);
 int mulut_net_stage(const mulut_net_unit *const units[], const char *modes, int is_last, const uint8_t *in, uint8_t *out, int N, int C,
                     int H, int W, void *stream);
+/* The cascade for a LIST of images of different sizes, HWC bytes to HWC bytes, in `stages` stream-ordered launches
+ * (mulut_net_list.hip): what the validation loop of sr/1_train_model.py:87-101 does per image -- the image to planar (:87-91),
+ * mulut_predict in the 'valid' phase (:93), back to HWC, round and clip (:95-101) -- without a launch, an allocation or a layout pass
+ * per image.  The inputs lie in one device pool of bytes, the results go to another; an item names one image: its input uint8
+ * [h][w][ch] at byte in_off of in_pool, its result uint8 [h * scale][w * scale][ch] at byte out_off of out_pool (no alignment asked
+ * of either offset), and it states the size of each pool, so the plan can vouch for every address the kernels will form.  Item i's
+ * result is, byte for byte, what mulut_net_stage called stage after stage on that image alone (planar [1][ch][h][w]) gives, permuted
+ * to HWC.
+ * mulut_net_plan_create (sr/1_train_model.py:87-101): `items` is a HOST array of n entries; the model has `stages` stages, every one
+ *   before the last of upscale 1 and the last of upscale `scale`.  Checked on the host, in this order, each class over the whole list
+ *   before the next, and before the device is touched: a NULL `plan` (then nothing is written), a NULL `items`, n, ch, stages or
+ *   scale < 1 MULUT_EINVAL; an item with h or w < 1 MULUT_EINVAL; an item with a negative offset, or whose input or result is not
+ *   wholly inside the pool size it states MULUT_EINVAL; two items whose result ranges overlap MULUT_EINVAL (inputs may be shared); an
+ *   item of 2^31 result bytes or more, 2^31 workgroups or more in one launch (ceil(ch * h * w / 128) per item), or a workspace of
+ *   2^31 bytes or more MULUT_EUNSUPPORTED.  Then one allocation and one blocking copy (not capturable): the item table (32 bytes an
+ *   item), the map from a workgroup to (item, first site of that item) (8 bytes a workgroup), and the plan's own planar
+ *   intermediate planes, which the stages before the last write and the stages after the first read: sum of ch * h * w bytes a
+ *   set, no set for one stage, one for two, two for more.  *plan is NULL after any failure.
+ * mulut_net_plan_run (sr/1_train_model.py:93-101): exactly `stages` kernel launches on `stream` and nothing else -- it allocates
+ *   nothing, copies nothing and waits for nothing, so it can be captured into a hipGraph, and a replay reads the input pool and the
+ *   units' weights as they are in memory then.  `units` holds stages x strlen(modes) handles, stage-major (stage s, mode m at
+ *   [s * M + m]); in_pool and out_pool are device pointers to at least the bytes the items stated.  Nothing of out_pool outside
+ *   the items' result ranges is written.  Refused before any launch, stage by stage: a NULL plan, units, modes or pool MULUT_EINVAL;
+ *   per stage the refusals of mulut_net_stage's unit list (an empty mode list, a NULL handle, an unknown pattern letter
+ *   MULUT_EINVAL; more than MULUT_MAX_MODES modes MULUT_EUNSUPPORTED; units that differ in upscale, padded width or device
+ *   MULUT_ESHAPE), then a stage before the last whose upscale is not 1, a last stage whose upscale is not `scale`, or units on
+ *   another device than the plan's MULUT_ESHAPE.  The planes belong to the plan: runs of ONE plan must be ordered one behind the
+ *   other (one stream, or events); different plans are independent.
+ * mulut_net_plan_destroy: frees the allocation (hipFree waits for work in flight on the device) and the plan. */
+typedef struct { long long in_off, out_off; int h, w; long long in_pool_bytes, out_pool_bytes; } mulut_net_item;   /* 40 bytes */
+typedef struct mulut_net_plan mulut_net_plan;
+int mulut_net_plan_create(int device, const mulut_net_item *items, int n, int ch, int stages, int scale, mulut_net_plan **plan);
+int mulut_net_plan_run(const mulut_net_plan *plan, const mulut_net_unit *const units[], const char *modes, const void *in_pool,
+                       void *out_pool, void *stream);
+int mulut_net_plan_destroy(mulut_net_plan *plan);
 
 /* ---- Training the network on the fused site body (mulut_net_train.hip): sr/1_train_model.py:26-45 in the 'train' phase and its
  * gradient.  Everything here is float32 on the device and stream-ordered; nothing allocates but mulut_net_unit_create_train.

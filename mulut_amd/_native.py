@@ -8,8 +8,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 _LIBDIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(_LIBDIR, "libmulut_hip.so")
-SOURCES = ["mulut_kernels.hip", "mulut_k1.hip", "mulut_detail.hip", "mulut_interval.hip", "mulut_capi.hip", "mulut_ft.hip", "mulut_ft_interval.hip", "mulut_ft_exact.hip", "mulut_ft_data.hip", "mulut_eval.hip", "mulut_resample.hip", "mulut_net.hip", "mulut_net_train.hip"]
-HEADERS = ["mulut_core.h", "mulut_interval.h", "mulut_ft.h", "mulut_ft_interval.h", "mulut_ft_exact.h", "mulut_kernels.h", "mulut_dev.h", "mulut_net.h", "mulut_net_dev.h", "mulut_tube2_asm.inc", os.path.join("..", "..", "include", "mulut.h")]
+SOURCES = ["mulut_kernels.hip", "mulut_k1.hip", "mulut_detail.hip", "mulut_interval.hip", "mulut_capi.hip", "mulut_ft.hip", "mulut_ft_interval.hip", "mulut_ft_exact.hip", "mulut_ft_data.hip", "mulut_eval.hip", "mulut_resample.hip", "mulut_net.hip", "mulut_net_list.hip", "mulut_net_train.hip"]
+HEADERS = ["mulut_core.h", "mulut_interval.h", "mulut_ft.h", "mulut_ft_interval.h", "mulut_ft_exact.h", "mulut_kernels.h", "mulut_dev.h", "mulut_net.h", "mulut_net_dev.h", "mulut_net_list.h", "mulut_tube2_asm.inc", os.path.join("..", "..", "include", "mulut.h")]
 # -Wno-inline-asm: stage_tube2_kernel names registers ABOVE the register allocator's budget in its asm clobber lists on purpose
 # (tools/gen_tube2_asm.py); -Wno-pass-failed: its occupancy attribute is that budget, not an occupancy the kernel reaches
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-inline-asm", "-Wno-pass-failed"]
@@ -76,6 +76,9 @@ def _prototypes():
         "mulut_net_table": (i, [p, i, p, p]),
         "mulut_net_pass": (i, [p, c, i, p, i, i, i, i, p, p]),
         "mulut_net_stage": (i, [pp, s, i, p, p, i, i, i, i, p]),
+        "mulut_net_plan_create": (i, [i, p, i, i, i, i, pp]),
+        "mulut_net_plan_run": (i, [p, pp, s, p, p, p]),
+        "mulut_net_plan_destroy": (i, [p]),
         # training the network
         "mulut_net_unit_create_train": (i, [i, i, i, pp]),
         "mulut_net_unit_load_dev": (i, [p, pp, pp, p]),

@@ -206,6 +206,8 @@ __device__ __forceinline__ int net_rhe_clip(int n, int D) {
 // sit in a wave-private LDS tile, [output][site]: in a pass a lane adds the outputs it computed to where they land un-rotated (which
 // may be the other lane half's slot), and LDS operations of a wave execute in order, so no synchronisation beyond program order is
 // needed.  O = unsigned char: the stage's epilogue in integers; O = float: the sums themselves (the 'train' phase's pred).
+// (net_list_kernel of mulut_net_list.hip holds a COPY of the loop over modes and rotations below, its taps apart: shared through one
+// function it changed this body's instructions.  A change to the accumulation or the sub-pixel rotation here goes there too.)
 template <int MT, int U, class T, class O>
 __device__ __forceinline__ void net_stage_body(const NetStageArgs<T, O> &a, float4 *lds, int (*sums)[16][kNetTileSites]) {
     NetStream s;

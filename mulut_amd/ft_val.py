@@ -153,11 +153,15 @@ class DeviceValSet:
       lr_f32    float32 the same images as the module takes them, planar [1][3][h][w], the HOST's astype(float32) / 255.0 uploaded
                         once (the device's division is a product with a rounded reciprocal: not the same float for every byte)
       plans     one mulut_eval_plan per dataset over (gt_pool, out_pool); sums: device float64 [images][2], read back once per point
-    `max_bytes`: a set that needs more raises ValidationSetTooLarge before anything is allocated on the device."""
+    `max_bytes`: a set that needs more raises ValidationSetTooLarge before anything is allocated on the device.
+    `lr_float` False leaves lr_f32 out (None): the three byte pools are all the network's validation reads (net_val).
+    `png_name`: (dataset, file name) -> the name `save` writes the result under; val_png_name if None.
+    `eval_plans` False makes no mulut_eval_plan: a set whose owner scores otherwise (net_val.NetValSet); `score` is then not to be called."""
 
-    def __init__(self, opt, max_bytes=None, workers=4, encode=None):
+    def __init__(self, opt, max_bytes=None, workers=4, encode=None, lr_float=True, png_name=None, eval_plans=True):
         self.lib = _native.load()
         self.scale = int(opt.scale)
+        self.png_name = png_name or val_png_name
         self.sets, images, gt_bytes, lr_bytes = [], [], 0, 0
         for ds, pairs in _by_dataset(opt):
             first, files = len(images), []
@@ -169,24 +173,25 @@ class DeviceValSet:
                 gt_bytes, lr_bytes = gt_bytes + lb.size, lr_bytes + im.size
             self.sets.append({"name": ds, "files": files, "first": first, "n": len(files), "out_dir": os.path.join(opt.valoutDir, ds)})
         self.gt_bytes, self.lr_bytes = gt_bytes, lr_bytes
-        self.nbytes = 2 * gt_bytes + 5 * lr_bytes          # gt + out, LR bytes + LR floats
+        self.nbytes = self.pool_bytes(gt_bytes, lr_bytes, lr_float)
         if max_bytes is not None and self.nbytes > max_bytes:
             raise ValidationSetTooLarge(self.nbytes, max_bytes)
         dev = self.device = torch.empty(0).cuda().device
         self.gt_pool = torch.empty(gt_bytes, dtype=torch.uint8, device=dev)
         self.out_pool = torch.zeros(gt_bytes, dtype=torch.uint8, device=dev)
         self.lr_pool = torch.empty(lr_bytes, dtype=torch.uint8, device=dev)
-        self.lr_f32 = torch.empty(lr_bytes, dtype=torch.float32, device=dev)
+        self.lr_f32 = torch.empty(lr_bytes, dtype=torch.float32, device=dev) if lr_float else None
         self.shapes = []                                   # a ValShape per image
         for im, lb, g, l in images:                        # image by image
             self.gt_pool[g:g + lb.size].copy_(torch.from_numpy(lb.reshape(-1)))
             self.lr_pool[l:l + im.size].copy_(torch.from_numpy(im.reshape(-1)))
-            self.lr_f32[l:l + im.size].copy_(torch.from_numpy((np.ascontiguousarray(im.transpose(2, 0, 1)).astype(np.float32) / 255.0).reshape(-1)))
+            if lr_float:
+                self.lr_f32[l:l + im.size].copy_(torch.from_numpy((np.ascontiguousarray(im.transpose(2, 0, 1)).astype(np.float32) / 255.0).reshape(-1)))
             self.shapes.append(ValShape(g, lb.shape[0], lb.shape[1], l, im.shape[0], im.shape[1]))
         del images
         self.sums = torch.zeros((len(self.shapes), 2), dtype=torch.float64, device=dev)
         self.sums_host = torch.zeros((len(self.shapes), 2), dtype=torch.float64).pin_memory()
-        for s in self.sets:
+        for s in (self.sets if eval_plans else []):
             items = np.zeros((s["n"], 5), np.int64)        # mulut_eval_item: gt_off, out_off, (H, W) as two int32, the two pool sizes
             for k, sh in enumerate(self.shapes[s["first"]:s["first"] + s["n"]]):
                 items[k, 0], items[k, 1], items[k, 3], items[k, 4] = sh.gt_off, sh.gt_off, gt_bytes, gt_bytes
@@ -200,6 +205,11 @@ class DeviceValSet:
         torch.cuda.synchronize(dev)                        # the set is in place whatever stream a validation runs on
         self.writer = ValWriter(workers, encode)
         self.copy_stream, self.copied, self.out_host = None, None, None
+
+    @staticmethod
+    def pool_bytes(gt_bytes, lr_bytes, lr_float=True):
+        """Device bytes of the pools: ground truths and results, the LR bytes, and with `lr_float` the LR floats."""
+        return 2 * gt_bytes + (5 if lr_float else 1) * lr_bytes
 
     def lr_tensor(self, n):
         _, _, _, l, h, w = self.shapes[n]
@@ -260,7 +270,7 @@ class DeviceValSet:
             os.makedirs(s["out_dir"], exist_ok=True)
             for k, fn in enumerate(s["files"]):
                 sh = self.shapes[s["first"] + k]
-                jobs.append((os.path.join(s["out_dir"], val_png_name(s["name"], fn)),
+                jobs.append((os.path.join(s["out_dir"], self.png_name(s["name"], fn)),
                              host[sh.gt_off:sh.gt_off + 3 * sh.H * sh.W].reshape(sh.H, sh.W, 3)))
         self.writer.submit(jobs, ready=copied.synchronize)
 

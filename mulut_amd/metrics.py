@@ -28,6 +28,8 @@ def rgb2ycbcr(img, max_val=255):
     # three scaled columns added up, NOT `flat @ _T.T`: the CLI scores images on several threads at once, and concurrent
     # dgemm calls of the bundled OpenBLAS (0.3.29, threaded) on these tall 3-column operands were seen to return wrong rows
     # now and then (tools/stress_cli.py: 19 of 300 Set5 runs printed a PSNR off by 0.03-0.6 dB with bit-exact PNGs)
+    # (net_val.luma32 restates column 0 of this sum -- the same products added in the same order -- so that the resident validation
+    # prints net_valid_steps' digits: change the two together; tests/test_net_list_cpu.py holds them to equal bits)
     out = flat[:, 0:1] * _T[:, 0] + flat[:, 1:2] * _T[:, 1] + flat[:, 2:3] * _T[:, 2] + off
     return out.reshape(img.shape)
 

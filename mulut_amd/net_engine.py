@@ -154,6 +154,61 @@ def _no_gpu():
         raise MuLUTError("no GPU visible: mulut_amd has no CPU path")
 
 
+class NetPlan:
+    """Owns a `mulut_net_plan` of a NetEngine: a list of images of different sizes through the whole cascade, HWC bytes in one device
+    pool to HWC bytes in another, in `stages` launches (csrc/mulut_net_list.hip).  The units stay the engine's: `load_weights` there
+    is seen by the next `run`, and the engine must outlive the plan."""
+
+    def __init__(self, engine, items, ch=3):
+        rows = [tuple(int(v) for v in it) for it in items]
+        if any(len(r) != 6 for r in rows):
+            raise ValueError("an item is (in_off, out_off, h, w, in_pool_bytes, out_pool_bytes)")
+        self._engine, self._lib, self._h = engine, engine._lib, None
+        self.n, self.ch = len(rows), int(ch)
+        self.in_bytes, self.out_bytes = max((r[4] for r in rows), default=0), max((r[5] for r in rows), default=0)
+        table = np.zeros((max(self.n, 1), 5), np.int64)      # mulut_net_item: in_off, out_off, (h, w) as two int32, the two pool sizes
+        for k, (in_off, out_off, h, w, in_pool, out_pool) in enumerate(rows):
+            if not (-2 ** 31 <= h < 2 ** 31 and -2 ** 31 <= w < 2 ** 31):
+                raise ValueError("item %d: h and w are 32-bit" % k)
+            table[k, 0], table[k, 1], table[k, 3], table[k, 4] = in_off, out_off, in_pool, out_pool
+            table[k, 2:3].view(np.int32)[:] = (h, w)
+        plan = ctypes.c_void_p()
+        engine._check(self._lib.mulut_net_plan_create(engine.device.index, table.ctypes.data, self.n, self.ch, engine.stages, engine.scale,
+                                                      ctypes.byref(plan)))
+        self._h = plan
+        un = engine._units
+        self._handles = (ctypes.c_void_p * (engine.stages * len(engine.modes)))(
+            *[un.handle(s, m).value for s in range(1, engine.stages + 1) for m in engine.modes])
+
+    def _pool(self, t, nbytes, name):
+        _dev(t, torch.uint8, name)
+        if t.device != self._engine.device:
+            raise ValueError("%s lives on %s, engine on %s" % (name, t.device, self._engine.device))
+        if t.numel() < nbytes:
+            raise ValueError("%s holds %d bytes, the items stated %d" % (name, t.numel(), nbytes))
+        return t.data_ptr()
+
+    def run(self, in_pool, out_pool):
+        """`stages` launches on torch's current stream, nothing else: capturable.  Runs of one plan are to be ordered one behind the other."""
+        if self._h is None:
+            raise MuLUTError("the plan is closed")
+        e = self._engine
+        e._check(self._lib.mulut_net_plan_run(self._h, self._handles, e.modes.encode(), self._pool(in_pool, self.in_bytes, "in_pool"),
+                                              self._pool(out_pool, self.out_bytes, "out_pool"), e._stream()))
+        return out_pool
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            self._lib.mulut_net_plan_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class NetEngine:
     """Owns a `mulut_net_unit` per module of `model_G` (an `SRNets`, also one rebuilt by `network.load_checkpoint`).  The weights are
     read once, here: a later change of the module's parameters is not seen until `load_weights` packs them anew, on the device.  Every method takes and returns device tensors and
@@ -229,6 +284,12 @@ class NetEngine:
         self._check(self._lib.mulut_net_stage(handles, self.modes.encode(), int(stage == self.stages), x.data_ptr(), out.data_ptr(),
                                               N, C, H, W, self._stream()))
         return out
+
+    def plan(self, items, ch=3):
+        """A NetPlan over `items`, each (in_off, out_off, h, w, in_pool_bytes, out_pool_bytes): image k is uint8 [h][w][ch] at byte
+        in_off of the input pool, and its result -- `predict` of that image alone, permuted to HWC -- goes to byte out_off of the
+        output pool as uint8 [h * scale][w * scale][ch].  `run(in_pool, out_pool)` is `stages` launches on the current stream."""
+        return NetPlan(self, items, ch)
 
     def predict(self, x_u8):
         """The whole cascade, bytes to bytes: np.round(np.clip(mulut_predict(model_G, x / 255, 'valid', opt), 0, 255)) of

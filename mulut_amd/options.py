@@ -89,11 +89,24 @@ class TestOptions:
         return opt
 
 
+def add_resident_validation(parser):
+    """--valResident, --valSave, --valWorkers: the flags, choices and defaults of the fine-tune parser (finetune_lut.build_parser); the
+    help says what they do for the network's validation (net_val.NetValSet), which scores on the host where the fine-tune driver's scores on the device."""
+    parser.add_argument('--valResident', default=False, action='store_true',
+                        help='validate from a device-resident set (NetValSet): decoded and uploaded once per run, one list launch of '
+                             'the network per stage and dataset, one read-back of the results per point, scored on the host as '
+                             'without the flag, PNGs written behind the loop -- the same log lines, numbers and files as without it')
+    parser.add_argument('--valSave', choices=['every', 'last', 'never'], default='every',
+                        help='with --valResident: write the PNGs of every validation point, of the final one only, or none')
+    parser.add_argument('--valWorkers', type=int, default=4,
+                        help='with --valResident: threads that score the results of a point, and as many that encode the PNGs behind the loop')
+
+
 class TrainOptions:
     """The reference's training command line (common/option.py:13-31,160-187), flag for flag with its defaults, for
     ``mulut_amd.train_model``.  ``parse()`` makes ``expDir`` and ``{expDir}/val`` (``opt.valoutDir``), writes ``opt.txt`` as the
     reference does, applies ``--debug``'s short schedule (:147-151) and, like ``TestOptions``, copies the code only with
-    ``--saveCode``.  Additions default to the reference's behaviour: ``--torchPath``, ``--hostData``, ``--seed``, ``--deterministic``, ``--saveOpt``."""
+    ``--saveCode``.  Additions default to the reference's behaviour: ``--torchPath``, ``--hostData``, ``--seed``, ``--deterministic``, ``--saveOpt``, ``--valResident`` with ``--valSave`` and ``--valWorkers``."""
 
     def __init__(self, debug=False):
         self.debug = debug
@@ -144,6 +157,7 @@ class TrainOptions:
                                  "draws' generator state), which --startIter loads when it exists: an exact resume")
         parser.add_argument('--saveCode', action='store_true', default=False,
                             help="copy *.py under cwd into <expDir>/code like the reference's parse()")
+        add_resident_validation(parser)
         return parser
 
     def parse(self, argv=None):

@@ -14,6 +14,10 @@ the checkpoint had `--saveOpt`: then `Opt_{N:06d}.pth` (the name the reference's
 `opt_G.state_dict()` and the state of the crop draws' generator, both are loaded, and the run goes on exactly where the other stood.
 `--deterministic` trains on `mulut_net_stage_backward_exact`: the input gradient of a stage is gathered in a fixed order, so with
 `--seed` two runs write the same `Model_*.pth`, tensor for tensor (it has no meaning for `--torchPath` and is refused with it).
+`--valResident` keeps the validation sets on the device for the whole run (`net_val.NetValSet`, built once before the loop under half
+the free device memory; a set that needs more is said and validated by `net_valid_steps`): a point is then one list launch of the
+cascade per stage and dataset (`NetPlan.run`) and one read-back of the results, scored with the host loop's arithmetic and encoded
+behind the loop on `--valWorkers` threads, per `--valSave every|last|never`; the writer is joined, and a failed write raised, before `Complete`.
 `--gpuNum > 1` is refused.
 """
 import math
@@ -28,7 +32,8 @@ from . import network
 from .ft_data import CropProvider, DeviceCropProvider, TrainingSetTooLarge
 from .net_engine import NetEngine
 from .net_train import NetTrainer, torch_predict
-from .net_val import net_valid_steps
+from .ft_val import ValidationSetTooLarge
+from .net_val import NetValSet, net_valid_steps, resident_net_valid_steps
 from .options import TrainOptions
 
 
@@ -39,6 +44,16 @@ def save_checkpoint(model_G, opt, i, log, opt_G=None, train_iter=None):
     if opt.saveOpt:
         torch.save({"opt_G": opt_G.state_dict(), "rng": train_iter.rng.getstate()}, os.path.join(opt.expDir, 'Opt_{:06d}.pth'.format(i)))
     log("Checkpoint saved {}".format(str(i)))
+
+
+def resident_val_set(opt, log=print):
+    """--valResident: the validation sets on the device, built once, under half the free device memory; None, and said, if they
+    need more -- the run then validates with net_valid_steps."""
+    try:
+        return NetValSet(opt, max_bytes=torch.cuda.mem_get_info()[0] // 2, workers=opt.valWorkers)
+    except ValidationSetTooLarge as e:
+        log("{} | validation set of {} bytes exceeds half the free device memory ({}): validation runs on the host loop".format(opt.expDir, e.nbytes, e.limit))
+        return None
 
 
 def train(opt, log=print):
@@ -93,50 +108,57 @@ def train(opt, log=print):
     engine = None
     if not os.path.isdir(opt.valDir):      # (the reference's SRBenchmark would fail here; a run without validation sets is allowed, and said)
         log("{} | valDir {} is not a directory: validation is skipped".format(opt.expDir, opt.valDir))
+    vset = resident_val_set(opt, log) if opt.valResident and os.path.isdir(opt.valDir) else None
     l_accum = [0., 0., 0.]
     dT = 0.
     rT = 0.
     accum_samples = 0
     losses = []
     opt.lrTrace = []      # the learning rate of every iteration run, for callers
-    for i in range(opt.startIter + 1, opt.totalIter + 1):
-        model_G.train()
-        st = time.time()
-        im, lb = train_iter.next()
-        dT += time.time() - st
+    try:
+        for i in range(opt.startIter + 1, opt.totalIter + 1):
+            model_G.train()
+            st = time.time()
+            im, lb = train_iter.next()
+            dT += time.time() - st
 
-        st = time.time()
-        opt_G.zero_grad()
-        opt.lrTrace.append(opt_G.param_groups[0]['lr'])
-        pred = torch_predict(model_G, im, modes, stages, 'train') if trainer is None else trainer.predict(im, 'train')
-        loss_G = F.mse_loss(pred, lb)
-        loss_G.backward()
-        opt_G.step()
-        scheduler.step()
-        rT += time.time() - st
+            st = time.time()
+            opt_G.zero_grad()
+            opt.lrTrace.append(opt_G.param_groups[0]['lr'])
+            pred = torch_predict(model_G, im, modes, stages, 'train') if trainer is None else trainer.predict(im, 'train')
+            loss_G = F.mse_loss(pred, lb)
+            loss_G.backward()
+            opt_G.step()
+            scheduler.step()
+            rT += time.time() - st
 
-        accum_samples += opt.batchSize
-        losses.append(loss_G.item())
-        l_accum[0] += losses[-1]
-        if i % opt.displayStep == 0:
-            if writer is not None:
-                writer.add_scalar('loss_Pixel', l_accum[0] / opt.displayStep, i)
-            log("{} | Iter:{:6d}, Sample:{:6d}, GPixel:{:.2e}, dT:{:.4f}, rT:{:.4f}".format(
-                opt.expDir, i, accum_samples, l_accum[0] / opt.displayStep, dT / opt.displayStep, rT / opt.displayStep))
-            l_accum = [0., 0., 0.]
-            dT = 0.
-            rT = 0.
-        if i % opt.saveStep == 0:
-            save_checkpoint(model_G, opt, i, log, opt_G, train_iter)
-        if i % opt.valStep == 0 and os.path.isdir(opt.valDir):
-            if engine is None:
-                engine = NetEngine(model_G, device=next(model_G.parameters()).device.index)
-            engine.load_weights(model_G)
-            res = net_valid_steps(engine, opt, i, log)
-            if writer is not None:
-                for ds, psnrs in res.items():
-                    writer.add_scalar('PSNR_valid/{}'.format(ds), float(psnrs.mean()), i)
-                writer.flush()
+            accum_samples += opt.batchSize
+            losses.append(loss_G.item())
+            l_accum[0] += losses[-1]
+            if i % opt.displayStep == 0:
+                if writer is not None:
+                    writer.add_scalar('loss_Pixel', l_accum[0] / opt.displayStep, i)
+                log("{} | Iter:{:6d}, Sample:{:6d}, GPixel:{:.2e}, dT:{:.4f}, rT:{:.4f}".format(
+                    opt.expDir, i, accum_samples, l_accum[0] / opt.displayStep, dT / opt.displayStep, rT / opt.displayStep))
+                l_accum = [0., 0., 0.]
+                dT = 0.
+                rT = 0.
+            if i % opt.saveStep == 0:
+                save_checkpoint(model_G, opt, i, log, opt_G, train_iter)
+            if i % opt.valStep == 0 and os.path.isdir(opt.valDir):
+                if engine is None:
+                    engine = NetEngine(model_G, device=next(model_G.parameters()).device.index)
+                engine.load_weights(model_G)
+                res = net_valid_steps(engine, opt, i, log) if vset is None else resident_net_valid_steps(engine, vset, opt, i, log)
+                if writer is not None:
+                    for ds, psnrs in res.items():
+                        writer.add_scalar('PSNR_valid/{}'.format(ds), float(psnrs.mean()), i)
+                    writer.flush()
+        if vset is not None:      # the files of the last point are on disk, or the writer's failure is raised here
+            vset.join()
+    finally:      # (also when a step or a point raised: the set's threads, plans and pinned buffer do not wait for the collector)
+        if vset is not None:
+            vset.close()
     log("Complete")
     if engine is not None:
         engine.close()

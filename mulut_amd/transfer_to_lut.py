@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import network
-from .options import TestOptions
+from .options import TestOptions, add_resident_validation
 
 
 def get_input_tensor(opt, device=None):
@@ -90,7 +90,8 @@ def transfer(model_G, opt, device=None, save=True, engine=None, net_engine=None)
 
 
 class TransferOptions(TestOptions):
-    """The test-time flags plus the two of this script: --fused, and the validation sets of sr/1_train_model.py for it."""
+    """The test-time flags plus those of this script: --fused, the validation sets of sr/1_train_model.py for it, and --valResident
+    (with --valSave, --valWorkers) to validate from a device-resident set as `train_model --valResident` does."""
 
     def initialize(self, parser):
         parser = super().initialize(parser)
@@ -100,6 +101,7 @@ class TransferOptions(TestOptions):
                             help="with --fused: validate the loaded checkpoint on the sets under this folder first "
                                  "(the 'AVG Val PSNR' lines of sr/1_train_model.py:70-117)")
         parser.add_argument('--valoutDir', type=str, default=None, help='default: {expDir}/val')
+        add_resident_validation(parser)
         return parser
 
 
@@ -121,7 +123,20 @@ def main(argv=None):
     if opt.valDir is not None:
         if opt.valoutDir is None:
             opt.valoutDir = os.path.join(opt.expDir, "val")
-        net_valid_steps(net_engine, opt, opt.loadIter)
+        vset = None
+        if opt.valResident and os.path.isdir(opt.valDir):
+            from .train_model import resident_val_set
+            opt.totalIter = opt.valStep = opt.loadIter      # this run's single point is its last (--valSave last)
+            vset = resident_val_set(opt)
+        if vset is None:
+            net_valid_steps(net_engine, opt, opt.loadIter)
+        else:
+            from .net_val import resident_net_valid_steps
+            try:
+                resident_net_valid_steps(net_engine, vset, opt, opt.loadIter)
+                vset.join()
+            finally:
+                vset.close()
     return transfer(model_G, opt, device, net_engine=net_engine)
 
 
